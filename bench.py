@@ -19,6 +19,13 @@ are outside `./final`'s compute phase, whose `--timing` shows the same kernel ti
 13.15 ms kernel, 13.26 ms/step here).
 Weak scaling: --records-per-gpu is fixed per rank, the global batch grows with N.
 
+A plain run sets up, warms up, times the steps and prints the result line. --full adds what the headline
+figure does not need: the verification of the results against the CPU engine (`verified`) and the
+wall-clock of `mpiexec -np N ./final < input6.txt` (`final_input6_wall`, `final_input6_wall_hip`); without it
+those fields are null. --dump-outputs DIR writes what the last timed step computed: the (score, n, k)
+triples of a fixed, seeded sample of each rank's records (DIR/results_rank<r>.npy, float64 [m, 3]) and the
+sampled record numbers (DIR/sample_rank<r>.npy). The same arguments give the same inputs and the same sample.
+
 Run: python bench.py [--gpus N --steps K --warmup W]. With N > 1 and no torch.distributed environment
 (WORLD_SIZE unset) the script launches itself: a child `python -m torch.distributed.run
 --nproc-per-node N --master-addr 127.0.0.1 bench.py ...` started before anything touches the GPU, whose
@@ -51,12 +58,19 @@ def parse_args():
     ap.add_argument("--shape", default="input6")
     ap.add_argument("--shm", type=int, default=1, help="1: node-shared /dev/shm arrays; 0: private pinned")
     ap.add_argument("--host-alloc", default="", help="'hip': private hipHostMalloc arrays (overrides --shm)")
-    ap.add_argument("--verify", type=int, default=20000, help="records per rank checked against the CPU engine")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the results against the CPU engine (--verify) and time ./final on "
+                         "input6.txt (--final-wall); a plain run only measures the headline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's results (a seeded sample of each rank's records, as "
+                         "float64 (score, n, k) rows) to DIR/results_rank<r>.npy")
+    ap.add_argument("--verify", type=int, default=20000,
+                    help="with --full: records per rank checked against the CPU engine")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--dist-backend", default="nccl", help="nccl (RCCL, default) | gloo (multi-rank rehearsal)")
     ap.add_argument("--numa", type=int, default=1, help="bind each rank to its GPU's NUMA node")
     ap.add_argument("--final-wall", type=int, default=1,
-                    help="1: also time `mpiexec -np N ./final < input6.txt` (median of 5, checked vs the golden)")
+                    help="with --full, 1: time `mpiexec -np N ./final < input6.txt` (median of 5, checked vs the golden)")
     ap.add_argument("--dump-steps", default="", help="rank 0 writes its per-step kernel and host ms to this JSON file")
     ap.add_argument("--dry-launch", action="store_true",
                     help="print the self-launch command (JSON) for --gpus N > 1 and exit; touches no GPU")
@@ -294,6 +308,65 @@ class HostArrays:
                 pass
 
 
+def dump_outputs(out_dir, rank, world, wire, eng, seed=20240, budget=1 << 20):
+    """Writes what the last step left in this rank's result array, as a caller of the step receives it:
+    (score, n, k) of a fixed sample of the records (the same record numbers for the same arguments, the
+    last records among them: the persistent grid's tail tiles), float64 [m, 3], and the record numbers.
+    `budget` sampled records are shared by the ranks, so a dump stays near 32 MB whatever the rank count."""
+    from mpi_openmp_cuda_amd.ops.align import as_triples
+
+    n = wire.n
+    m = max(1, budget // world)
+    if n <= m:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        tail = min(4096, m // 2)
+        idx = np.unique(np.concatenate([np.random.default_rng(seed + rank).integers(0, n, size=m - tail),
+                                        np.arange(n - tail, n)]))
+    r2 = eng.r2_params(wire.l2_min, wire.l2_max) if wire.fmt == "r2" else None
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"results_rank{rank}.npy"), as_triples(wire.results[idx], r2=r2).astype(np.float64))
+    np.save(os.path.join(out_dir, f"sample_rank{rank}.npy"), idx.astype(np.float64))
+
+
+def verify(args, shape, seq1, host, eng, step, barrier):
+    """--full, untimed: the result array is poisoned and one more step is run, so a step that skipped work
+    (stale results from an earlier step) cannot pass; a sample is checked vs the CPU engine. 1 when all agree."""
+    from mpi_openmp_cuda_amd import Problem, search_cpu
+    from mpi_openmp_cuda_amd.ops.align import as_triples
+
+    wire = host.wire
+    R = wire.n
+    res = wire.results
+    # poison: R2's 0xFFFF is also its "no candidate" code, a sentinel only when every record has a candidate
+    # (|Seq2| < |Seq1| for the whole shape); R4/R8/R12 all-zero rows never occur (n or k or score non-zero
+    # is not guaranteed either, so those check the decoded sample only)
+    sentinel = res.dtype.kind == "u" and shape.l2_max < shape.L1
+    res[:] = np.iinfo(res.dtype).max if res.dtype.kind == "u" else 0
+    step()
+    barrier()
+    nv = min(args.verify, R)
+    while nv > 0 and int(wire.offsets[nv]) > host.check_letters.shape[0]:
+        nv //= 2
+    ok = 1
+    if nv > 0:
+        sub = Problem(shape.weights, seq1, host.check_letters[:int(wire.offsets[nv])], wire.offsets[:nv + 1].copy())
+        ref = as_triples(search_cpu(sub))
+        ok = int(np.array_equal(wire.triples(eng, nv), ref))
+        # a sample from the end of the slice, where the persistent grid runs its tail tiles: letters decoded
+        # back from the wire form, every result of the sample checked against the CPU engine
+        nt = min(nv, R)
+        t0 = int(wire.offsets[R - nt])
+        sub_t = Problem(shape.weights, seq1, wire.letters(t0, wire.total), wire.offsets[R - nt:] - t0)
+        r2 = eng.r2_params(wire.l2_min, wire.l2_max) if wire.fmt == "r2" else None
+        ok &= int(np.array_equal(as_triples(res[R - nt:], r2=r2), as_triples(search_cpu(sub_t))))
+        # and the tail of the batch was written by the last step too (no sentinel left anywhere)
+        tail = res[R - min(R, 1 << 16):]
+        if sentinel:
+            ok &= int(not (tail == np.iinfo(res.dtype).max).any())
+    return ok
+
+
 def main():
     args = parse_args()
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dry_launch):
@@ -304,9 +377,8 @@ def main():
     import torch
     import torch.distributed as dist
 
-    from mpi_openmp_cuda_amd import HipSearchEngine, Problem, search_cpu
+    from mpi_openmp_cuda_amd import HipSearchEngine
     from mpi_openmp_cuda_amd._lib import Pinned
-    from mpi_openmp_cuda_amd.ops.align import as_triples
     from mpi_openmp_cuda_amd.utils.synthetic import SHAPES
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -427,40 +499,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     st = eng.stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, wire, eng)
 
-    # ---- verification (untimed): the result array is poisoned and one more step is run, so a step that
-    # skipped work (stale results from an earlier step) cannot pass; a sample is checked vs the CPU engine
-    res = wire.results
-    # poison: R2's 0xFFFF is also its "no candidate" code, a sentinel only when every record has a candidate
-    # (|Seq2| < |Seq1| for the whole shape); R4/R8/R12 all-zero rows never occur (n or k or score non-zero
-    # is not guaranteed either, so those check the decoded sample only)
-    sentinel = res.dtype.kind == "u" and shape.l2_max < shape.L1
-    res[:] = np.iinfo(res.dtype).max if res.dtype.kind == "u" else 0
-    step()
-    barrier()
-    nv = min(args.verify, R)
-    while nv > 0 and int(wire.offsets[nv]) > host.check_letters.shape[0]:
-        nv //= 2
-    ok = 1
-    if nv > 0:
-        sub = Problem(shape.weights, seq1, host.check_letters[:int(wire.offsets[nv])], wire.offsets[:nv + 1].copy())
-        ref = as_triples(search_cpu(sub))
-        ok = int(np.array_equal(wire.triples(eng, nv), ref))
-        # a sample from the end of the slice, where the persistent grid runs its tail tiles: letters decoded
-        # back from the wire form, every result of the sample checked against the CPU engine
-        nt = min(nv, R)
-        t0 = int(wire.offsets[R - nt])
-        sub_t = Problem(shape.weights, seq1, wire.letters(t0, wire.total), wire.offsets[R - nt:] - t0)
-        r2 = eng.r2_params(wire.l2_min, wire.l2_max) if wire.fmt == "r2" else None
-        ok &= int(np.array_equal(as_triples(res[R - nt:], r2=r2), as_triples(search_cpu(sub_t))))
-        # and the tail of the batch was written by the last step too (no sentinel left anywhere)
-        tail = res[R - min(R, 1 << 16):]
-        if sentinel:
-            ok &= int(not (tail == np.iinfo(res.dtype).max).any())
-    ok &= int(np.array_equal(header.cpu().numpy(), hdr_host))  # the header every step broadcast is the one used
-    okt = torch.tensor([ok], dtype=torch.int32, device=cdev)
-    if distributed:
-        dist.all_reduce(okt, op=dist.ReduceOp.MIN)
+    verified = None
+    if args.full:
+        ok = verify(args, shape, seq1, host, eng, step, barrier)
+        ok &= int(np.array_equal(header.cpu().numpy(), hdr_host))  # the header every step broadcast is the one used
+        okt = torch.tensor([ok], dtype=torch.int32, device=cdev)
+        if distributed:
+            dist.all_reduce(okt, op=dist.ReduceOp.MIN)
+        verified = bool(okt.item())
 
     total_records = R * world
     total_elems = wire.total * world  # per-rank chars ~ equal (same length distribution)
@@ -484,11 +533,11 @@ def main():
         per_rank = torch.stack(allv).cpu().numpy()
     else:
         per_rank = mine.cpu().numpy()[None, :]
-    # the literal wall-clock of the reference invocation on input6.txt at this rank count (rank 0, untimed,
-    # after the steps; the other ranks wait at the barrier below)
-    wall6 = final_input6_wall(world) if (rank == 0 and args.final_wall) else None
-    wall6_hip = (final_input6_wall(world, extra=("--backend=hip",), spacing=1.0)
-                 if (rank == 0 and args.final_wall) else None)
+    # --full: the literal wall-clock of the reference invocation on input6.txt at this rank count (rank 0,
+    # untimed, after the steps; the other ranks wait at the barrier below)
+    final_wall = rank == 0 and args.full and args.final_wall
+    wall6 = final_input6_wall(world) if final_wall else None
+    wall6_hip = final_input6_wall(world, extra=("--backend=hip",), spacing=1.0) if final_wall else None
     ms_per_step = elapsed / args.steps * 1e3
     value = total_elems * args.steps / elapsed
     cells_per_rec = float(np.mean([(shape.L1 - l + 1) * l for l in range(shape.l2_min, shape.l2_max + 1)]))
@@ -540,7 +589,8 @@ def main():
             "rank_pci_bus": [pci_bus_id(int(x)) for x in per_rank[:, 7]],
             "rank0_kernels": st["kernels"],
             "host_stream": "zero_copy" if st["direct"] else "staged",
-            "verified": bool(okt.item()),
+            "full": bool(args.full),
+            "verified": verified,  # None: not checked (a plain run; --full checks)
             # each timed step broadcasts the header over the process group (N > 1) but the engine's image
             # comes from the host copy made before the loop (set_problem of an unchanged problem is a
             # no-op), as the reference broadcasts it once per job (main.c:149-150)

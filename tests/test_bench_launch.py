@@ -1,5 +1,6 @@
 """bench.py launcher contract (CPU only, no GPU touched): --gpus N > 1 outside torch.distributed launches
-N ranks itself, and a rank count that does not match --gpus fails instead of reporting fewer GPUs."""
+N ranks itself, and a rank count that does not match --gpus fails instead of reporting fewer GPUs. The one
+GPU test runs a plain and a --full benchmark on a small batch and compares what --dump-outputs wrote."""
 import json
 import os
 import subprocess
@@ -75,8 +76,16 @@ def test_kfd_gpu_count_from_sysfs(tmp_path):
     assert b.kfd_gpu_count(str(nodes), env={"HIP_VISIBLE_DEVICES": "0,2"}) == 2
     assert b.kfd_gpu_count(str(nodes), env={"ROCR_VISIBLE_DEVICES": ""}) == 0
     assert b.kfd_gpu_count(str(tmp_path / "absent"), env={}) is None
-    # this container: no GPU nodes (or no KFD at all) -> the 2-GPU launch refusal above comes from sysfs
-    assert b.kfd_gpu_count(env={}) in (None, 0)
+    # the machine's own topology: without a GPU no GPU nodes (or no KFD at all) -> the 2-GPU launch refusal
+    # above comes from sysfs; with GPUs the count the runtime reports
+    from conftest import gpu_available
+
+    if gpu_available():
+        import torch
+
+        assert b.kfd_gpu_count() == torch.cuda.device_count()
+    else:
+        assert b.kfd_gpu_count(env={}) in (None, 0)
 
 
 def test_kfd_gpu_count_8gpu_node(tmp_path):
@@ -137,7 +146,7 @@ def test_pci_bus_code_roundtrip():
 
 @pytest.mark.parametrize("np_", [1, 2])
 def test_final_input6_wall(np_):
-    # the BASELINE metric's wall-clock half, reported by every bench run: the reference invocation on
+    # the BASELINE metric's wall-clock half, reported by every bench.py --full run: the reference invocation on
     # input6.txt at the run's rank count, each output checked against the golden
     import bench
 
@@ -145,3 +154,63 @@ def test_final_input6_wall(np_):
     if r is None:
         pytest.skip("./final or mpiexec not built here")
     assert r["ok"] and r["np"] == np_ and 0 < r["best_s"] <= r["wall_s"] < 60
+
+
+def test_plain_run_options():
+    # --full is off by default: a plain run neither verifies nor times ./final; --dump-outputs names a directory
+    b = _bench_module()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]
+        a = b.parse_args()
+        assert not a.full and a.dump_outputs == "" and a.steps == 3 and a.warmup == 1
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        a = b.parse_args()
+        assert a.full and a.dump_outputs == "out"
+    finally:
+        sys.argv = argv
+
+
+def test_dump_outputs_sample(tmp_path):
+    # the dump is the (score, n, k) rows of a seeded sample of the result array: the same records every
+    # time, the slice's tail among them, float64, bounded by the budget shared between the ranks
+    import numpy as np
+
+    b = _bench_module()
+    n = 10000
+    res = np.arange(3 * n, dtype=np.int32).reshape(n, 3)
+    wire = types.SimpleNamespace(n=n, results=res, fmt="r12", l2_min=6, l2_max=11)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), 0, 2, wire, None, budget=2000)
+    got, idx = np.load(tmp_path / "a" / "results_rank0.npy"), np.load(tmp_path / "a" / "sample_rank0.npy")
+    assert got.dtype == np.float64 and idx.dtype == np.float64 and got.shape == (idx.shape[0], 3)
+    assert 500 < idx.shape[0] <= 1000 and idx[-1] == n - 1 and (np.diff(idx) > 0).all()
+    assert np.array_equal(got, res[idx.astype(np.int64)])
+    assert np.array_equal(got, np.load(tmp_path / "b" / "results_rank0.npy"))
+    # another rank samples other records; a slice within the budget is written whole
+    b.dump_outputs(str(tmp_path / "a"), 1, 2, wire, None, budget=2000)
+    assert not np.array_equal(idx[:100], np.load(tmp_path / "a" / "sample_rank1.npy")[:100])
+    b.dump_outputs(str(tmp_path / "c"), 0, 1, wire, None, budget=1 << 20)
+    assert np.array_equal(np.load(tmp_path / "c" / "results_rank0.npy"), res)
+
+
+@pytest.mark.gpu
+def test_plain_and_full_runs_dump_the_same_outputs(tmp_path):
+    # a plain run reports the headline without the checks (verified: null) and writes what its last timed
+    # step computed; --full computes the same from the same inputs, and verifies it against the CPU engine
+    import numpy as np
+
+    lines = {}
+    for mode in ("plain", "full"):
+        r = run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--records-per-gpu", "70001", "--final-wall", "0",
+                 "--dump-outputs", str(tmp_path / mode)] + (["--full"] if mode == "full" else []))
+        assert r.returncode == 0, r.stderr.decode()
+        lines[mode] = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    for d in lines.values():
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "elements/s" and d["higher_is_better"]
+        assert abs(d["ms_per_step"] - d["wall_clock_s"] * 1e3 / 3) < 1e-3
+    assert lines["plain"]["verified"] is None and not lines["plain"]["full"]
+    assert lines["full"]["verified"] is True and lines["full"]["full"]
+    a, f = (np.load(tmp_path / m / "results_rank0.npy") for m in ("plain", "full"))
+    assert a.dtype == np.float64 and a.shape == (70001, 3) and np.array_equal(a, f)
+    assert np.array_equal(np.load(tmp_path / "plain" / "sample_rank0.npy"), np.arange(70001))

@@ -6,7 +6,7 @@
 #
 #   tier          the GPU test tier (pytest -m gpu)
 #   smoke         __graft_entry__.smoke()
-#   bench         python bench.py --steps 50 --warmup 5 (headline line with both wall-clock fields)
+#   bench         python bench.py --full --steps 50 --warmup 5 (headline line, verified, with both wall-clock fields)
 #   bench-trace   rocprofv3 kernel trace + stats of 20 headline steps -> gpurun_out/bench_trace/
 #   wall          mpiexec -np 1/2/4 ./final < input1..6 (default engine) beside mpi_hello / hip_hello
 #   wall-hip      the same forced onto the GPU (--backend=hip), launches 1 s apart, with --timing (np 1/2)
@@ -32,7 +32,7 @@ for c in "$@"; do
   case $c in
     tier) steps+=("tier$sfx:900:python -u -m pytest -q --timeout 200 --timeout-method thread tests/ -m gpu") ;;
     smoke) steps+=("smoke$sfx:300:python -c 'import __graft_entry__ as g; g.smoke()'") ;;
-    bench) steps+=("bench$sfx:300:python bench.py --steps 50 --warmup 5") ;;
+    bench) steps+=("bench$sfx:300:python bench.py --full --steps 50 --warmup 5") ;;
     bench-trace) steps+=("bench_trace$sfx:300:timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/bench_trace -o b -- python3 bench.py --steps 20 --warmup 5 --final-wall 0") ;;
     wall) steps+=("wall$sfx:400:NPS='1 2 4' REPS=7 HELLO=1 bash tools/final_walltime.sh") ;;
     wall-hip) steps+=("wall_hip$sfx:400:NPS='1 2' INPUTS='6 1 3 4' REPS=7 SPACING=1 HELLO=1 TIMING=1 EXTRA='--backend=hip --log-level=debug' bash tools/final_walltime.sh") ;;

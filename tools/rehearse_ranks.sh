@@ -1,6 +1,6 @@
 #!/bin/bash
 # Multi-rank rehearsal on the one MI355X of a gpurun box, before any 8-GPU node runs it:
-#   1. bench.py --gpus $NR --allow-shared-gpu --dist-backend gloo at the default per-rank size (NR x 285 M
+#   1. bench.py --full --gpus $NR --allow-shared-gpu --dist-backend gloo at the default per-rank size (NR x 285 M
 #      letters): the self-launch, the per-rank fields of the scaling record, the verification at NR ranks.
 #   2. ./final at 1.14 G letters (134 M input6-shaped records, 1.28 GB of text) on NPS ranks, all on
 #      --device=0, bulk and streamed (--batch-records=16777216): output md5 against np 1, per-rank --timing.
@@ -14,7 +14,7 @@ NPS=${NPS:-"1 4 8"}
 STEP=${STEP:-all}
 if [ "$STEP" = all ] || [ "$STEP" = bench ]; then
   echo "=== bench.py --gpus $NR (gloo, shared GPU)"
-  timeout -k 10 600 python3 bench.py --gpus $NR --allow-shared-gpu --dist-backend gloo --steps ${STEPS:-20} \
+  timeout -k 10 600 python3 bench.py --full --gpus $NR --allow-shared-gpu --dist-backend gloo --steps ${STEPS:-20} \
     --warmup 3 --final-wall ${FINAL_WALL:-0} > gpurun_out/rehearse_bench_$NR.json 2> gpurun_out/rehearse_bench_$NR.err || {
     tail -20 gpurun_out/rehearse_bench_$NR.err; exit 1; }
   cat gpurun_out/rehearse_bench_$NR.json
