@@ -115,6 +115,11 @@ int moc_engine_pin(void* e, const void* p, size_t bytes);
 int moc_engine_solve_wire_device(void* e, const uint8_t* d_letters, const int64_t* d_offsets, const uint8_t* d_lengths,
                                  int len_bits, int len_base, int64_t n, void* d_out, int fmt, int64_t min_l2,
                                  int64_t max_l2, int packed);
+// The same with sparse offsets (the rccl transport's batches): d_offsets holds one entry per 2^off_shift
+// records and the batch end (moc::sparse_count entries; off_shift 0: dense); narrow lengths are then required.
+int moc_engine_solve_wire_device_sparse(void* e, const uint8_t* d_letters, const int64_t* d_offsets, int off_shift,
+                                        const uint8_t* d_lengths, int len_bits, int len_base, int64_t n, void* d_out,
+                                        int fmt, int64_t min_l2, int64_t max_l2, int packed);
 // device time (ms) of the last moc_engine_solve_device's kernels; waits for them
 int moc_engine_device_kernel_ms(void* e, double* ms);
 int moc_engine_solve_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,

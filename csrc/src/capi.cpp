@@ -348,12 +348,21 @@ int moc_engine_solve_ex(void* e, const uint8_t* codes, const int64_t* offsets, c
 int moc_engine_solve_wire_device(void* e, const uint8_t* d_letters, const int64_t* d_offsets, const uint8_t* d_lengths,
                                  int len_bits, int len_base, int64_t n, void* d_out, int fmt, int64_t min_l2,
                                  int64_t max_l2, int packed) {
+  return moc_engine_solve_wire_device_sparse(e, d_letters, d_offsets, 0, d_lengths, len_bits, len_base, n, d_out, fmt,
+                                             min_l2, max_l2, packed);
+}
+
+int moc_engine_solve_wire_device_sparse(void* e, const uint8_t* d_letters, const int64_t* d_offsets, int off_shift,
+                                        const uint8_t* d_lengths, int len_bits, int len_base, int64_t n, void* d_out,
+                                        int fmt, int64_t min_l2, int64_t max_l2, int packed) {
   return guard([&] {
     if (packed != 0 && packed != 3) throw moc::Error("device-resident letters: 0 bytes or 3 P33 fields");
+    if (off_shift < 0 || off_shift > 6) throw moc::Error("sparse offsets: one per 2^shift records, shift 0..6");
     moc::WireBatch b;
     b.letters = d_letters;
     b.packed33 = packed == 3;
     b.offsets = d_offsets;
+    b.off_shift = off_shift;
     b.lengths = d_lengths;
     b.len_bits = len_bits;
     b.len_base = len_base;

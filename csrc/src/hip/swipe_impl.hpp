@@ -772,7 +772,7 @@ void swipe_direct_kernel(ProblemView pv, ShortArgs a, SwipeLayout lay) {
   load_meta(t, o0, o1);
   for (; t < n_tiles; t += waves) {  // wave-uniform
     uint32_t wd[L2W];
-    int L2h[H], excl[H];  // the halves' lengths and (P33) their records' starts within the tile
+    int L2h[H], excl[H] = {};  // the halves' lengths and (P33) their records' starts within the tile
 #pragma unroll
     for (int h = 0; h < H; ++h) L2h[h] = static_cast<int>(P33 ? o1[h] : o1[0] - o0);
     auto searching = [&](int h, int L2) {  // others belong to the tile kernel
@@ -866,9 +866,10 @@ void swipe_direct_kernel(ProblemView pv, ShortArgs a, SwipeLayout lay) {
 // b.swipe_rk = RK); false when no instance matches.
 // The lane-direct kernel's grid: every block resident at once (the waves stride over the tiles statically,
 // so a block that only starts when another ends would run its share after everyone else), sized by the
-// occupancy the instance reaches.
-inline void launch_direct_instance(void (*kernel)(ProblemView, ShortArgs, SwipeLayout), const ProblemView& pv,
-                                   const ShortArgs& b, const SwipeLayout& lay, int num_cus, hipStream_t stream) {
+// occupancy the instance reaches. `halves`: the instance's 64-record halves per tile (direct_halves).
+inline void launch_direct_instance(void (*kernel)(ProblemView, ShortArgs, SwipeLayout), int halves,
+                                   const ProblemView& pv, const ShortArgs& b, const SwipeLayout& lay, int num_cus,
+                                   hipStream_t stream) {
   constexpr int block = kBlockD;
   int occ = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kernel), block, lay.total) !=
@@ -877,7 +878,7 @@ inline void launch_direct_instance(void (*kernel)(ProblemView, ShortArgs, SwipeL
     (void)hipGetLastError();
     occ = 1;
   }
-  const int64_t tiles = (b.n + 63) >> 6;
+  const int64_t tiles = (b.n + 64 * halves - 1) / (64 * halves);
   const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + block / 64 - 1) / (block / 64),
                                                                 static_cast<int64_t>(occ) * num_cus));
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(block), lay.total, stream, pv, b, lay);
@@ -892,7 +893,8 @@ bool launch_swipe_noff(const ProblemView& pv, const ShortArgs& b, const SwipeLay
   if (l2w == LW && rk == RKV) {                                                                            \
     if constexpr (LF == 0 || LW <= 16) { /* P33 records over 64 letters: the block-tiled kernel */        \
       if (b.lane_direct) {                                                                                 \
-        launch_direct_instance(&swipe_direct_kernel<NO, LW, LF, RKV>, pv, b, lay, num_cus, stream);       \
+        launch_direct_instance(&swipe_direct_kernel<NO, LW, LF, RKV>, direct_halves(LF, LW, NO), pv, b, lay, \
+                               num_cus, stream);                                                           \
         return true;                                                                                       \
       }                                                                                                    \
     }                                                                                                      \

@@ -241,29 +241,37 @@ class HipSearchEngine:
         return out_t
 
     def solve_wire_device(self, letters_t, offsets_t, lengths_t, n: int, out_t, fmt: str, l2_range,
-                          lengths_bits: int = 8, lengths_base: int = 0, packed33: bool = True):
+                          lengths_bits: int = 8, lengths_base: int = 0, packed33: bool = True, off_shift: int = 0):
         """Device-resident batch in the wire formats (torch tensors on this engine's GPU, as the rccl transport
         holds them): ``letters_t`` P33 fields (``packed33``) or bytes, ``offsets_t`` int64 [n + 1] letter
         offsets, ``lengths_t`` narrow lengths (as ``solve``'s) or None, results into ``out_t`` (a uint8
-        tensor of n * itemsize bytes of ``fmt``, decoded on the host as ``solve``'s). Synchronous;
-        ``stats()["kernel_ms"]`` is the kernel's time."""
+        tensor of n * itemsize bytes of ``fmt``, decoded on the host as ``solve``'s). ``off_shift`` > 0:
+        ``offsets_t`` is sparse, one entry per 2^off_shift records and the batch end (``sparse_offsets``),
+        and ``lengths_t`` is required; the sparse form trusts ``l2_range`` (the lengths are narrow fields in device
+        memory: the check below needs dense offsets). Synchronous; ``stats()["kernel_ms"]`` is the kernel's time."""
         import torch
 
         fid = _format_id(fmt)
-        assert letters_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        entries = n + 1 if not off_shift else ((n + (1 << off_shift) - 1) >> off_shift) + 1
+        assert letters_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == entries
         assert out_t.dtype == torch.uint8 and out_t.numel() >= n * _lib.FORMAT_DTYPES[fid].itemsize
-        if n > 0:
+        assert not off_shift or lengths_t is not None, "sparse offsets need narrow lengths"
+        if n > 0 and not off_shift:
             # the kernel sizes its LDS and per-lane record words from l2_range and cannot re-scan device
-            # lengths: a range narrower than the batch would give wrong results, so it is checked here
+            # lengths: a range narrower than the batch would give wrong results, so it is checked here (dense
+            # offsets only: sparse ones do not hold the lengths, and the caller's range is taken as stated)
             d = offsets_t[1:] - offsets_t[:-1]
             lo, hi = int(d.min()), int(d.max())
             if lo < int(l2_range[0]) or hi > int(l2_range[1]):
                 raise ValueError(f"l2_range {tuple(l2_range)} does not hold the batch's lengths [{lo}, {hi}]")
         lp = ctypes.c_void_p(lengths_t.data_ptr()) if lengths_t is not None else None
-        _lib.check(_lib.lib().moc_engine_solve_wire_device(
-            self._h, ctypes.c_void_p(letters_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), lp,
-            int(lengths_bits), int(lengths_base), int(n), ctypes.c_void_p(out_t.data_ptr()), fid, int(l2_range[0]),
-            int(l2_range[1]), 3 if packed33 else 0))
+        tail = (lp, int(lengths_bits), int(lengths_base), int(n), ctypes.c_void_p(out_t.data_ptr()), fid,
+                int(l2_range[0]), int(l2_range[1]), 3 if packed33 else 0)
+        head = (self._h, ctypes.c_void_p(letters_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()))
+        if off_shift:
+            _lib.check(_lib.lib().moc_engine_solve_wire_device_sparse(*head, int(off_shift), *tail))
+        else:
+            _lib.check(_lib.lib().moc_engine_solve_wire_device(*head, *tail))
         return out_t
 
     def device_kernel_ms(self) -> float:

@@ -101,6 +101,12 @@ class WireSlice:
         offsets = np.asarray(offsets, dtype=np.int64)
         return cls(np.diff(offsets), np.asarray(codes)[offsets[0]:offsets[-1]], **kw)
 
+    def sparse_offsets(self, shift: int = 6) -> np.ndarray:
+        """One offset per 2^shift records and the batch end (csrc/include/moc/wire.hpp: entry j = offset of
+        record min(j << shift, n)): what the streaming kernels read beside the narrow lengths."""
+        idx = np.minimum(np.arange(((self.n + (1 << shift) - 1) >> shift) + 1, dtype=np.int64) << shift, self.n)
+        return np.ascontiguousarray(self.offsets[idx])
+
     # ---- results
     def alloc_results(self, engine, fmt: str = "auto") -> np.ndarray:
         """Results in ``fmt`` (auto: the narrowest the engine can produce for this slice's lengths)."""
