@@ -54,7 +54,7 @@ COMM_OBJS := $(OBJ)/comm/comm.o $(OBJ)/comm/mpi_device_comm.o
 RCCL_OBJS := $(OBJ)/comm/rccl_comm.o
 HEADERS   := $(shell find csrc/include -name '*.h' -o -name '*.hpp')
 
-.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels
+.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san
 
 all: build
 build: lib final $(GPU_PLUGIN)
@@ -204,6 +204,18 @@ $(BUILD)/test_core: csrc/tests/test_core.cpp csrc/apps/text_cut.cpp csrc/apps/te
 
 unit: $(BUILD)/test_core
 	$(BUILD)/test_core
+
+# stand-alone ASan/UBSan check of the CPU engine's profile / top-K code (own main, host code only)
+profile-san: $(BUILD)/profile_san
+	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/profile_san
+PSAN_FLAGS := -O1 -g -std=c++17 -fopenmp -fsanitize=address,undefined -fno-omit-frame-pointer $(INC) \
+              -I$(ROCM)/include -D__HIP_PLATFORM_AMD__
+PSAN_OBJS  := $(patsubst csrc/src/%.cpp,$(BUILD)/psan/%.o,$(CPU_SRCS))
+$(BUILD)/psan/%.o: csrc/src/%.cpp $(HEADERS)
+	@mkdir -p $(dir $@)
+	$(CXX) $(PSAN_FLAGS) -c $< -o $@
+$(BUILD)/profile_san: csrc/tests/profile_san.cpp $(PSAN_OBJS) $(HEADERS)
+	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/profile_san.cpp $(PSAN_OBJS) -ldl
 
 # parser throughput (count vs fill, SIMD A/B): build/fill_bench [records]
 $(BUILD)/fill_bench: tools/fill_bench.cpp $(CPU_OBJS) $(HEADERS)

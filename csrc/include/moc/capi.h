@@ -67,6 +67,21 @@ int moc_cpu_solve_keys(const int32_t* weights4, const uint8_t* seq1, int64_t L1,
 int moc_resolve_keys(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
                      const int64_t* offsets, int64_t n, const uint64_t* keys, moc_result* out);
 
+/* ---- per-offset score profile and top-K alignments (moc/cpu_engine.hpp) ----
+ * A record's profile has C = moc_candidate_offsets(L1, L2, semantics) entries {int32 score, int32 k}: entry o is
+ * the best candidate at offset o. poffsets (n + 1, filled by the call) indexes the batch's flat profile; prof may
+ * be NULL to get poffsets alone. Top-K: out is int32 [n, K, 3] rows (score, n, k) in better() order, padded with
+ * (INT32_MIN, 0, 0); K outside 1..64 is an error. */
+typedef struct moc_profile_entry {
+  int32_t score, k;
+} moc_profile_entry;
+int64_t moc_candidate_offsets(int64_t L1, int64_t L2, int semantics);
+int moc_cpu_profile(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                    const int64_t* offsets, int64_t n, int semantics, int threads, int64_t* poffsets,
+                    moc_profile_entry* prof);
+int moc_cpu_topk(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                 const int64_t* offsets, int64_t n, int semantics, int threads, int K, moc_result* out);
+
 /* ---- partition ---- */
 int moc_partition(const int64_t* lengths, int64_t n, int64_t L1, int parts, double cell_w, double byte_w,
                   double record_w, int64_t* bounds_out /* parts+1 */);
@@ -131,6 +146,20 @@ int moc_engine_search_keys_device(void* e, const uint8_t* d_codes, const int64_t
 int moc_engine_finalize_keys_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
                                     int64_t n, const uint64_t* d_keys, void* d_out,
                                     int fmt, void* stream);
+/* Profile / top-K on the GPU (byte letters, dense offsets; moc/hip_engine.hpp). Host forms are synchronous
+ * (poffsets: n + 1 entries, filled; prof: poffsets[n] entries, NULL = poffsets alone); device forms queue on
+ * `stream` without a sync (d_prof: the flat profile in the host-computed poffsets order; d_out: [n, K, 3]). */
+int moc_engine_solve_profile(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int64_t* poffsets,
+                             moc_profile_entry* prof);
+int moc_engine_solve_topk(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int K, moc_result* out);
+int moc_engine_solve_profile_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                    int64_t n, moc_profile_entry* d_prof, void* stream);
+int moc_engine_solve_topk_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                 int64_t n, int K, moc_result* d_out, void* stream);
+/* bound (bytes) of the top-K profile scratch; a record larger than it still runs, alone in its chunk */
+int moc_engine_set_profile_scratch(void* e, int64_t bytes);
+/* device time (ms) of the last top-K call's select launches (engines started with MOC_PROFILE_TIMING=1; else 0) */
+int moc_engine_topk_select_ms(void* e, double* ms);
 /* stats: kernel_ms, total_ms, h2d_bytes, d2h_bytes, chunks, cells, records, direct, format, kernels,
  * r2 smin, r2 kw, r2 j, forms (moc::bounds::FormBits of the last solve) */
 int moc_engine_stats(void* e, double* out14);

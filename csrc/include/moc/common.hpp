@@ -48,6 +48,16 @@ constexpr int32_t kNoCandidateScore = std::numeric_limits<int32_t>::min();  // L
 
 inline Result no_candidate() { return Result{kNoCandidateScore, 0, 0}; }
 
+// One entry of a record's per-offset score profile: the best candidate at that offset (the smallest k
+// among equal scores, k = 0 first). The offset is the entry's index (moc/cpu_engine.hpp).
+struct ProfileEntry {
+  int32_t score;
+  int32_t k;
+};
+static_assert(sizeof(ProfileEntry) == 8, "ProfileEntry is one 8-byte device store");
+
+constexpr int kMaxTopK = 64;  // rows per record of a top-K search
+
 class Error : public std::runtime_error {
  public:
   explicit Error(const std::string& what) : std::runtime_error(what) {}

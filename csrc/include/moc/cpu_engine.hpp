@@ -64,6 +64,21 @@ Result resolve_key(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uin
 void solve_keys_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int part,
                     int parts, uint64_t* keys, Semantics sem, int num_threads = 0);
 
+// ---- per-offset score profile and top-K alignments
+// Profile of a record with C = candidate_offsets(L1, L2, sem) offsets: C entries, entry o = the best candidate
+// AT offset o — the maximum of score(o, 0) and, where mutated candidates exist (o < L1 - L2, k = 1..L2-1), of
+// score(o, k); ties go to the smallest k, k = 0 first. A batch's profile is one flat array indexed through
+// poffsets (int64[n+1], poffsets[i+1] - poffsets[i] = C_i). The better()-maximum over a record's profile is
+// solve_record's result. Built on the same one-pass-per-offset recurrence as solve_offsets.
+void profile_offsets(int64_t L1, const RecordBatch& batch, Semantics sem, int64_t* poffsets /* n + 1 */);
+void profile_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                       const int64_t* poffsets, ProfileEntry* prof, Semantics sem, int num_threads = 0);
+// Top-K, 1 <= K <= kMaxTopK: out[i*K .. i*K+K) = record i's min(K, C_i) best offsets in better() order (higher
+// score, then smaller n), each as (score, n, that offset's profile k), then no_candidate() rows. Row 0 is
+// solve_record's result. One record's profile exists at a time per thread, never the batch's.
+void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
+                    Semantics sem, int num_threads = 0);
+
 // Literal O(L1*L2^2) emulation of calc_result's loops (cudaFunctions.cu:74-172), race-free.
 // Test oracle only.
 Result brute_force_record(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2,

@@ -259,6 +259,26 @@ void launch_mfma_i8_probe(const int8_t* d_a, const int8_t* d_b, int* d_c, hipStr
 // Waves per CU the tile16 kernel keeps resident (16-wave workgroups, as many as the LDS allows).
 int tile16_waves_per_cu(int lds_bytes);
 
+// ---- per-offset score profile and top-K selection (profile_kernels.hip; definitions: moc/cpu_engine.hpp)
+// One chunk of consecutive records [rec0, rec0 + n) of a batch: `starts` is a wave plan in the LUT-tile
+// geometry (63·u offsets per wave tile) over ALL of the chunk's records, its li relative to rec0; `poffsets`
+// is the batch's profile index (n_batch + 1 entries, device) and the chunk's profile is written to
+// prof[poffsets[r] - base + o], base = poffsets[rec0].
+struct ProfileArgs {
+  const WaveStart* starts = nullptr;  // device, n_waves + 1 entries
+  int64_t n_waves = 0;
+  int32_t u = 2;                      // sub-tiles per wave tile (1, 2 or 4)
+  int64_t rec0 = 0;
+  const int64_t* poffsets = nullptr;
+  int64_t base = 0;
+  ProfileEntry* prof = nullptr;
+  int64_t prof_entries = 0;           // entries of `prof` (debug builds check the store index against it)
+};
+void launch_offset_profile(const ProblemView& pv, const BatchView& bv, const ProfileArgs& pa, hipStream_t stream);
+// The K best offsets of records [pa.rec0, pa.rec0 + n_rec) from their profile -> out[r * K + j] (batch-wide
+// record index r), padded with no_candidate(); 1 <= K <= kMaxTopK.
+void launch_topk_select(const ProfileArgs& pa, int64_t n_rec, int K, Result* out, hipStream_t stream);
+
 // Loads every kernel file's code object onto the current device now (HIP loads them lazily, at the first
 // launch from each file: milliseconds inside the first timed search of a job otherwise).
 void preload_align_kernels();
@@ -267,6 +287,7 @@ void preload_swipe_byte_kernels();
 void preload_swipe_p33_kernels();
 void preload_tile16_kernels();
 void preload_mfma_kernels();
+void preload_profile_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -275,7 +296,8 @@ enum PreloadSet : unsigned {
   kPreloadSwipeP33 = 8,
   kPreloadTile16 = 16,
   kPreloadMfma = 32,  // the measured-slower MFMA variant: only when it is selected (MOC_MFMA=1)
-  kPreloadAll = 31,   // all but MFMA
+  kPreloadAll = 31,   // all but MFMA and the profile file: existing jobs' start-up stays as it is
+  kPreloadProfile = 64,  // profile_kernels.hip: loads at its first launch unless named
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -284,8 +306,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadSwipeByte) preload_swipe_byte_kernels();
   if (set & kPreloadSwipeP33) preload_swipe_p33_kernels();
   if (set & kPreloadTile16) preload_tile16_kernels();
+  if (set & kPreloadProfile) preload_profile_kernels();
 }
-// "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma;
+// "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
+// profile;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

@@ -45,6 +45,10 @@ struct EngineOptions {
   // Pinned host batches stream zero-copy: the kernel reads / writes host memory itself. A chunked SDMA
   // pipeline around the HBM-resident kernel was measured slower on the registered node-shared arrays the
   // headline streams from (4.4 vs 4.0 ms/step, profiles/host_stream_ab.log) and was retired in round 4.
+  // Top-K: bound of the per-offset profile scratch (8 bytes per candidate offset). A batch runs in chunks of
+  // consecutive records whose profiles fit it; a record larger than the bound runs alone in its chunk.
+  // HipEngine::set_profile_scratch changes it at run time.
+  int64_t profile_scratch_bytes = 256ll << 20;
 };
 
 struct EngineStats {
@@ -54,7 +58,7 @@ struct EngineStats {
   int32_t direct = 0;    // 1 if the last solve streamed from pinned host memory (zero-copy)
   int32_t format = 0;    // ResultFormat of the last solve
   int32_t kernels = 0;   // bitmask of kernels used: 1 swipe (lane/record), 2 short (lane/offset), 4 tiles
-                         // (LUT tile kernel), 8 tile16
+                         // (LUT tile kernel), 8 tile16, 16 profile (per-offset profile / top-K)
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -114,6 +118,30 @@ class HipEngine {
   double device_kernel_ms();
   void solve_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
                     Result* d_out, hipStream_t stream);
+
+  // ---- per-offset score profile and top-K alignments (definitions: moc/cpu_engine.hpp; kernels:
+  // csrc/src/hip/profile_kernels.hip). Byte letters and dense int64 offsets only: wire-format and packed-letter
+  // inputs, the zero-copy path and the context-parallel split are not part of these calls.
+  // Device-resident forms, queued on `stream` (0 = engine compute stream) with no sync, like solve_device:
+  // d_prof receives the batch's flat profile (sum of candidate_offsets entries, record i's at the host-computed
+  // profile offset i), d_out the int32 [n, K, 3] top-K rows, 1 <= K <= kMaxTopK. Top-K never materialises the
+  // batch's profile: it runs chunk by chunk (profile kernel, then select) in a scratch bounded by
+  // EngineOptions::profile_scratch_bytes.
+  void solve_profile_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                            ProfileEntry* d_prof, hipStream_t stream);
+  void solve_topk_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n, int K,
+                         Result* d_out, hipStream_t stream);
+  // Host forms (upload through the pooled buffers; synchronous). prof_out holds poffsets_out[n] entries;
+  // poffsets_out (n + 1) is filled first and may be computed beforehand with profile_offsets().
+  void solve_profile(const uint8_t* codes, const int64_t* offsets, int64_t n, ProfileEntry* prof_out,
+                     int64_t* poffsets_out);
+  void solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, Result* out);
+  // poffsets[0..n]: record i's profile starts at entry poffsets[i] (this problem's L1 and semantics)
+  void profile_offsets(const int64_t* offsets, int64_t n, int64_t* poffsets) const;
+  void set_profile_scratch(int64_t bytes);
+  // Device time (ms) of the select launches of the last top-K call; recorded only when MOC_PROFILE_TIMING=1
+  // was set at engine start (an event pair per chunk), else 0. Waits for them.
+  double topk_select_ms();
 
   // Context-parallel search: this engine evaluates part `part` of `parts` of the batch's
   // global list of offset tiles and writes one packed 64-bit key per record (moc::encode_key; 0 =
@@ -189,6 +217,8 @@ class HipEngine {
   void run_staged(const uint8_t* codes, const int64_t* offsets, int64_t n, void* out, ResultFormat fmt,
                   bool packed5);
   void solve_wire_impl(const WireBatch& b, void* out, ResultFormat fmt, bool async);
+  void run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n, int K,
+                   void* d_dst, hipStream_t stream);
 
   EngineOptions opt_;
   int device_ = 0;
@@ -240,6 +270,12 @@ class HipEngine {
   size_t h_plan_cap_ = 0;
   hipEvent_t ev_plan_ = nullptr;
   hipEvent_t ev_d0_ = nullptr, ev_d1_ = nullptr;  // around solve_device's launches (device_kernel_ms)
+  // top-K: the chunks' profile scratch, and event pairs around the select launches (MOC_PROFILE_TIMING=1)
+  void* d_prof_scratch_ = nullptr;
+  size_t d_prof_scratch_cap_ = 0;
+  bool profile_timing_ = false;
+  std::vector<hipEvent_t> ev_select_;
+  size_t ev_select_used_ = 0;
   std::vector<void*> pinned_;
   struct DirectKey {
     dev::ProblemView pv;

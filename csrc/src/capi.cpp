@@ -21,6 +21,7 @@
 #include "moc/score_table.hpp"
 
 static_assert(sizeof(moc_result) == sizeof(moc::Result), "ABI result layout");
+static_assert(sizeof(moc_profile_entry) == sizeof(moc::ProfileEntry), "ABI profile entry layout");
 
 namespace {
 thread_local std::string g_err;
@@ -186,6 +187,37 @@ int moc_brute_force(const int32_t* weights4, const uint8_t* seq1, int64_t L1, co
                                               static_cast<moc::Semantics>(semantics));
       std::memcpy(out + i, &r, sizeof r);
     }
+  });
+}
+
+int64_t moc_candidate_offsets(int64_t L1, int64_t L2, int semantics) {
+  return moc::candidate_offsets(L1, L2, static_cast<moc::Semantics>(semantics));
+}
+
+int moc_cpu_profile(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                    const int64_t* offsets, int64_t n, int semantics, int threads, int64_t* poffsets,
+                    moc_profile_entry* prof) {
+  return guard([&] {
+    moc::Weights w = weights_of(weights4);
+    moc::RecordBatch b = view_batch(codes, offsets, n);
+    moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
+    const auto sem = static_cast<moc::Semantics>(semantics);
+    moc::profile_offsets(L1, b, sem, poffsets);
+    if (!prof) return;
+    moc::ScoreTable t = moc::ScoreTable::build(w);
+    moc::profile_batch_cpu(t, seq1, L1, b, poffsets, reinterpret_cast<moc::ProfileEntry*>(prof), sem, threads);
+  });
+}
+
+int moc_cpu_topk(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                 const int64_t* offsets, int64_t n, int semantics, int threads, int K, moc_result* out) {
+  return guard([&] {
+    moc::Weights w = weights_of(weights4);
+    moc::RecordBatch b = view_batch(codes, offsets, n);
+    moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
+    moc::ScoreTable t = moc::ScoreTable::build(w);
+    moc::topk_batch_cpu(t, seq1, L1, b, K, reinterpret_cast<moc::Result*>(out), static_cast<moc::Semantics>(semantics),
+                        threads);
   });
 }
 
@@ -427,6 +459,49 @@ int moc_engine_finalize_keys_device(void* e, const uint8_t* d_codes, const int64
                                                           static_cast<moc::ResultFormat>(fmt),
                                                           static_cast<hipStream_t>(stream));
   });
+}
+
+int moc_engine_solve_profile(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int64_t* poffsets,
+                             moc_profile_entry* prof) {
+  return guard([&] {
+    auto* eng = static_cast<moc::HipEngine*>(e);
+    if (!prof)
+      eng->profile_offsets(offsets, n, poffsets);
+    else
+      eng->solve_profile(codes, offsets, n, reinterpret_cast<moc::ProfileEntry*>(prof), poffsets);
+  });
+}
+
+int moc_engine_solve_topk(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int K, moc_result* out) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_topk(codes, offsets, n, K, reinterpret_cast<moc::Result*>(out));
+  });
+}
+
+int moc_engine_solve_profile_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                    int64_t n, moc_profile_entry* d_prof, void* stream) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_profile_device(d_codes, d_offsets, h_offsets, n,
+                                                          reinterpret_cast<moc::ProfileEntry*>(d_prof),
+                                                          static_cast<hipStream_t>(stream));
+  });
+}
+
+int moc_engine_solve_topk_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                 int64_t n, int K, moc_result* d_out, void* stream) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_topk_device(d_codes, d_offsets, h_offsets, n, K,
+                                                       reinterpret_cast<moc::Result*>(d_out),
+                                                       static_cast<hipStream_t>(stream));
+  });
+}
+
+int moc_engine_set_profile_scratch(void* e, int64_t bytes) {
+  return guard([&] { static_cast<moc::HipEngine*>(e)->set_profile_scratch(bytes); });
+}
+
+int moc_engine_topk_select_ms(void* e, double* ms) {
+  return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->topk_select_ms(); });
 }
 
 int moc_engine_stats(void* e, double* out14) {

@@ -5,6 +5,7 @@
 #include <omp.h>
 
 #include <algorithm>
+#include <functional>
 #include <vector>
 
 namespace moc {
@@ -22,19 +23,20 @@ inline void consider(Result& best, int32_t score, int64_t o, int64_t k) {
   if (best.n < 0 || better(c, best)) best = c;
 }
 
-}  // namespace
 
-Result solve_offsets(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2,
-                     int64_t o_begin, int64_t o_end, Semantics sem) {
-  Result best{kNoCandidateScore, -1, -1};
+// The one-pass-per-offset recurrence over offsets [o_begin, o_end) of a record's candidate set:
+// emit(o, score, k) receives every offset's best candidate (k = 0 first, then the smallest k).
+template <class Emit>
+inline void sweep_offsets(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2,
+                          int64_t o_begin, int64_t o_end, Semantics sem, Emit&& emit) {
   const int64_t n_off = candidate_offsets(L1, L2, sem);
   o_end = std::min(o_end, n_off);
-  if (o_begin >= o_end) return best;
+  if (o_begin >= o_end) return;
   if (L2 == L1) {  // equal lengths: un-shifted, un-mutated only (cudaFunctions.cu:74-106)
     int32_t s = 0;
     for (int64_t i = 0; i < L2; ++i) s += t.lut[s2[i] * kLutStride + s1[i]];
-    consider(best, s, 0, 0);
-    return best;
+    emit(int64_t{0}, s, int64_t{0});
+    return;
   }
   const int64_t last_mut_off = L1 - L2;  // offsets with a hyphen need o + L2 + 1 <= L1
   // per-thread scratch (no allocation per record): LUT row of every Seq2 letter, and P_o(1..L2) of the
@@ -54,8 +56,11 @@ Result solve_offsets(const ScoreTable& t, const uint8_t* s1, int64_t L1, const u
     for (int64_t i = 0; i < L2; ++i) P[i + 1] = acc += rw[i][a[i]];
   }
   for (int64_t o = o_begin; o < o_end; ++o) {
-    consider(best, P[L2], o, 0);
-    if (o >= last_mut_off) continue;
+    const int32_t tot = P[L2];  // the un-mutated candidate
+    if (o >= last_mut_off) {
+      emit(o, tot, int64_t{0});
+      continue;
+    }
     const uint8_t* a = s1 + o + 1;
     int32_t q = 0, bd = INT32_MIN;
     int64_t bk = 0;
@@ -70,8 +75,20 @@ Result solve_offsets(const ScoreTable& t, const uint8_t* s1, int64_t L1, const u
     }
     q += rw[L2 - 1][a[L2 - 1]];
     P[L2] = q;  // Tot_{o+1}
-    if (L2 >= 2) consider(best, bd + q, o, bk);
+    if (L2 >= 2 && bd + q > tot)
+      emit(o, bd + q, bk);
+    else
+      emit(o, tot, int64_t{0});
   }
+}
+
+}  // namespace
+
+Result solve_offsets(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2,
+                     int64_t o_begin, int64_t o_end, Semantics sem) {
+  Result best{kNoCandidateScore, -1, -1};
+  sweep_offsets(t, s1, L1, s2, L2, o_begin, o_end, sem,
+                [&](int64_t o, int32_t score, int64_t k) { consider(best, score, o, k); });
   return best;
 }
 
@@ -179,6 +196,102 @@ void solve_keys_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const Re
   }
   for (int64_t i = 0; i < n; ++i) keys[i] = 0;
   for (size_t j = 0; j < items.size(); ++j) keys[items[j].rec] = std::max(keys[items[j].rec], pk[j]);
+}
+
+void profile_offsets(int64_t L1, const RecordBatch& batch, Semantics sem, int64_t* poffsets) {
+  poffsets[0] = 0;
+  for (int64_t i = 0; i < batch.size(); ++i) poffsets[i + 1] = poffsets[i] + candidate_offsets(L1, batch.length(i), sem);
+}
+
+namespace {
+inline void profile_range(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2,
+                          int64_t o_begin, int64_t o_end, Semantics sem, ProfileEntry* prof) {
+  sweep_offsets(t, s1, L1, s2, L2, o_begin, o_end, sem, [&](int64_t o, int32_t score, int64_t k) {
+    prof[o] = ProfileEntry{score, static_cast<int32_t>(k)};
+  });
+}
+
+// The min(K, C) best offsets of a profile in better() order (higher score, then smaller n), then padding.
+// Keys as on the device (topk_select_kernel): (score ^ 2^31) << 32 | (2^32 - 1 - o), larger is better.
+void select_topk(const ProfileEntry* prof, int64_t C, int K, Result* out, std::vector<uint64_t>& keys) {
+  keys.resize(static_cast<size_t>(C));
+  for (int64_t o = 0; o < C; ++o)
+    keys[o] = (static_cast<uint64_t>(static_cast<uint32_t>(prof[o].score) ^ 0x80000000u) << 32) |
+              (0xffffffffu - static_cast<uint32_t>(o));
+  const int64_t m = std::min<int64_t>(K, C);
+  std::partial_sort(keys.begin(), keys.begin() + m, keys.end(), std::greater<uint64_t>());
+  for (int64_t j = 0; j < m; ++j) {
+    const int64_t o = 0xffffffffu - static_cast<uint32_t>(keys[j]);
+    out[j] = Result{prof[o].score, static_cast<int32_t>(o), prof[o].k};
+  }
+  for (int64_t j = m; j < K; ++j) out[j] = no_candidate();
+}
+
+// (record, offset chunk) work items of a batch with few records, as solve_batch_cpu cuts them
+struct OffsetItem {
+  int64_t rec, ob, oe;
+};
+void offset_items(int64_t rec, int64_t n_off, int nt, std::vector<OffsetItem>& items) {
+  const int64_t chunk = std::max<int64_t>(16, (n_off + 4 * nt - 1) / (4 * nt));
+  for (int64_t ob = 0; ob < n_off; ob += chunk) items.push_back(OffsetItem{rec, ob, std::min(n_off, ob + chunk)});
+}
+}  // namespace
+
+void profile_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                       const int64_t* poffsets, ProfileEntry* prof, Semantics sem, int num_threads) {
+  const int64_t n = batch.size();
+  const int nt = threads_for(batch, L1, sem, num_threads > 0 ? num_threads : omp_get_max_threads());
+  if (n >= 4 * nt || nt == 1) {
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(1024, n / (64 * nt)));
+#pragma omp parallel for schedule(dynamic, chunk) num_threads(nt) if (nt > 1)
+    for (int64_t i = 0; i < n; ++i)
+      profile_range(t, s1, L1, batch.record(i), batch.length(i), 0, L1 + 1, sem, prof + poffsets[i]);
+    return;
+  }
+  std::vector<OffsetItem> items;
+  for (int64_t i = 0; i < n; ++i) offset_items(i, poffsets[i + 1] - poffsets[i], nt, items);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt) if (nt > 1)
+  for (int64_t j = 0; j < static_cast<int64_t>(items.size()); ++j) {
+    const OffsetItem& it = items[j];
+    profile_range(t, s1, L1, batch.record(it.rec), batch.length(it.rec), it.ob, it.oe, sem, prof + poffsets[it.rec]);
+  }
+}
+
+void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
+                    Semantics sem, int num_threads) {
+  if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  const int64_t n = batch.size();
+  const int nt = threads_for(batch, L1, sem, num_threads > 0 ? num_threads : omp_get_max_threads());
+  if (n >= 4 * nt || nt == 1) {  // one record's profile per thread at a time
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(1024, n / (64 * nt)));
+#pragma omp parallel num_threads(nt) if (nt > 1)
+    {
+      std::vector<ProfileEntry> prof;
+      std::vector<uint64_t> keys;
+#pragma omp for schedule(dynamic, chunk)
+      for (int64_t i = 0; i < n; ++i) {
+        const int64_t C = candidate_offsets(L1, batch.length(i), sem);
+        prof.resize(static_cast<size_t>(C));
+        profile_range(t, s1, L1, batch.record(i), batch.length(i), 0, C, sem, prof.data());
+        select_topk(prof.data(), C, K, out + i * K, keys);
+      }
+    }
+    return;
+  }
+  // few records: one record's profile at a time, its offset chunks in parallel
+  std::vector<ProfileEntry> prof;
+  std::vector<uint64_t> keys;
+  std::vector<OffsetItem> items;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t C = candidate_offsets(L1, batch.length(i), sem);
+    prof.resize(static_cast<size_t>(C));
+    items.clear();
+    offset_items(i, C, nt, items);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt) if (nt > 1)
+    for (int64_t j = 0; j < static_cast<int64_t>(items.size()); ++j)
+      profile_range(t, s1, L1, batch.record(i), batch.length(i), items[j].ob, items[j].oe, sem, prof.data());
+    select_topk(prof.data(), C, K, out + i * K, keys);
+  }
 }
 
 Result brute_force_record(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2,

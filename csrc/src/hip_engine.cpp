@@ -10,6 +10,7 @@
 #include <queue>
 #include <string>
 
+#include "moc/cpu_engine.hpp"
 #include "moc/problem.hpp"
 #include "moc/runtime/hip_check.hpp"
 #include "moc/runtime/log.hpp"
@@ -109,7 +110,8 @@ int parse_preload_set(const char* s) {
     unsigned set;
   } names[] = {{"all", kPreloadAll}, {"none", 0}, {"align", kPreloadAlign}, {"short", kPreloadShort},
                {"swipe", kPreloadSwipeByte | kPreloadSwipeP33}, {"swipe8", kPreloadSwipeByte},
-               {"swipe33", kPreloadSwipeP33}, {"tile16", kPreloadTile16}, {"mfma", kPreloadMfma}};
+               {"swipe33", kPreloadSwipeP33}, {"tile16", kPreloadTile16}, {"mfma", kPreloadMfma},
+               {"profile", kPreloadProfile}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -160,6 +162,7 @@ HipEngine::HipEngine(const EngineOptions& opt) : opt_(opt) {
     if (v == 1 || v == 2 || v == 4 || v == 8) tile_u_ = v;
   }
   if (const char* t16 = std::getenv("MOC_TILE16")) tile16_ = std::atoi(t16) != 0;
+  if (const char* pt = std::getenv("MOC_PROFILE_TIMING")) profile_timing_ = std::atoi(pt) != 0;
   // MOC_TILE16_WINWIDE=0: short records on an L1 ~ 1500..3050 problem keep the whole byte-pair image (A/B)
   if (const char* ww = std::getenv("MOC_TILE16_WINWIDE")) tile16_window_wide_ = std::atoi(ww) != 0;
   if (const char* w8 = std::getenv("MOC_TILE16_WIN_U8")) short_window_u8_ = std::atoi(w8) != 0;
@@ -215,6 +218,8 @@ HipEngine::~HipEngine() {
     if (g) (void)hipGraphExecDestroy(g);
   (void)hipFree(d_counter_);
   (void)hipFree(d_plan_);
+  (void)hipFree(d_prof_scratch_);
+  for (hipEvent_t e : ev_select_) (void)hipEventDestroy(e);
   (void)hipHostFree(h_plan_);
   (void)hipEventDestroy(ev_plan_);
   if (ev_d0_) (void)hipEventDestroy(ev_d0_);
@@ -469,6 +474,30 @@ struct PlanLayout {
 constexpr int64_t kTileOverheadSteps = 24;
 // Staging one sliding window (tile16_slide_kernel), per wave, in step units.
 constexpr int64_t kSlideStageSteps = 96;
+
+// Part `part` of `parts` (by cost) of a record-major tile list — record li has ntiles[li] tiles of tcost[li]
+// each — cut into contiguous, cost-balanced runs for at most max_waves waves: n_waves + 1 run boundaries.
+std::vector<dev::WaveStart> balanced_runs(const std::vector<int32_t>& ntiles, const std::vector<int64_t>& tcost,
+                                          int64_t total_tiles, int part, int parts, int64_t max_waves) {
+  const int64_t n_long = static_cast<int64_t>(ntiles.size());
+  std::vector<int64_t> pre(static_cast<size_t>(n_long) + 1, 0);
+  for (int64_t li = 0; li < n_long; ++li) pre[li + 1] = pre[li] + ntiles[li] * tcost[li];
+  const int64_t C = pre[n_long];
+  const int64_t lo = C * part / parts, hi = C * (part + 1) / parts;
+  // position of cost threshold X in (li, t): first tile whose start cost is >= X
+  auto locate = [&](int64_t X) {
+    if (X >= C) return dev::WaveStart{static_cast<int32_t>(n_long), 0};
+    const int64_t li = std::upper_bound(pre.begin(), pre.end(), X) - pre.begin() - 1;
+    const int64_t t = (X - pre[li] + tcost[li] - 1) / tcost[li];
+    if (t >= ntiles[li]) return dev::WaveStart{static_cast<int32_t>(li + 1), 0};
+    return dev::WaveStart{static_cast<int32_t>(li), static_cast<int32_t>(t)};
+  };
+  const int64_t part_tiles = std::max<int64_t>(1, total_tiles * (hi - lo) / std::max<int64_t>(C, 1));
+  const int64_t n_waves = std::min<int64_t>(part_tiles, max_waves);
+  std::vector<dev::WaveStart> starts(static_cast<size_t>(n_waves) + 1);
+  for (int64_t w = 0; w <= n_waves; ++w) starts[w] = locate(lo + (hi - lo) * w / n_waves);
+  return starts;
+}
 }  // namespace
 
 // Device view of an uploaded plan buffer (starts | long_recs | keys). Identity record lists upload no
@@ -689,25 +718,8 @@ std::vector<dev::WaveStart> HipEngine::plan_waves(const int64_t* offsets, const 
   const int64_t prof_lds = (wide ? 2 : 1) * (W ? dev::tile16_window_bytes(W) : static_cast<int64_t>(prof16_bytes_));
   const int waves_per_cu = tp.tile16 ? dev::tile16_waves_per_cu(static_cast<int>(dev::tile16_lds_bytes(prof_lds, s1_len)))
                                      : tile_waves_per_cu_;
-  if (!(tp.tile16 && W > 0)) {
-    std::vector<int64_t> pre(static_cast<size_t>(n_long) + 1, 0);
-    for (int64_t li = 0; li < n_long; ++li) pre[li + 1] = pre[li] + ntiles[li] * tcost[li];
-    const int64_t C = pre[n_long];
-    const int64_t lo = C * part / parts, hi = C * (part + 1) / parts;
-    // position of cost threshold X in (li, t): first tile whose start cost is >= X
-    auto locate = [&](int64_t X) {
-      if (X >= C) return dev::WaveStart{static_cast<int32_t>(n_long), 0};
-      const int64_t li = std::upper_bound(pre.begin(), pre.end(), X) - pre.begin() - 1;
-      const int64_t t = (X - pre[li] + tcost[li] - 1) / tcost[li];
-      if (t >= ntiles[li]) return dev::WaveStart{static_cast<int32_t>(li + 1), 0};
-      return dev::WaveStart{static_cast<int32_t>(li), static_cast<int32_t>(t)};
-    };
-    const int64_t part_tiles = std::max<int64_t>(1, total_tiles * (hi - lo) / std::max<int64_t>(C, 1));
-    const int64_t n_waves = std::min<int64_t>(part_tiles, static_cast<int64_t>(num_cus_) * waves_per_cu);
-    starts.resize(static_cast<size_t>(n_waves) + 1);
-    for (int64_t w = 0; w <= n_waves; ++w) starts[w] = locate(lo + (hi - lo) * w / n_waves);
-    return starts;
-  }
+  if (!(tp.tile16 && W > 0))
+    return balanced_runs(ntiles, tcost, total_tiles, part, parts, static_cast<int64_t>(num_cus_) * waves_per_cu);
   // ---- windowed tile16: window-major runs, whole workgroups per window
   // (a widened window, chosen for short records only, packs one more tile: its columns
   // [0, T * span + max L2) still lie inside the window)
@@ -1354,6 +1366,225 @@ void HipEngine::search_keys(const uint8_t* codes, const int64_t* offsets, int64_
   stats_.kernel_ms = ms;
   stats_.h2d_bytes = static_cast<int64_t>(cbytes + sizeof(int64_t) * (n + 1));
   stats_.d2h_bytes = static_cast<int64_t>(sizeof(uint64_t) * n);
+  wall.stop();
+  stats_.total_ms = wall.total_ms();
+}
+
+// ---- per-offset score profile and top-K alignments ------------------------------------------------------
+void HipEngine::set_profile_scratch(int64_t bytes) {
+  if (bytes < static_cast<int64_t>(sizeof(ProfileEntry))) throw Error("profile scratch: at least one entry (8 bytes)");
+  opt_.profile_scratch_bytes = bytes;
+}
+
+void HipEngine::profile_offsets(const int64_t* offsets, int64_t n, int64_t* poffsets) const {
+  if (!have_problem_) throw Error("HipEngine::profile_offsets before set_problem");
+  poffsets[0] = 0;
+  for (int64_t i = 0; i < n; ++i) poffsets[i + 1] = poffsets[i] + candidate_offsets(L1_, offsets[i + 1] - offsets[i], sem_);
+}
+
+double HipEngine::topk_select_ms() {
+  double total = 0;
+  for (size_t i = 0; i + 1 < ev_select_used_; i += 2) {
+    MOC_HIP_CHECK(hipEventSynchronize(ev_select_[i + 1]));
+    float ms = 0;
+    MOC_HIP_CHECK(hipEventElapsedTime(&ms, ev_select_[i], ev_select_[i + 1]));
+    total += ms;
+  }
+  return total;
+}
+
+// K == 0: the whole batch's profile -> d_dst (ProfileEntry, one chunk). K >= 1: top-K rows -> d_dst (Result
+// [n, K]), chunk by chunk through the bounded scratch. Plan buffer: poffsets (n + 1) | every chunk's wave starts.
+void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                            int K, void* d_dst, hipStream_t stream) {
+  if (!have_problem_) throw Error("HipEngine: profile / top-K before set_problem");
+  if (K < 0 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  ev_select_used_ = 0;
+  if (n <= 0) return;
+  if (n >= (int64_t{1} << 31) - 1) throw Error("profile / top-K: more than 2^31 - 2 records in one call");
+  if (!stream) stream = s_compute_;
+  TraceRange tr(K ? "moc.solve_topk_device" : "moc.solve_profile_device");
+  std::vector<int64_t> poff(static_cast<size_t>(n) + 1);
+  profile_offsets(h_offsets, n, poff.data());
+  int64_t sum_l2 = 0, max_l2 = 0, cells = 0, max_need = 1;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t L2 = h_offsets[i + 1] - h_offsets[i];
+    sum_l2 += L2;
+    max_l2 = std::max(max_l2, L2);
+    max_need = std::max(max_need, dev::lanes_needed(L1_, L2));
+    cells += record_cells(L1_, L2);
+  }
+  if (L1_ >= (int64_t{1} << 30) || max_l2 >= (int64_t{1} << 30))
+    throw Error("Seq1 / Seq2 lengths beyond 2^30 exceed the device engine's offset range");
+  // sub-tiles per wave tile, as the LUT tile kernel picks them: 4 amortises the per-tile set-up over short
+  // records, 2 keeps more waves busy on long ones; MOC_TILE_U = 1 | 2 | 4 overrides (8 is tile16's: 4 here)
+  // — and never more sub-tiles than the batch's widest offset range fills (short records: one sub-tile)
+  int u = tile_u_ > 0 ? std::min(tile_u_, 4) : (sum_l2 < 96 * n ? 4 : 2);
+  if (tile_u_ <= 0)
+    while (u > 1 && max_need <= dev::kTileOffsets * (u / 2)) u /= 2;
+  const int span = dev::tile_span(false, u);
+  // chunks of consecutive records: the whole batch for a profile, bounded scratch for top-K
+  struct Chunk {
+    int64_t r0, r1;
+    size_t starts_at, n_starts;
+  };
+  std::vector<Chunk> chunks;
+  const int64_t cap_entries = std::max<int64_t>(1, opt_.profile_scratch_bytes / static_cast<int64_t>(sizeof(ProfileEntry)));
+  for (int64_t r0 = 0; r0 < n;) {
+    int64_t r1 = r0 + 1;
+    if (K == 0)
+      r1 = n;
+    else
+      while (r1 < n && poff[r1 + 1] - poff[r0] <= cap_entries) ++r1;
+    chunks.push_back(Chunk{r0, r1, 0, 0});
+    r0 = r1;
+  }
+  std::vector<dev::WaveStart> starts;
+  std::vector<int32_t> ntiles;
+  std::vector<int64_t> tcost;
+  int64_t max_entries = 0;
+  for (Chunk& c : chunks) {
+    const int64_t m = c.r1 - c.r0;
+    ntiles.resize(static_cast<size_t>(m));
+    tcost.resize(static_cast<size_t>(m));
+    int64_t total_tiles = 0;
+    for (int64_t li = 0; li < m; ++li) {
+      const int64_t L2 = h_offsets[c.r0 + li + 1] - h_offsets[c.r0 + li];
+      ntiles[li] = static_cast<int32_t>(dev::tiles_of(dev::lanes_needed(L1_, L2), span));
+      tcost[li] = (L2 <= L1_ ? L2 : 0) + kTileOverheadSteps;
+      total_tiles += ntiles[li];
+    }
+    const std::vector<dev::WaveStart> runs =
+        balanced_runs(ntiles, tcost, total_tiles, 0, 1, static_cast<int64_t>(num_cus_) * tile_waves_per_cu_);
+    c.starts_at = starts.size();
+    c.n_starts = runs.size();
+    starts.insert(starts.end(), runs.begin(), runs.end());
+    max_entries = std::max(max_entries, poff[c.r1] - poff[c.r0]);
+  }
+  const size_t poff_bytes = sizeof(int64_t) * poff.size();
+  const size_t plan_bytes = poff_bytes + sizeof(dev::WaveStart) * starts.size();
+  MOC_HIP_CHECK(hipEventSynchronize(ev_plan_));  // previous call's plan buffers are free again
+  ensure(d_plan_, d_plan_cap_, plan_bytes);
+  ensure_host(h_plan_, h_plan_cap_, plan_bytes);
+  if (K) ensure(d_prof_scratch_, d_prof_scratch_cap_, sizeof(ProfileEntry) * static_cast<size_t>(std::max<int64_t>(max_entries, 1)));
+  std::memcpy(h_plan_, poff.data(), poff_bytes);
+  std::memcpy(static_cast<char*>(h_plan_) + poff_bytes, starts.data(), sizeof(dev::WaveStart) * starts.size());
+  upload_staged(d_plan_, h_plan_, plan_bytes, stream);
+  dev::ProblemView pv = problem_view(max_l2);
+  pv.prof16 = nullptr;  // the LUT sweep: exact int32 for any weights
+  pv.mfma_sweep = 0;
+  const dev::BatchView bv{d_codes + h_offsets[0], d_offsets, n};
+  if (!ev_d0_) {
+    MOC_HIP_CHECK(hipEventCreate(&ev_d0_));
+    MOC_HIP_CHECK(hipEventCreate(&ev_d1_));
+  }
+  if (K && profile_timing_)
+    while (ev_select_.size() < 2 * chunks.size()) {
+      hipEvent_t e = nullptr;
+      MOC_HIP_CHECK(hipEventCreate(&e));
+      ev_select_.push_back(e);
+    }
+  MOC_HIP_CHECK(hipEventRecord(ev_d0_, stream));
+  for (const Chunk& c : chunks) {
+    dev::ProfileArgs pa;
+    pa.starts = reinterpret_cast<const dev::WaveStart*>(static_cast<const char*>(d_plan_) + poff_bytes) + c.starts_at;
+    pa.n_waves = static_cast<int64_t>(c.n_starts) - 1;
+    pa.u = u;
+    pa.rec0 = c.r0;
+    pa.poffsets = static_cast<const int64_t*>(d_plan_);
+    pa.base = K ? poff[c.r0] : 0;
+    pa.prof = K ? static_cast<ProfileEntry*>(d_prof_scratch_) : static_cast<ProfileEntry*>(d_dst);
+    pa.prof_entries = K ? poff[c.r1] - poff[c.r0] : poff[n];
+    dev::launch_offset_profile(pv, bv, pa, stream);
+    if (K) {
+      if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
+      dev::launch_topk_select(pa, c.r1 - c.r0, K, static_cast<Result*>(d_dst), stream);
+      if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
+    }
+  }
+  MOC_HIP_CHECK(hipGetLastError());
+  MOC_HIP_CHECK(hipEventRecord(ev_d1_, stream));
+  MOC_HIP_CHECK(hipEventRecord(ev_plan_, stream));
+  stats_ = EngineStats{};
+  stats_.cells = cells;
+  stats_.records = n;
+  stats_.chunks = static_cast<int64_t>(chunks.size());
+  stats_.kernels = 16;
+}
+
+void HipEngine::solve_profile_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                     int64_t n, ProfileEntry* d_prof, hipStream_t stream) {
+  run_profile(d_codes, d_offsets, h_offsets, n, 0, d_prof, stream);
+}
+
+void HipEngine::solve_topk_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                  int64_t n, int K, Result* d_out, hipStream_t stream) {
+  if (K < 1) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  run_profile(d_codes, d_offsets, h_offsets, n, K, d_out, stream);
+}
+
+namespace {
+// host batch -> pooled device buffers of a slot (offsets rebased to 0: the device base pointer is the buffer)
+std::vector<int64_t> rebase_offsets(const int64_t* offsets, int64_t n) {
+  std::vector<int64_t> rebased(static_cast<size_t>(n) + 1);
+  for (int64_t i = 0; i <= n; ++i) rebased[i] = offsets[i] - offsets[0];
+  return rebased;
+}
+}  // namespace
+
+void HipEngine::solve_profile(const uint8_t* codes, const int64_t* offsets, int64_t n, ProfileEntry* prof_out,
+                              int64_t* poffsets_out) {
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  profile_offsets(offsets, std::max<int64_t>(n, 0), poffsets_out);
+  if (n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  Slot& s = *slots_[0];
+  const size_t cbytes = static_cast<size_t>(offsets[n] - offsets[0]);
+  const size_t pbytes = sizeof(ProfileEntry) * static_cast<size_t>(poffsets_out[n]);
+  ensure(s.d_codes, s.d_codes_cap, std::max<size_t>(cbytes, 16) + 32);
+  ensure(s.d_offsets, s.d_offsets_cap, sizeof(int64_t) * static_cast<size_t>(n + 1));
+  ensure(s.d_out, s.d_out_cap, std::max<size_t>(pbytes, 8));
+  const std::vector<int64_t> rebased = rebase_offsets(offsets, n);
+  if (cbytes) copy_h2d(s.d_codes, codes + offsets[0], cbytes, s_compute_);
+  MOC_HIP_CHECK(hipMemcpyAsync(s.d_offsets, rebased.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s_compute_));
+  run_profile(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(), n, 0,
+              s.d_out, s_compute_);
+  if (pbytes) copy_d2h(prof_out, s.d_out, pbytes, s_compute_);
+  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+  stats_.kernel_ms = device_kernel_ms();
+  stats_.h2d_bytes = static_cast<int64_t>(cbytes + sizeof(int64_t) * (n + 1));
+  stats_.d2h_bytes = static_cast<int64_t>(pbytes);
+  wall.stop();
+  stats_.total_ms = wall.total_ms();
+}
+
+void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, Result* out) {
+  if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  if (n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  Slot& s = *slots_[0];
+  const size_t cbytes = static_cast<size_t>(offsets[n] - offsets[0]);
+  const size_t obytes = sizeof(Result) * static_cast<size_t>(n) * static_cast<size_t>(K);
+  ensure(s.d_codes, s.d_codes_cap, std::max<size_t>(cbytes, 16) + 32);
+  ensure(s.d_offsets, s.d_offsets_cap, sizeof(int64_t) * static_cast<size_t>(n + 1));
+  ensure(s.d_out, s.d_out_cap, obytes);
+  const std::vector<int64_t> rebased = rebase_offsets(offsets, n);
+  if (cbytes) copy_h2d(s.d_codes, codes + offsets[0], cbytes, s_compute_);
+  MOC_HIP_CHECK(hipMemcpyAsync(s.d_offsets, rebased.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s_compute_));
+  run_profile(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(), n, K,
+              s.d_out, s_compute_);
+  copy_d2h(out, s.d_out, obytes, s_compute_);
+  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+  stats_.kernel_ms = device_kernel_ms();
+  stats_.h2d_bytes = static_cast<int64_t>(cbytes + sizeof(int64_t) * (n + 1));
+  stats_.d2h_bytes = static_cast<int64_t>(obytes);
   wall.stop();
   stats_.total_ms = wall.total_ms();
 }

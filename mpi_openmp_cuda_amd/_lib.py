@@ -20,6 +20,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MOC_LIB_PATH") or os.path.join(_HERE, "lib", "libmoc.so")
 
 RESULT_DTYPE = np.dtype([("score", "<i4"), ("n", "<i4"), ("k", "<i4")])
+# One entry of a per-offset score profile (moc::ProfileEntry): the best candidate at that offset.
+PROFILE_DTYPE = np.dtype([("score", "<i4"), ("k", "<i4")])
 # Packed result wire formats (moc/device.hpp ResultFormat): index = format id.
 R8_DTYPE = np.dtype([("score", "<i4"), ("n", "<u2"), ("k", "<u2")])
 R4_DTYPE = np.dtype([("score", "<i2"), ("n", "u1"), ("k", "u1")])
@@ -64,6 +66,18 @@ def _decl(lib):
                                        c_int, c_void_p]),
         "moc_resolve_keys": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
         "moc_brute_force": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+        "moc_candidate_offsets": (c_int64, [c_int64, c_int64, c_int]),
+        "moc_cpu_profile": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                    c_void_p]),
+        "moc_cpu_topk": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                 c_void_p]),
+        "moc_engine_solve_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+        "moc_engine_solve_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+        "moc_engine_solve_profile_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+        "moc_engine_solve_topk_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                                 c_void_p]),
+        "moc_engine_set_profile_scratch": (c_int, [c_void_p, c_int64]),
+        "moc_engine_topk_select_ms": (c_int, [c_void_p, c_void_p]),
         "moc_partition": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_double, c_void_p]),
         "moc_device_count": (c_int, []),
         "moc_host_register": (c_int, [c_void_p, c_size_t]),

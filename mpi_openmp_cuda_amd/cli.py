@@ -16,7 +16,7 @@ from .models.problem import Problem
 from .models.scoring import Semantics
 from .parallel import dist as D
 from .parallel.search import DistributedSearch
-from .utils.io import write_results
+from .utils.io import format_topk, write_results
 
 
 def main(argv=None) -> int:
@@ -36,7 +36,12 @@ def main(argv=None) -> int:
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--strict-limits", action="store_true")
     ap.add_argument("--timing", action="store_true")
+    ap.add_argument("--top", type=int, default=1, metavar="K",
+                    help="print every record's K best offsets (1..64): rank 1 as always, ranks j >= 2 as "
+                         "'#i.j: score: S, n: N, k: K'. Record slices on one node only (--partition records)")
     a = ap.parse_args(argv)
+    if not 1 <= a.top <= 64:
+        ap.error("--top K: K must be in 1..64")
 
     from .ops.align import device_count
 
@@ -61,9 +66,22 @@ def main(argv=None) -> int:
         return 1
     search = DistributedSearch(ctx, backend="hip" if use_gpu else "cpu", transport=a.transport, threads=a.threads,
                                partition=a.partition)
-    results = search.run(problem, Semantics.parse(a.semantics))
+    if a.top > 1 and search.partition != "records":
+        if ctx.is_root:
+            print("--top K > 1 needs record slices (--partition records, one node); --partition offsets combines "
+                  "one candidate per record", file=sys.stderr)
+        D.finalize(ctx)
+        return 2
+    if a.top > 1:
+        results = search.run_topk(problem, a.top, Semantics.parse(a.semantics))
+    else:
+        results = search.run(problem, Semantics.parse(a.semantics))
     if ctx.is_root:
-        write_results(results)
+        if a.top > 1:
+            sys.stdout.write(format_topk(results))
+            sys.stdout.flush()
+        else:
+            write_results(results)
         if a.timing:
             print(json.dumps({"timing": json.loads(search.timer.json()), "ranks": ctx.world,
                               "backend": search.backend, "transport": search.transport}), file=sys.stderr)

@@ -39,6 +39,33 @@ def brute_force(table: np.ndarray, s1: np.ndarray, s2: np.ndarray, semantics=Sem
     return best
 
 
+def brute_force_profile(table: np.ndarray, s1: np.ndarray, s2: np.ndarray, semantics=Semantics.REFERENCE):
+    """Per-offset score profile by literal letter-by-letter replay: a list of (score, k), one per candidate
+    offset — L1-L2 offsets under reference semantics, one more (k = 0 only) under spec, the single (0, 0)
+    candidate when L2 == L1, none when L2 > L1 or L2 == 0. Each offset's best candidate, ties to the smallest
+    k with k = 0 (no hyphen) first. O(L1*L2^2); the anchor oracle of the native profile code."""
+    L1, L2 = len(s1), len(s2)
+    if L2 > L1 or L2 <= 0:
+        return []
+    if L2 == L1:
+        return [(int(sum(int(table[s2[i], s1[i]]) for i in range(L2))), 0)]
+    prof = []
+    for o in range(L1 - L2):
+        best = None
+        for m in range(L2):
+            s = 0
+            for i in range(L2):
+                j = i + o if (i < m or m == 0) else i + o + 1
+                s += int(table[s2[i], s1[j]])
+            if best is None or best[0] < s:
+                best = (s, m)
+        prof.append(best)
+    if Semantics.parse(semantics) == Semantics.SPEC:
+        o = L1 - L2
+        prof.append((int(sum(int(table[s2[i], s1[i + o]]) for i in range(L2))), 0))
+    return prof
+
+
 def prefix_oracle(table: np.ndarray, s1: np.ndarray, s2: np.ndarray, semantics=Semantics.REFERENCE):
     L1, L2 = len(s1), len(s2)
     if L2 > L1:

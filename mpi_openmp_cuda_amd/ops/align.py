@@ -18,6 +18,7 @@ from ..models.problem import Problem
 from ..models.scoring import Semantics, Weights
 
 RESULT_DTYPE = _lib.RESULT_DTYPE
+PROFILE_DTYPE = _lib.PROFILE_DTYPE
 
 
 def empty_results(n: int) -> np.ndarray:
@@ -90,6 +91,53 @@ def keys_to_ordered_int64(keys: np.ndarray) -> np.ndarray:
 
 def ordered_int64_to_keys(v: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(v, dtype=np.int64).view(np.uint64) ^ np.uint64(1 << 63)
+
+
+MAX_TOP_K = 64
+
+
+def _check_k(K) -> int:
+    K = int(K)
+    if not 1 <= K <= MAX_TOP_K:
+        raise ValueError(f"top-K: K must be in 1..{MAX_TOP_K}, got {K}")
+    return K
+
+
+def profile_offsets(L1: int, lengths, semantics=Semantics.REFERENCE) -> np.ndarray:
+    """int64 [n + 1] index of a batch's flat per-offset profile: record i owns entries
+    [poffsets[i], poffsets[i + 1]), one per candidate offset — 0 if L2 > L1 or L2 <= 0, 1 if L2 == L1,
+    L1 - L2 under reference semantics and L1 - L2 + 1 under spec."""
+    L2 = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    spec = 1 if Semantics.parse(semantics) == Semantics.SPEC else 0
+    c = np.where((L2 > L1) | (L2 <= 0), 0, np.where(L2 == L1, 1, L1 - L2 + spec))
+    out = np.zeros(L2.shape[0] + 1, np.int64)
+    np.cumsum(c, out=out[1:])
+    return out
+
+
+def search_profile_cpu(problem: Problem, semantics=Semantics.REFERENCE, threads: int = 0):
+    """Per-offset score profile on the CPU engine: ``(prof, poffsets)`` — ``prof`` a flat PROFILE_DTYPE array
+    (score, k), entry ``poffsets[i] + o`` = the best candidate of record i at offset o (ties: k = 0, then the
+    smallest k). The maximum over a record's entries (higher score, then smaller offset) is search_cpu's row."""
+    sem = Semantics.parse(semantics)
+    poffsets = profile_offsets(problem.L1, problem.lengths, sem)
+    prof = np.zeros(int(poffsets[-1]), dtype=PROFILE_DTYPE)
+    _lib.check(_lib.lib().moc_cpu_profile(
+        _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+        _lib.ptr(problem.offsets), problem.n, int(sem), int(threads), _lib.ptr(poffsets), _lib.ptr(prof)))
+    return prof, poffsets
+
+
+def search_topk_cpu(problem: Problem, K: int, semantics=Semantics.REFERENCE, threads: int = 0) -> np.ndarray:
+    """The K best offsets of every record on the CPU engine: int32 [n, K, 3] rows (score, n, k) in the order
+    higher score, then smaller n, each with that offset's profile k; records with fewer than K candidate
+    offsets are padded with (INT32_MIN, 0, 0). Row 0 is search_cpu's result."""
+    K = _check_k(K)
+    out = np.zeros((problem.n, K, 3), np.int32)
+    _lib.check(_lib.lib().moc_cpu_topk(
+        _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+        _lib.ptr(problem.offsets), problem.n, int(Semantics.parse(semantics)), int(threads), K, _lib.ptr(out)))
+    return out
 
 
 def brute_force_native(problem: Problem, semantics=Semantics.REFERENCE) -> np.ndarray:
@@ -323,6 +371,89 @@ class HipSearchEngine:
             ctypes.c_void_p(stream.cuda_stream)))
         return out_t
 
+    # ---- per-offset score profile and top-K alignments (byte letters, dense offsets)
+    def profile_offsets(self, offsets: np.ndarray) -> np.ndarray:
+        """int64 [n + 1] profile index of a batch for the engine's problem (see :func:`profile_offsets`)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        poffsets = np.zeros(n + 1, np.int64)
+        _lib.check(_lib.lib().moc_engine_solve_profile(self._h, None, _lib.ptr(offsets), n, _lib.ptr(poffsets), None))
+        return poffsets
+
+    def solve_profile(self, codes: np.ndarray, offsets: np.ndarray):
+        """Host CSR -> ``(prof, poffsets)`` as :func:`search_profile_cpu` returns them, computed by the profile
+        kernel (csrc/src/hip/profile_kernels.hip). Synchronous."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        poffsets = self.profile_offsets(offsets)
+        prof = np.zeros(max(int(poffsets[-1]), 1), dtype=PROFILE_DTYPE)  # never a NULL pointer: NULL asks for poffsets
+        _lib.check(_lib.lib().moc_engine_solve_profile(self._h, _lib.ptr(codes), _lib.ptr(offsets), n,
+                                                       _lib.ptr(poffsets), _lib.ptr(prof)))
+        return prof[:int(poffsets[-1])], poffsets
+
+    def solve_topk(self, codes: np.ndarray, offsets: np.ndarray, K: int) -> np.ndarray:
+        """Host CSR -> int32 [n, K, 3] top-K rows as :func:`search_topk_cpu` returns them. The batch's profile
+        is never materialised: records run in chunks whose profile scratch stays under the bound of
+        :meth:`set_profile_scratch` (default 256 MiB). Synchronous."""
+        K = _check_k(K)
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        out = np.zeros((n, K, 3), np.int32)
+        _lib.check(_lib.lib().moc_engine_solve_topk(self._h, _lib.ptr(codes), _lib.ptr(offsets), n, K, _lib.ptr(out)))
+        return out
+
+    def solve_profile_device(self, codes_t, offsets_t, h_offsets: np.ndarray, prof_t=None, stream=None):
+        """Device-resident batch (as :meth:`solve_device`) -> ``(prof_t, poffsets)``: ``prof_t`` an int32
+        [total, 2] tensor of (score, k) entries on the codes' device (allocated when None), ``poffsets`` the host
+        index. Queued on ``stream`` (default: the current stream); returns immediately."""
+        import torch
+
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        n = h_offsets.shape[0] - 1
+        poffsets = self.profile_offsets(h_offsets)
+        total = int(poffsets[-1])
+        if prof_t is None:
+            prof_t = torch.empty((total, 2), dtype=torch.int32, device=codes_t.device)
+        assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        assert prof_t.dtype == torch.int32 and prof_t.shape == (total, 2) and prof_t.is_contiguous()
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        _lib.check(_lib.lib().moc_engine_solve_profile_device(
+            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
+            n, ctypes.c_void_p(prof_t.data_ptr()), ctypes.c_void_p(stream.cuda_stream)))
+        return prof_t, poffsets
+
+    def solve_topk_device(self, codes_t, offsets_t, h_offsets: np.ndarray, K: int, out_t, stream=None):
+        """Device-resident batch -> ``out_t``, an int32 [n, K, 3] tensor of top-K rows. Queued on ``stream``
+        (default: the current stream); returns immediately."""
+        import torch
+
+        K = _check_k(K)
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        n = h_offsets.shape[0] - 1
+        assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        assert out_t.dtype == torch.int32 and out_t.shape == (n, K, 3) and out_t.is_contiguous()
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        _lib.check(_lib.lib().moc_engine_solve_topk_device(
+            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
+            n, K, ctypes.c_void_p(out_t.data_ptr()), ctypes.c_void_p(stream.cuda_stream)))
+        return out_t
+
+    def set_profile_scratch(self, nbytes: int):
+        """Bound (bytes) of the profile scratch a top-K call may hold; a record whose profile is larger still
+        runs, alone in its chunk. ``stats()["chunks"]`` reports the chunks of the last call."""
+        _lib.check(_lib.lib().moc_engine_set_profile_scratch(self._h, int(nbytes)))
+
+    def topk_select_ms(self) -> float:
+        """Device time (ms) of the select launches of the last top-K call; 0 unless the engine was created with
+        MOC_PROFILE_TIMING=1 in the environment. Waits for them."""
+        ms = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().moc_engine_topk_select_ms(self._h, ctypes.addressof(ms)))
+        return float(ms.value)
+
     def kernel_times(self) -> tuple:
         """(kernel_ms, total_ms) of the last solve: the two fields a timed loop reads, without stats()'s dict."""
         v = self._stats_buf
@@ -341,7 +472,7 @@ class HipSearchEngine:
         d = dict(zip(keys, list(v)[:10]))
         d["r2"] = tuple(int(x) for x in list(v)[10:13])
         d["format"] = _lib.FORMAT_NAMES[int(d["format"])]
-        d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16")) if int(d["kernels"]) & b]
+        d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16"), (16, "profile")) if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
 
@@ -391,4 +522,21 @@ def align_search_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, 
     n = int(len(h_offsets) - 1)
     out = torch.empty((n, 3), dtype=torch.int32, device=codes_t.device)
     engine.solve_device(codes_t, offsets_t, h_offsets, out, stream)
+    return out
+
+
+def align_profile_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, stream=None):
+    """torch-facing op: ``(prof_t, poffsets)`` — an int32 [total, 2] tensor of per-offset (score, k) entries on
+    the codes' device and the host int64 [n + 1] index into it."""
+    return engine.solve_profile_device(codes_t, offsets_t, h_offsets, None, stream)
+
+
+def align_topk_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, K: int, stream=None):
+    """torch-facing op: an int32 [n, K, 3] tensor of the K best (score, n, k) rows per record on the codes'
+    device; ``[:, 0]`` equals :func:`align_search_device`."""
+    import torch
+
+    n = int(len(h_offsets) - 1)
+    out = torch.empty((n, _check_k(K), 3), dtype=torch.int32, device=codes_t.device)
+    engine.solve_topk_device(codes_t, offsets_t, h_offsets, K, out, stream)
     return out

@@ -28,7 +28,7 @@ from .. import _lib
 from ..models.problem import Problem
 from ..models.scoring import Semantics
 from ..ops.align import (HipSearchEngine, decode_keys, device_count, keys_to_ordered_int64, ordered_int64_to_keys,
-                        search_cpu, search_keys_cpu)
+                        search_cpu, search_keys_cpu, search_topk_cpu)
 from ..utils.timer import PhaseTimer
 from . import dist as D
 from .partition import CPU_COST, GPU_COST, partition
@@ -105,28 +105,82 @@ class DistributedSearch:
             sub = Problem(prob.weights, prob.seq1, codes[offsets[0]:offsets[-1]], offsets - offsets[0])
             out[:] = search_cpu(sub, sem, self.threads)
 
+    def _setup(self, problem: Optional[Problem], semantics):
+        """Header + Seq1 broadcasts and the cost-balanced record bounds: (prob, sem, n, total, bounds)."""
+        ctx = self.ctx
+        sem = Semantics.parse(semantics)
+        if ctx.is_root:
+            hdr = np.array(problem.weights.as_list() + [problem.L1, problem.n, problem.total_chars, int(sem)],
+                           np.int64)
+        else:
+            hdr = None
+        hdr = D.bcast_array(ctx, hdr, 8, np.int64)
+        w, L1, n, total, sem = list(hdr[:4]), int(hdr[4]), int(hdr[5]), int(hdr[6]), Semantics(int(hdr[7]))
+        seq1 = D.bcast_array(ctx, problem.seq1 if ctx.is_root else None, L1, np.uint8)
+        prob = Problem(w, seq1)
+        if self.engine is not None:
+            self.engine.set_problem(w, seq1, sem)
+        bounds = partition(problem.lengths, L1, ctx.world, GPU_COST if self.backend == "hip" else CPU_COST) \
+            if ctx.is_root else None
+        bounds = D.bcast_array(ctx, bounds, ctx.world + 1, np.int64)
+        return prob, sem, n, total, bounds
+
     def run(self, problem: Optional[Problem], semantics=Semantics.REFERENCE) -> Optional[np.ndarray]:
         ctx, T = self.ctx, self.timer
-        sem = Semantics.parse(semantics)
         with T.phase("bcast"):
-            if ctx.is_root:
-                hdr = np.array(problem.weights.as_list() + [problem.L1, problem.n, problem.total_chars, int(sem)],
-                               np.int64)
-            else:
-                hdr = None
-            hdr = D.bcast_array(ctx, hdr, 8, np.int64)
-            w, L1, n, total, sem = list(hdr[:4]), int(hdr[4]), int(hdr[5]), int(hdr[6]), Semantics(int(hdr[7]))
-            seq1 = D.bcast_array(ctx, problem.seq1 if ctx.is_root else None, L1, np.uint8)
-            prob = Problem(w, seq1)
-            if self.engine is not None:
-                self.engine.set_problem(w, seq1, sem)
-            bounds = partition(problem.lengths, L1, ctx.world, GPU_COST if self.backend == "hip" else CPU_COST) \
-                if ctx.is_root else None
-            bounds = D.bcast_array(ctx, bounds, ctx.world + 1, np.int64)
+            prob, sem, n, total, bounds = self._setup(problem, semantics)
         b, e = int(bounds[ctx.rank]), int(bounds[ctx.rank + 1])
         if self.partition == "offsets":
             return self._run_offsets(problem, prob, sem, n, total)
         return self._run_shm(problem, prob, sem, n, total, b, e)
+
+    def _open_window(self, problem, n, total) -> NodeWindow:
+        """The node-shared input window: the root writes the batch once, every rank maps it."""
+        ctx = self.ctx
+        name_arr = None
+        if ctx.is_root:  # fixed 20-byte name: "moc_win_" + 12 hex digits
+            name_arr = np.frombuffer(f"moc_win_{uuid.uuid4().hex[:12]}".encode(), np.uint8)
+        name = bytes(D.bcast_array(ctx, name_arr, 20, np.uint8)).decode()
+        win = None
+        if ctx.is_root:
+            win = NodeWindow(name, n, total, create=True)
+            win.offsets[:] = problem.offsets
+            win.codes[:] = problem.codes
+            win._mm.flush()
+        D.barrier(ctx)
+        if not ctx.is_root:
+            win = NodeWindow(name, n, total, create=False)
+        return win
+
+    def run_topk(self, problem: Optional[Problem], K: int, semantics=Semantics.REFERENCE) -> Optional[np.ndarray]:
+        """The K best offsets of every record (ops.align.search_topk_cpu's int32 [n, K, 3] rows) for the
+        ``records`` partition: every rank searches its cost-balanced slice of the node-shared input window, and
+        the root collects the rows with one MAX all-reduce of an array each rank fills only in its own slice
+        (no new transport). One node; byte letters through the engines' top-K calls."""
+        if self.partition != "records":
+            raise ValueError("top-K runs on record slices (--partition records, one node): the offsets partition "
+                             "combines one packed key per record and cannot carry K rows")
+        ctx, T = self.ctx, self.timer
+        with T.phase("bcast"):
+            prob, sem, n, total, bounds = self._setup(problem, semantics)
+        b, e = int(bounds[ctx.rank]), int(bounds[ctx.rank + 1])
+        with T.phase("distribute"):
+            win = self._open_window(problem, n, total)
+        with T.phase("compute"):
+            rows = np.full((n, K, 3), np.iinfo(np.int64).min, np.int64)
+            if e > b:
+                offsets = np.asarray(win.offsets[b:e + 1])
+                if self.engine is not None:
+                    rows[b:e] = self.engine.solve_topk(np.asarray(win.codes), offsets, K)
+                else:
+                    sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
+                                  offsets - offsets[0])
+                    rows[b:e] = search_topk_cpu(sub, K, sem, self.threads)
+        with T.phase("gather"):
+            rows = D.allreduce_max_int64(ctx, rows.reshape(-1)).reshape(n, K, 3)
+            D.barrier(ctx)
+            win.close(unlink=ctx.is_root)
+        return rows.astype(np.int32) if ctx.is_root else None
 
     def _run_shm(self, problem, prob, sem, n, total, b, e):
         ctx, T = self.ctx, self.timer

@@ -32,6 +32,24 @@ def format_results_py(results, first_index: int = 0) -> str:
     return "".join(out)
 
 
+def format_topk(topk, first_index: int = 0) -> str:
+    """Top-K rows (int [n, K, 3] of (score, n, k), padded with (INT32_MIN, 0, 0)) as text: rank 1 of record i
+    exactly as :func:`format_results` prints it, "#i: score: S, n: N, k: K"; ranks j >= 2 as
+    "#i.j: score: S, n: N, k: K", real candidates only."""
+    t = np.asarray(topk, dtype=np.int64)
+    if t.ndim != 3 or t.shape[2] != 3:
+        raise ValueError("format_topk needs an [n, K, 3] array")
+    none = np.iinfo(np.int32).min
+    out = []
+    for i, rows in enumerate(t):
+        s, n, k = rows[0]
+        out.append(f"#{i + first_index}: score: {s}, n: {n}, k: {k}\n")
+        for j, (s, n, k) in enumerate(rows[1:], start=2):
+            if s != none:
+                out.append(f"#{i + first_index}.{j}: score: {s}, n: {n}, k: {k}\n")
+    return "".join(out)
+
+
 def write_results(results: np.ndarray, stream=None, first_index: int = 0):
     stream = stream or sys.stdout
     stream.write(format_results(results, first_index))
