@@ -36,7 +36,7 @@ GPU_PLUGIN := mpi_openmp_cuda_amd/lib/libmoc_final_gpu.so
 
 # host core without any ROCm dependency (parser, CPU engine, partitioner, runtime utilities)
 CPU_SRCS  := csrc/src/cpu_engine.cpp csrc/src/device_batch.cpp csrc/src/io.cpp csrc/src/partition.cpp csrc/src/problem.cpp csrc/src/wire.cpp \
-             csrc/src/score_table.cpp csrc/src/runtime/runtime.cpp csrc/src/runtime/host_region.cpp \
+             csrc/src/score_table.cpp csrc/src/tile_plan.cpp csrc/src/runtime/runtime.cpp csrc/src/runtime/host_region.cpp \
              csrc/src/runtime/kfd_topology.cpp csrc/src/runtime/watchdog.cpp
 # host code of the GPU engine (HIP runtime API) and the C ABI of libmoc.so
 GPU_SRCS  := csrc/src/hip_engine.cpp csrc/src/capi.cpp csrc/src/runtime/device.cpp csrc/src/runtime/pinned.cpp
@@ -54,7 +54,7 @@ COMM_OBJS := $(OBJ)/comm/comm.o $(OBJ)/comm/mpi_device_comm.o
 RCCL_OBJS := $(OBJ)/comm/rccl_comm.o
 HEADERS   := $(shell find csrc/include -name '*.h' -o -name '*.hpp')
 
-.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san
+.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san
 
 all: build
 build: lib final $(GPU_PLUGIN)
@@ -216,6 +216,13 @@ $(BUILD)/psan/%.o: csrc/src/%.cpp $(HEADERS)
 	$(CXX) $(PSAN_FLAGS) -c $< -o $@
 $(BUILD)/profile_san: csrc/tests/profile_san.cpp $(PSAN_OBJS) $(HEADERS)
 	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/profile_san.cpp $(PSAN_OBJS) -ldl
+
+# stand-alone ASan/UBSan run of the tile planner's tests (moc/tile_plan.hpp): test_core itself, built like
+# profile_san, running only the tests named *plan* (host code only)
+tile-plan-san: $(BUILD)/tile_plan_san
+	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/tile_plan_san plan
+$(BUILD)/tile_plan_san: csrc/tests/test_core.cpp csrc/apps/text_cut.cpp csrc/apps/text_cut.hpp $(PSAN_OBJS) $(HEADERS)
+	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/test_core.cpp csrc/apps/text_cut.cpp $(PSAN_OBJS) -ldl
 
 # parser throughput (count vs fill, SIMD A/B): build/fill_bench [records]
 $(BUILD)/fill_bench: tools/fill_bench.cpp $(CPU_OBJS) $(HEADERS)

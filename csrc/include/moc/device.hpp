@@ -256,8 +256,12 @@ void launch_tile16_keys(const ProblemView& pv, const BatchView& bv, const Plan& 
 void launch_tile_mfma_sweep(const ProblemView& pv, const BatchView& bv, const Plan& plan, hipStream_t stream);
 // i8 MFMA operand/accumulator layout self-test: C = A * B (row-major 32x32 int8 -> int32), one wave.
 void launch_mfma_i8_probe(const int8_t* d_a, const int8_t* d_b, int* d_c, hipStream_t stream);
-// Waves per CU the tile16 kernel keeps resident (16-wave workgroups, as many as the LDS allows).
-int tile16_waves_per_cu(int lds_bytes);
+// Waves per CU the tile16 kernel keeps resident (16-wave workgroups, as many as the LDS allows — at most two);
+// lds_bytes: the whole image a workgroup stages.
+inline int tile16_waves_per_cu(int lds_bytes) {
+  const int blocks = lds_bytes > 0 ? kProf16MaxLds / lds_bytes : 2;
+  return kTile16WavesPerBlock * (blocks < 1 ? 1 : blocks > 2 ? 2 : blocks);
+}
 
 // ---- per-offset score profile and top-K selection (profile_kernels.hip; definitions: moc/cpu_engine.hpp)
 // One chunk of consecutive records [rec0, rec0 + n) of a batch: `starts` is a wave plan in the LUT-tile

@@ -1,4 +1,5 @@
-// Per-rank GPU engine: problem upload, launch planning, and host<->device data movement.
+// Per-rank GPU engine: problem upload, launches, and host<->device data movement. The tile kernels' work is
+// planned on the host by moc/tile_plan.hpp (no HIP call there: plans are checked without a device).
 //
 // Reference: send_divided_Seq2_To_Cuda (cudaFunctions.cu:178-242) — cudaMalloc per call and per
 // record (leaking all but the last dev_count_signs), a blocking H2D of the whole fixed-stride chunk,
@@ -29,6 +30,7 @@
 #include "moc/device.hpp"
 #include "moc/runtime/timer.hpp"
 #include "moc/score_table.hpp"
+#include "moc/tile_plan.hpp"
 
 namespace moc {
 
@@ -167,44 +169,49 @@ class HipEngine {
   const EngineStats& stats() const { return stats_; }
   int device() const { return device_; }
   hipStream_t compute_stream() const { return s_compute_; }
-  int64_t L1() const { return L1_; }
-  int num_cus() const { return num_cus_; }
+  int64_t L1() const { return cfg_.L1; }
+  int num_cus() const { return cfg_.num_cus; }
 
  private:
   struct Slot;  // one double-buffer half
-  struct ChunkPlan {
-    int64_t min_short = 0, max_l2 = 0, n_short = 0, cells = 0;
-    std::vector<int32_t> long_recs;
+  // One chunk classified and planned: the short / swipe kernel's arguments and the tile plan of the rest.
+  struct PlannedBatch {
+    plan::ChunkPlan cp;
+    dev::ShortArgs a;
+    bool swipe = false, short_ok = false;
+    bool all_tiles = false;  // the short kernel cannot hold its records (LDS budget): the tile kernel takes all
+    int64_t n_long = 0;
+    plan::TilePlan tp;
+    std::vector<dev::WaveStart> starts;  // empty: no tile launch
+    plan::PlanLayout lay{0, 0};
+    const int32_t* lrecs() const { return all_tiles ? nullptr : cp.long_recs.data(); }  // null: the identity list
+    size_t plan_bytes() const { return lay.total + (lrecs() ? 0 : sizeof(unsigned long long) * static_cast<size_t>(n_long)); }
   };
-  void plan_chunk(const int64_t* offsets, int64_t n, ChunkPlan& cp) const;
-  struct TilePlan {
-    int u = 2;              // sub-tiles per wave tile
-    int win_tiles = 0;      // windowed tile16: tiles per window stride
-    bool tile16 = false;    // the plan is for the tile16 sweep (else the LUT tile kernel)
-    int64_t window = 0;     // tile16: columns per LDS window (0: the whole profile is the image)
-    bool wide = false;      // tile16: widened int16-pair entries
-    bool slide = false;     // tile16: sliding widened windows (window = their columns; dev::Plan::slide_*)
-    int64_t slide_items = 0, slide_members = 0, slide_wgs = 0;
-    int slide_per_cu = 1;  // workgroups per CU the slide plan is for (1, or 2 with half-LDS windows)
+  struct Ran {
+    int32_t kernels = 0, forms = 0;  // EngineStats bits
   };
-  std::vector<dev::WaveStart> plan_waves(const int64_t* offsets, const int32_t* long_recs, int64_t n_long, int part,
-                                         int parts, TilePlan& tp) const;
-  bool plan_slide(const int64_t* offsets, const int32_t* long_recs, int64_t n_long, double min_fill, TilePlan& tp,
-                  std::vector<dev::WaveStart>& starts) const;
-  dev::Plan device_plan(void* d_plan, size_t n_starts, bool has_long_recs, int64_t n_long, const TilePlan& tp) const;
+  void plan_batch(const int64_t* offsets, int64_t n, ResultFormat fmt, PlannedBatch& pb) const;
+  void upload_plan(const PlannedBatch& pb, void*& h_plan, size_t& h_cap, void*& d_plan, size_t& d_cap, hipStream_t s);
+  Ran launch_planned(PlannedBatch& pb, const dev::BatchView& bv, int64_t first_offset, void* d_out, unsigned* counter,
+                     void* d_plan, ResultFormat fmt, hipStream_t s);
+  std::vector<int64_t> upload_batch(const uint8_t* codes, const int64_t* offsets, int64_t n, size_t out_bytes);
+  void host_call_stats(Stopwatch& wall, double kernel_ms, int64_t letters, int64_t n, size_t d2h_bytes);
+  void ensure_device_events();  // ev_d0_ / ev_d1_, made by the first call that records them
+  dev::Plan device_plan(void* d_plan, size_t n_starts, bool has_long_recs, int64_t n_long, const plan::TilePlan& tp,
+                        unsigned long long* keys = nullptr) const;
   // problem view for a plan: without the profile when the plan is for the LUT tile kernel
-  dev::ProblemView tile_view(int64_t max_l2, const TilePlan& tp) const {
+  dev::ProblemView tile_view(int64_t max_l2, const plan::TilePlan& tp) const {
     dev::ProblemView pv = problem_view(max_l2);
     if (!tp.tile16) {
       pv.prof16 = nullptr;
       pv.mfma_sweep = 0;
     } else {  // the plan's image: whole or windowed, byte pairs or widened
       pv.prof16_window = static_cast<int32_t>(tp.window);
-      pv.prof16_bytes = tp.window ? static_cast<int32_t>(dev::tile16_window_bytes(tp.window)) : prof16_bytes_;
+      pv.prof16_bytes = tp.window ? static_cast<int32_t>(dev::tile16_window_bytes(tp.window)) : cfg_.prof16_bytes;
       pv.prof16_wide = tp.wide ? 1 : 0;
       pv.t16_slide = tp.slide ? tp.slide_per_cu : 0;
       if (tp.window) pv.mfma_sweep = 0;
-      if (!pv.mfma_sweep) pv.t16_key_bits = bounds::tile16_key32_bits(L1_, table_.max_abs(), max_l2);
+      if (!pv.mfma_sweep) pv.t16_key_bits = bounds::tile16_key32_bits(cfg_.L1, table_.max_abs(), max_l2);
     }
     return pv;
   }
@@ -222,13 +229,7 @@ class HipEngine {
 
   EngineOptions opt_;
   int device_ = 0;
-  int num_cus_ = 256;
-  int tile_u_ = 0;              // tile-kernel sub-tiles per wave tile (0 = per batch; MOC_TILE_U = 1|2|4)
-  bool tile16_window_wide_ = true;  // widened windows for short records where the widened whole image is too big
-  bool short_window_u8_ = true;     // ... with 8 sub-tiles per wave tile (MOC_TILE16_WIN_U8=0: 4)
-  bool tile16_slide_ = true;        // long records past the widened image: sliding windows (MOC_TILE16_SLIDE=0: not)
-  int slide_wgs_per_cu_ = 2;        // ... two workgroups per CU, half-LDS windows (MOC_TILE16_SLIDE_WG=1: one)
-  int tile_waves_per_cu_ = 32;  // tile-kernel waves per CU (MOC_TILE_WAVES_PER_CU)
+  plan::Config cfg_;  // the problem's length and profile geometry, the device's CUs, the tuning switches
   hipStream_t s_copy_ = nullptr, s_compute_ = nullptr, s_return_ = nullptr;  // copy / return: made on first use
   void ensure_side_streams();
   // problem
@@ -248,16 +249,8 @@ class HipEngine {
   int32_t* d_lut_ = nullptr;
   uint8_t* d_seq1_ = nullptr;
   uint16_t* d_prof16_ = nullptr;  // tile16 profile (null: the problem does not fit it, or MOC_TILE16=0)
-  int32_t prof16_bytes_ = 0;
-  int32_t prof16_overhang_ = 0;  // zero profile entries past the last row (bounds the tile span)
-  int32_t prof16_window_ = 0;    // > 0: windowed tile16 (columns per workgroup window; Seq1 > one LDS image)
   int64_t prof16_entries_ = 0;   // entries of the device profile (windowed staging bounds)
-  int32_t prof16_lds_bytes_ = 0; // LDS bytes of the profile part of a workgroup's image
-  bool prof16_wide_ = false;      // the sweep stages widened int16 pairs (dev::ProblemView::prof16_wide)
-  bool prof16_i16_ = false;       // the profile holds one int16 Dt per entry (dev::ProblemView::prof16_i16)
   bool tile16_ = true;            // MOC_TILE16 (A/B switch of the long-record kernel)
-  bool mfma_ = false;             // MOC_MFMA: tile16 plans swept on the matrix cores (tile_mfma_kernels.hip)
-  int64_t L1_ = 0;
   Semantics sem_ = Semantics::Reference;
   bool have_problem_ = false;
   std::vector<std::unique_ptr<Slot>> slots_;

@@ -1,7 +1,7 @@
 // Long-record search kernels (gfx950, wave64). Work unit: a wave tile = (record, 63·U consecutive
 // offsets) as U sub-tiles of 63 owned offsets + 1 helper lane that advance together (they share each
 // Seq2 letter; their dependency chains interleave). Persistent waves walk cost-balanced contiguous runs
-// of the record-major tile list (host plan: moc::HipEngine::plan_waves), keeping a record's letters in
+// of the record-major tile list (host plan: moc::plan::plan_waves), keeping a record's letters in
 // registers and its running best key across the run (one reduction + atomic per record run).
 //
 // Replaces calc_result (cudaFunctions.cu:63-176) for records whose offset range does not fit in one

@@ -657,7 +657,7 @@ __global__ __launch_bounds__(kBlock16) void tile16_search_kernel(ProblemView pv,
 // [o0 + iw, o0 + iw + span + C), so the workgroup stages that window (widened, W = span + C columns), runs the
 // window's 64-step chunks, and slides on. The per-offset state stays in registers across windows; waves
 // whose record ends early (or has fewer tiles) only join the barriers. Items (group, tiles [t0, t1)) are
-// LPT-balanced over the workgroups on the host (HipEngine::plan_waves).
+// LPT-balanced over the workgroups on the host (plan::plan_slide, moc/tile_plan.hpp).
 //   plan16[0 .. n_wg]: workgroup b takes items [plan16[b].li, plan16[b + 1].li);
 //   plan16[items + 2k]     = {group g, t0},  plan16[items + 2k + 1] = {group's longest record, t1};
 //   plan16[members + 16g + w] = {li (-1: none), L2} — wave w's record.
@@ -846,11 +846,6 @@ void tile16_slide_kernel(ProblemView pv, BatchView bv,
       if (lane == 0 && kk != 0ull) atomicMax(keys + li, kk);
     }
   }
-}
-
-int tile16_waves_per_cu(int lds_bytes) {  // lds_bytes: the whole image a workgroup stages
-  const int blocks = lds_bytes > 0 ? kProf16MaxLds / lds_bytes : 2;
-  return kWavesPerBlock16 * max(1, min(2, blocks));
 }
 
 namespace {

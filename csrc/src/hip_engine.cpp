@@ -7,7 +7,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <future>
-#include <queue>
 #include <string>
 
 #include "moc/cpu_engine.hpp"
@@ -136,16 +135,16 @@ HipEngine::HipEngine(const EngineOptions& opt) : opt_(opt) {
   init_sw.start();
   if (opt_.device >= 0) MOC_HIP_CHECK(hipSetDevice(opt_.device));
   MOC_HIP_CHECK(hipGetDevice(&device_));
-  MOC_HIP_CHECK(hipDeviceGetAttribute(&num_cus_, hipDeviceAttributeMultiprocessorCount, device_));
+  MOC_HIP_CHECK(hipDeviceGetAttribute(&cfg_.num_cus, hipDeviceAttributeMultiprocessorCount, device_));
   const double t_dev = init_sw.total_ms();
-  if (const char* m = std::getenv("MOC_MFMA")) mfma_ = std::atoi(m) != 0;
+  if (const char* m = std::getenv("MOC_MFMA")) cfg_.mfma = std::atoi(m) != 0;
   unsigned set = opt_.preload;
   if (const char* p = std::getenv("MOC_PRELOAD")) {
     const int v = dev::parse_preload_set(p);
     if (v < 0) throw Error(std::string("MOC_PRELOAD: unknown kernel file in '") + p + "'");
     set = static_cast<unsigned>(v);
   }
-  if (mfma_ && (set & dev::kPreloadTile16)) set |= dev::kPreloadMfma;
+  if (cfg_.mfma && (set & dev::kPreloadTile16)) set |= dev::kPreloadMfma;
   // code objects on the device now, not inside the first timed launch, and the image's page-locked staging
   // — on a helper thread, while this one sets up the compute stream and buffers (independent runtime work,
   // ~13 and ~20 ms on the MI355X box)
@@ -159,18 +158,18 @@ HipEngine::HipEngine(const EngineOptions& opt) : opt_(opt) {
   if (const char* g = std::getenv("MOC_GRAPHS")) opt_.use_graphs = std::atoi(g) != 0;
   if (const char* u = std::getenv("MOC_TILE_U")) {  // tuning override of the per-batch choice
     const int v = std::atoi(u);
-    if (v == 1 || v == 2 || v == 4 || v == 8) tile_u_ = v;
+    if (v == 1 || v == 2 || v == 4 || v == 8) cfg_.tile_u = v;
   }
   if (const char* t16 = std::getenv("MOC_TILE16")) tile16_ = std::atoi(t16) != 0;
   if (const char* pt = std::getenv("MOC_PROFILE_TIMING")) profile_timing_ = std::atoi(pt) != 0;
   // MOC_TILE16_WINWIDE=0: short records on an L1 ~ 1500..3050 problem keep the whole byte-pair image (A/B)
-  if (const char* ww = std::getenv("MOC_TILE16_WINWIDE")) tile16_window_wide_ = std::atoi(ww) != 0;
-  if (const char* w8 = std::getenv("MOC_TILE16_WIN_U8")) short_window_u8_ = std::atoi(w8) != 0;
-  if (const char* sl = std::getenv("MOC_TILE16_SLIDE")) tile16_slide_ = std::atoi(sl) != 0;
-  if (const char* sw = std::getenv("MOC_TILE16_SLIDE_WG")) slide_wgs_per_cu_ = std::atoi(sw) == 1 ? 1 : 2;
+  if (const char* ww = std::getenv("MOC_TILE16_WINWIDE")) cfg_.tile16_window_wide = std::atoi(ww) != 0;
+  if (const char* w8 = std::getenv("MOC_TILE16_WIN_U8")) cfg_.short_window_u8 = std::atoi(w8) != 0;
+  if (const char* sl = std::getenv("MOC_TILE16_SLIDE")) cfg_.tile16_slide = std::atoi(sl) != 0;
+  if (const char* sw = std::getenv("MOC_TILE16_SLIDE_WG")) cfg_.slide_wgs_per_cu = std::atoi(sw) == 1 ? 1 : 2;
   if (const char* w = std::getenv("MOC_TILE_WAVES_PER_CU")) {
     const int v = std::atoi(w);
-    if (v >= 1 && v <= 32) tile_waves_per_cu_ = v;
+    if (v >= 1 && v <= 32) cfg_.tile_waves_per_cu = v;
   }
   // the compute stream only: each stream costs ~10 ms of hardware-queue set-up on the MI355X box
   // (profiles/hip_init_variants_box.log), and the streaming kernels need no other; the staged pipeline
@@ -271,7 +270,7 @@ void HipEngine::ensure_host(void*& ptr, size_t& cap, size_t bytes) {
 void HipEngine::set_problem(const Weights& w, const uint8_t* seq1, int64_t L1, Semantics sem) {
   finish_wire();
   // the same problem again (every step of a repeated job): nothing to rebuild or upload
-  if (have_problem_ && sem == sem_ && L1 == L1_ && std::equal(w.w, w.w + 4, last_w_.w) &&
+  if (have_problem_ && sem == sem_ && L1 == cfg_.L1 && std::equal(w.w, w.w + 4, last_w_.w) &&
       (L1 == 0 || std::memcmp(seq1, last_seq1_.data(), static_cast<size_t>(L1)) == 0))
     return;
   MOC_HIP_CHECK(hipSetDevice(device_));
@@ -287,7 +286,6 @@ void HipEngine::set_problem(const Weights& w, const uint8_t* seq1, int64_t L1, S
       min_t_ = std::min(min_t_, table_.lut[x * kLutStride + y]);
       max_t_ = std::max(max_t_, table_.lut[x * kLutStride + y]);
     }
-  L1_ = L1;
   sem_ = sem;
   // One device image per problem, uploaded with one copy: LUT | Seq1 + zero pad | tile16 profile. The
   // buffer only grows, so repeated problems (one per job step) cost no allocation, and kernel arguments
@@ -296,41 +294,18 @@ void HipEngine::set_problem(const Weights& w, const uint8_t* seq1, int64_t L1, S
   const size_t lut_bytes = sizeof(int32_t) * table_.lut.size();
   const size_t s1_off = (lut_bytes + 255) & ~size_t{255};
   const size_t prof_off = (s1_off + s1bytes + 255) & ~size_t{255};
+  // the tile16 profile, when the weights fit it, and the geometry every plan of this problem starts from
   Profile16 prof;
-  // the overhang (zero entries past the last row) must cover the widest tile span, 128*U entries: 1024
-  // when that still fits the LDS (U = 8 for short records), else 512 (U <= 4, L1 up to 3052)
-  auto prof_bytes = [&](int64_t oh) { return ((2 * ((kAlphabet - 1) * L1 + oh)) + 15) & ~int64_t{15}; };
-  // Occupancy first: a CU holds two 16-wave workgroups when the image fits half its LDS, and the sweep is
-  // latency-bound, so the wide overhang (U = 8 tiles, for short records only) is kept only where it costs no
-  // workgroup: input3's 1489-letter Seq1 fits twice with 512 (32 waves per CU), once with 1024 (16).
-  int64_t overhang = 2 * dev::kProf16Overhang;
-  const int64_t half = dev::kProf16MaxLds / 2;
-  if (dev::tile16_lds_bytes(prof_bytes(overhang), L1) > dev::kProf16MaxLds ||
-      (dev::tile16_lds_bytes(prof_bytes(overhang), L1) > half &&
-       dev::tile16_lds_bytes(prof_bytes(dev::kProf16Overhang), L1) <= half))
-    overhang = dev::kProf16Overhang;
-  int64_t pbytes = prof_bytes(overhang);
-  // Seq1 too long for one LDS image: the whole profile lives in device memory and each workgroup stages
-  // a window of it (tile16_search_kernel<U, true>); records must then fit a window with two tiles' slack
-  const bool whole = dev::tile16_lds_bytes(pbytes, L1) <= dev::kProf16MaxLds;
-  const int64_t window = whole ? 0 : dev::tile16_max_window();
-  // weights past the byte pairs (|Dt| > 127) up to |Dt| <= 511: one int16 Dt per entry, which only the widened
-  // images take (whole where it fits, windows for short records; otherwise the LUT tile kernel)
-  const bool t16 = tile16_ && L1 > 0 && build_profile16(table_, seq1, L1, overhang, prof, /*allow_i16=*/true);
-  prof16_i16_ = t16 && prof.i16;
-  prof16_window_ = t16 && !prof16_i16_ ? static_cast<int32_t>(window) : 0;
-  prof16_entries_ = t16 ? static_cast<int64_t>(prof.entries.size()) : 0;
-  prof16_lds_bytes_ = t16 ? dev::tile16_profile_lds_bytes(L1, overhang, prof16_i16_) : 0;
-  pbytes = (2 * static_cast<int64_t>(prof.entries.size()) + 15) & ~int64_t{15};
-  prof16_overhang_ = t16 ? static_cast<int>(overhang) : 0;
-  // widened entries (two int16 halves per column: one packed add per lane and step) where the doubled image
-  // still fits one CU; MOC_TILE16_WIDE=0 keeps the byte pairs (A/B runs, same results)
+  const bool t16 = tile16_ && L1 > 0 &&
+                   build_profile16(table_, seq1, L1, plan::profile16_overhang(L1), prof, /*allow_i16=*/true);
+  // MOC_TILE16_WIDE=0 keeps a whole image's byte pairs (A/B runs, same results)
   static const bool wide_env = [] {
     const char* v = std::getenv("MOC_TILE16_WIDE");
     return !(v && std::atoi(v) == 0);
   }();
-  prof16_wide_ = t16 && (whole || prof16_i16_) && (wide_env || prof16_i16_) &&
-                 dev::tile16_lds_bytes(2 * static_cast<int64_t>(prof16_lds_bytes_), L1) <= dev::kProf16MaxLds;
+  plan::set_profile_geometry(cfg_, L1, t16 ? &prof : nullptr, wide_env);
+  prof16_entries_ = t16 ? static_cast<int64_t>(prof.entries.size()) : 0;
+  const int64_t pbytes = (2 * static_cast<int64_t>(prof.entries.size()) + 15) & ~int64_t{15};
   const size_t total = t16 ? prof_off + static_cast<size_t>(pbytes) : prof_off;
   std::vector<uint8_t> next(total, 0);
   std::memcpy(next.data(), table_.lut.data(), lut_bytes);
@@ -339,7 +314,6 @@ void HipEngine::set_problem(const Weights& w, const uint8_t* seq1, int64_t L1, S
   // the same problem again (one per job step of a repeated job): the device image is already current —
   // no device-wide synchronisation, no copy
   if (!image_.empty() && next == image_ && d_image_) {
-    prof16_bytes_ = prof16_lds_bytes_;
     last_w_ = w;
     last_seq1_.assign(seq1, seq1 + L1);
     have_problem_ = true;
@@ -372,7 +346,6 @@ void HipEngine::set_problem(const Weights& w, const uint8_t* seq1, int64_t L1, S
   d_lut_ = reinterpret_cast<int32_t*>(base);
   d_seq1_ = reinterpret_cast<uint8_t*>(base + s1_off);
   d_prof16_ = t16 ? reinterpret_cast<uint16_t*>(base + prof_off) : nullptr;
-  prof16_bytes_ = prof16_lds_bytes_;
   last_w_ = w;
   last_seq1_.assign(seq1, seq1 + L1);
   have_problem_ = true;
@@ -388,406 +361,113 @@ dev::ProblemView HipEngine::problem_view(int64_t max_l2) const {
   dev::ProblemView pv;
   pv.lut = d_lut_;
   pv.seq1 = d_seq1_;
-  pv.L1 = static_cast<int32_t>(L1_);
+  pv.L1 = static_cast<int32_t>(cfg_.L1);
   pv.semantics = static_cast<int32_t>(sem_);
-  pv.key_shift = choose_key_shift(table_.max_abs(), std::min<int64_t>(std::max<int64_t>(max_l2, 1), L1_ + 1));
+  pv.key_shift = choose_key_shift(table_.max_abs(), std::min<int64_t>(std::max<int64_t>(max_l2, 1), cfg_.L1 + 1));
   pv.r2 = r2_;
   pv.prof16 = d_prof16_;
-  pv.prof16_bytes = prof16_bytes_;
-  pv.prof16_window = prof16_window_;
+  pv.prof16_bytes = cfg_.prof16_bytes;
+  pv.prof16_window = cfg_.prof16_window;
   pv.prof16_entries = prof16_entries_;
-  pv.prof16_wide = prof16_wide_ && !mfma_ ? 1 : 0;
-  pv.prof16_i16 = prof16_i16_ ? 1 : 0;
+  pv.prof16_wide = cfg_.prof16_wide && !cfg_.mfma ? 1 : 0;
+  pv.prof16_i16 = cfg_.prof16_i16 ? 1 : 0;
   pv.max_abs_t = table_.max_abs();
-  pv.mfma_sweep = mfma_ && d_prof16_ && !prof16_window_ && !prof16_i16_ ? 1 : 0;
+  pv.mfma_sweep = cfg_.mfma && d_prof16_ && !cfg_.prof16_window && !cfg_.prof16_i16 ? 1 : 0;
   return pv;
 }
 
 ResultFormat HipEngine::auto_format(int64_t max_l2, int64_t min_l2) const {
   R2Params p;
-  if (min_l2 > 0 && r2_params(L1_, min_l2, max_l2, min_t_, max_t_, p)) return ResultFormat::R2;
-  return pick_result_format(L1_, max_l2, table_.max_abs());
+  if (min_l2 > 0 && r2_params(cfg_.L1, min_l2, max_l2, min_t_, max_t_, p)) return ResultFormat::R2;
+  return pick_result_format(cfg_.L1, max_l2, table_.max_abs());
 }
 
 R2Params HipEngine::r2_params_for(int64_t min_l2, int64_t max_l2) const {
   R2Params p;
-  if (!r2_params(L1_, min_l2, max_l2, min_t_, max_t_, p)) throw Error("R2 cannot hold records of these lengths");
+  if (!r2_params(cfg_.L1, min_l2, max_l2, min_t_, max_t_, p)) throw Error("R2 cannot hold records of these lengths");
   return p;
 }
 
-// Splits a chunk's records into the short-kernel set (<= 64 lanes) and the long list (tile kernel).
-// OpenMP: per-thread partial lists are concatenated in thread order, so long_recs stays sorted.
-void HipEngine::plan_chunk(const int64_t* offsets, int64_t n, ChunkPlan& cp) const {
-  cp.long_recs.clear();
-  const int64_t short_min_len = std::max<int64_t>(L1_ - (dev::kWave - 1), 0);  // lanes_needed <= 64
-  const int nt = n > (1 << 16) ? omp_get_max_threads() : 1;
-  std::vector<std::vector<int32_t>> part(nt);
-  std::vector<int64_t> mins(nt, INT64_MAX), maxs(nt, 0), nshort(nt, 0), cells(nt, 0);
-#pragma omp parallel for schedule(static, 1) num_threads(nt)  // parts, not thread ids (any team size)
-  for (int t = 0; t < nt; ++t) {
-    const int64_t b = n * t / nt, e = n * (t + 1) / nt;
-    int64_t mn = INT64_MAX, mx = 0, ns = 0, cl = 0;
-    for (int64_t i = b; i < e; ++i) {
-      const int64_t L2 = offsets[i + 1] - offsets[i];
-      mx = std::max(mx, L2);
-      cl += record_cells(L1_, L2);
-      if (L2 >= short_min_len) {
-        mn = std::min(mn, L2);
-        ++ns;
-      } else {
-        part[t].push_back(static_cast<int32_t>(i));
-      }
-    }
-    mins[t] = mn;
-    maxs[t] = mx;
-    nshort[t] = ns;
-    cells[t] = cl;
-  }
-  cp.min_short = INT64_MAX;
-  cp.max_l2 = 0;
-  cp.n_short = 0;
-  cp.cells = 0;
-  for (int t = 0; t < nt; ++t) {
-    cp.min_short = std::min(cp.min_short, mins[t]);
-    cp.max_l2 = std::max(cp.max_l2, maxs[t]);
-    cp.n_short += nshort[t];
-    cp.cells += cells[t];
-    cp.long_recs.insert(cp.long_recs.end(), part[t].begin(), part[t].end());
-  }
-  if (L1_ >= (int64_t{1} << 30) || cp.max_l2 >= (int64_t{1} << 30))
-    throw Error("Seq1 / Seq2 lengths beyond 2^30 exceed the device engine's offset range");
-}
-
-namespace {
-// Layout of one chunk's tile plan in a single buffer: wave starts | long_recs | keys (8-aligned).
-struct PlanLayout {
-  size_t starts_off = 0, long_off = 0, keys_off = 0, upload_bytes = 0, total = 0;
-  PlanLayout(size_t n_starts, size_t n_long) {
-    long_off = n_starts * sizeof(dev::WaveStart);
-    keys_off = (long_off + n_long * sizeof(int32_t) + 7) & ~size_t{7};
-    upload_bytes = long_off + n_long * sizeof(int32_t);
-    total = keys_off + n_long * sizeof(unsigned long long);
-  }
-};
-
-// Per-tile fixed cost in step units (record/tile setup, the wave reduction), for load balancing.
-constexpr int64_t kTileOverheadSteps = 24;
-// Staging one sliding window (tile16_slide_kernel), per wave, in step units.
-constexpr int64_t kSlideStageSteps = 96;
-
-// Part `part` of `parts` (by cost) of a record-major tile list — record li has ntiles[li] tiles of tcost[li]
-// each — cut into contiguous, cost-balanced runs for at most max_waves waves: n_waves + 1 run boundaries.
-std::vector<dev::WaveStart> balanced_runs(const std::vector<int32_t>& ntiles, const std::vector<int64_t>& tcost,
-                                          int64_t total_tiles, int part, int parts, int64_t max_waves) {
-  const int64_t n_long = static_cast<int64_t>(ntiles.size());
-  std::vector<int64_t> pre(static_cast<size_t>(n_long) + 1, 0);
-  for (int64_t li = 0; li < n_long; ++li) pre[li + 1] = pre[li] + ntiles[li] * tcost[li];
-  const int64_t C = pre[n_long];
-  const int64_t lo = C * part / parts, hi = C * (part + 1) / parts;
-  // position of cost threshold X in (li, t): first tile whose start cost is >= X
-  auto locate = [&](int64_t X) {
-    if (X >= C) return dev::WaveStart{static_cast<int32_t>(n_long), 0};
-    const int64_t li = std::upper_bound(pre.begin(), pre.end(), X) - pre.begin() - 1;
-    const int64_t t = (X - pre[li] + tcost[li] - 1) / tcost[li];
-    if (t >= ntiles[li]) return dev::WaveStart{static_cast<int32_t>(li + 1), 0};
-    return dev::WaveStart{static_cast<int32_t>(li), static_cast<int32_t>(t)};
-  };
-  const int64_t part_tiles = std::max<int64_t>(1, total_tiles * (hi - lo) / std::max<int64_t>(C, 1));
-  const int64_t n_waves = std::min<int64_t>(part_tiles, max_waves);
-  std::vector<dev::WaveStart> starts(static_cast<size_t>(n_waves) + 1);
-  for (int64_t w = 0; w <= n_waves; ++w) starts[w] = locate(lo + (hi - lo) * w / n_waves);
-  return starts;
-}
-}  // namespace
-
-// Device view of an uploaded plan buffer (starts | long_recs | keys). Identity record lists upload no
-// long_recs (PlanLayout built with n_long = 0): their keys follow the starts.
+// Device view of an uploaded plan buffer (starts | long_recs | keys; plan::PlanLayout), or of the starts alone
+// with the caller's `keys`. No starts: no waves.
 dev::Plan HipEngine::device_plan(void* d_plan, size_t n_starts, bool has_long_recs, int64_t n_long,
-                                 const TilePlan& tp) const {
-  const PlanLayout lay(n_starts, has_long_recs ? static_cast<size_t>(n_long) : 0);
+                                 const plan::TilePlan& tp, unsigned long long* keys) const {
+  const plan::PlanLayout lay(n_starts, has_long_recs ? static_cast<size_t>(n_long) : 0);
   char* base = static_cast<char*>(d_plan);
   dev::Plan plan;
   plan.u = tp.u;
   plan.win_tiles = tp.win_tiles;
-  plan.n_waves = tp.slide ? tp.slide_wgs * dev::kTile16WavesPerBlock : static_cast<int64_t>(n_starts) - 1;
+  plan.n_waves = n_starts == 0 ? 0
+                 : tp.slide    ? tp.slide_wgs * dev::kTile16WavesPerBlock
+                               : static_cast<int64_t>(n_starts) - 1;
   plan.slide_items = tp.slide_items;
   plan.slide_members = tp.slide_members;
   plan.starts = reinterpret_cast<const dev::WaveStart*>(base + lay.starts_off);
   plan.long_recs = has_long_recs ? reinterpret_cast<const int32_t*>(base + lay.long_off) : nullptr;
   plan.n_long = n_long;
-  plan.keys = reinterpret_cast<unsigned long long*>(base + lay.keys_off);
+  plan.keys = keys ? keys : reinterpret_cast<unsigned long long*>(base + lay.keys_off);
   plan.r2 = r2_;
   return plan;
 }
 
-// Sliding-window plan (tile16_slide_kernel): the long records sorted by length (longest first) in groups of 16,
-// one per wave of a workgroup; a group's tiles split into items of at most half a workgroup's share, the
-// items assigned largest first to the least-loaded workgroup (one 16-wave workgroup per CU: the window takes
-// most of the LDS). Encoding in `starts` (dev::Plan::slide_items / slide_members). False: no window fits, or
-// the groups would run less than min_fill of their waves (a few huge records: the other plans give every wave
-// a tile of its own; an int16 profile's other plan is the LUT tile kernel, so it takes emptier groups).
-bool HipEngine::plan_slide(const int64_t* offsets, const int32_t* long_recs, int64_t n_long, double min_fill,
-                           TilePlan& tp, std::vector<dev::WaveStart>& starts) const {
-  // 4 sub-tiles by default: limits 14.9 (U = 2) -> 16.7 T cells/s, the int16 profile on limits' lengths
-  // 10.6 -> 13.8 (profiles/tile16_r5/README.txt)
-  const int u = tile_u_ == 2 || (tile_u_ == 8 && slide_wgs_per_cu_ == 1) ? tile_u_ : 4;
-  const int span = dev::tile_span(true, u);
-  // two workgroups per CU with half the LDS each (8 waves per SIMD hide the sweep's LDS waits: limits 16.8 ->
-  // 17.6 T cells/s, the int16 profile 16.9 -> 18.0), or one with the widest window (MOC_TILE16_SLIDE_WG=1)
-  int64_t wmax = dev::tile16_max_window(true);
-  if (slide_wgs_per_cu_ == 2)
-    while (wmax > 0 && dev::tile16_lds_bytes(2 * dev::tile16_window_bytes(wmax), wmax) > dev::kProf16MaxLds / 2) --wmax;
-  const int64_t C = (wmax - span) / 64 * 64;  // steps per window
-  if (C < 64) return false;
-  constexpr int G = dev::kTile16WavesPerBlock;
-  if (static_cast<double>(n_long) < min_fill * static_cast<double>(G * ((n_long + G - 1) / G))) return false;
-  std::vector<int32_t> order(static_cast<size_t>(n_long));
-  std::vector<int32_t> steps(static_cast<size_t>(n_long));
-  for (int64_t li = 0; li < n_long; ++li) {
-    const int64_t r = long_recs ? long_recs[li] : li;
-    const int64_t L2 = offsets[r + 1] - offsets[r];
-    order[li] = static_cast<int32_t>(li);
-    steps[li] = static_cast<int32_t>(L2 <= L1_ ? L2 : 0);
-  }
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return steps[a] > steps[b]; });
-  const int64_t n_groups = (n_long + G - 1) / G;
-  struct Item {
-    int64_t cost;
-    int32_t g, t0, t1;
-  };
-  std::vector<Item> items;
-  std::vector<int32_t> glmax(static_cast<size_t>(n_groups), 0);
-  int64_t total = 0;
-  std::vector<int64_t> gcost(static_cast<size_t>(n_groups), 0);
-  std::vector<int32_t> gtiles(static_cast<size_t>(n_groups), 0);
-  for (int64_t g = 0; g < n_groups; ++g) {
-    int32_t lmax = 0, nt = 0;
-    for (int64_t k = g * G; k < std::min<int64_t>(n_long, (g + 1) * G); ++k) {
-      const int32_t st = steps[order[k]];
-      if (st <= 0) continue;
-      lmax = std::max(lmax, st);
-      nt = std::max<int32_t>(nt, static_cast<int32_t>(dev::tiles_of(L1_ - st + 1, span)));
-    }
-    glmax[g] = lmax;
-    gtiles[g] = nt;
-    // a tile: every wave in lockstep for the group's longest record, plus the staging of each window
-    gcost[g] = G * (lmax + kTileOverheadSteps + kSlideStageSteps * ((lmax + C - 1) / C));
-    total += gcost[g] * nt;
-  }
-  if (total <= 0) return false;
-  int64_t all_tiles = 0;
-  for (int64_t g = 0; g < n_groups; ++g) all_tiles += gtiles[g];
-  const int64_t n_wg = std::min<int64_t>(static_cast<int64_t>(num_cus_) * slide_wgs_per_cu_, all_tiles);
-  const double share = static_cast<double>(total) / static_cast<double>(n_wg);
-  for (int64_t g = 0; g < n_groups; ++g) {
-    if (gtiles[g] <= 0) continue;
-    const int32_t per = static_cast<int32_t>(std::max<int64_t>(1, static_cast<int64_t>(share / 2) / gcost[g]));
-    for (int32_t t0 = 0; t0 < gtiles[g]; t0 += per) {
-      const int32_t t1 = std::min(gtiles[g], t0 + per);
-      items.push_back(Item{gcost[g] * (t1 - t0), static_cast<int32_t>(g), t0, t1});
-    }
-  }
-  std::stable_sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.cost > b.cost; });
-  std::vector<std::vector<int32_t>> of(static_cast<size_t>(n_wg));
-  std::priority_queue<std::pair<int64_t, int64_t>, std::vector<std::pair<int64_t, int64_t>>, std::greater<>> load;
-  for (int64_t b = 0; b < n_wg; ++b) load.emplace(0, b);
-  for (size_t k = 0; k < items.size(); ++k) {
-    auto [l, b] = load.top();
-    load.pop();
-    of[static_cast<size_t>(b)].push_back(static_cast<int32_t>(k));
-    load.emplace(l + items[k].cost, b);
-  }
-  starts.clear();
-  starts.reserve(static_cast<size_t>(n_wg + 1 + 2 * static_cast<int64_t>(items.size()) + n_groups * G));
-  int32_t n_it = 0;
-  for (int64_t b = 0; b < n_wg; ++b) {
-    starts.push_back(dev::WaveStart{n_it, 0});
-    n_it += static_cast<int32_t>(of[b].size());
-  }
-  starts.push_back(dev::WaveStart{n_it, 0});
-  tp.slide_items = static_cast<int64_t>(starts.size());
-  for (int64_t b = 0; b < n_wg; ++b)
-    for (const int32_t k : of[b]) {
-      const Item& it = items[k];
-      starts.push_back(dev::WaveStart{it.g, it.t0});
-      starts.push_back(dev::WaveStart{glmax[it.g], it.t1});
-    }
-  tp.slide_members = static_cast<int64_t>(starts.size());
-  for (int64_t k = 0; k < n_groups * G; ++k) {
-    if (k < n_long) {
-      const int32_t li = order[k];
-      const int64_t r = long_recs ? long_recs[li] : li;
-      starts.push_back(dev::WaveStart{li, static_cast<int32_t>(offsets[r + 1] - offsets[r])});
-    } else {
-      starts.push_back(dev::WaveStart{-1, 0});
-    }
-  }
-  tp.slide_wgs = n_wg;
-  tp.slide_per_cu = slide_wgs_per_cu_;
-  tp.tile16 = true;
-  tp.wide = true;
-  tp.slide = true;
-  tp.u = u;
-  tp.window = span + C;
-  tp.win_tiles = 0;
-  return true;
+// Classifies a chunk (swipe / short kernel, and which records the tile kernel takes) and plans its tiles.
+void HipEngine::plan_batch(const int64_t* offsets, int64_t n, ResultFormat fmt, PlannedBatch& pb) const {
+  plan::plan_chunk(cfg_, offsets, n, pb.cp);
+  const plan::ChunkPlan& cp = pb.cp;
+  pb.a = dev::ShortArgs{};
+  pb.a.fmt = static_cast<int32_t>(fmt);
+  pb.swipe = cp.n_short > 0 && cp.long_recs.empty() &&
+             dev::configure_swipe(cfg_.L1, cp.min_short, cp.max_l2, table_.max_abs(), pb.a, true, sem_ == Semantics::Spec);
+  pb.short_ok = pb.swipe || (cp.n_short > 0 && dev::configure_short(cfg_.L1, cp.min_short, cp.max_l2, pb.a));
+  // records that the short kernel cannot hold (LDS budget) go to the tile kernel too (identity record list)
+  pb.all_tiles = cp.n_short > 0 && !pb.short_ok;
+  pb.n_long = pb.all_tiles ? n : static_cast<int64_t>(cp.long_recs.size());
+  pb.starts = plan::plan_waves(cfg_, offsets, pb.lrecs(), pb.n_long, 0, 1, pb.tp);
+  pb.lay = plan::PlanLayout(pb.starts.size(), pb.lrecs() ? static_cast<size_t>(pb.n_long) : 0);
 }
 
-// Cost-balanced contiguous wave runs over the record-major tile list of the long records (record li =
-// offsets-relative index long_recs[li], or li when long_recs is null), restricted to part `part` of
-// `parts` of the total cost (context-parallel shares). Returns n_waves + 1 starts (empty: no work).
-// tp: sub-tiles per wave tile, and which sweep the plan is for (tile16 when the problem has a profile and,
-// for a windowed one, the records fit a window — else the LUT tile kernel).
-// Windowed tile16 (Seq1 longer than one LDS image): the list is window-major — window m holds the tiles
-// t in [m*T, (m+1)*T) of every record, T = (W - span - max L2) / span so that their profile columns
-// [t*span, t*span + span + L2) all lie in [m*T*span, m*T*span + W) — and every window gets whole
-// workgroups of waves (16-aligned; its last wave is an empty marker ending at (n_long, m*T)), each
-// workgroup staging its window once.
-std::vector<dev::WaveStart> HipEngine::plan_waves(const int64_t* offsets, const int32_t* long_recs, int64_t n_long,
-                                                  int part, int parts, TilePlan& tp) const {
-  std::vector<dev::WaveStart> starts;
-  tp = TilePlan{};
-  if (n_long <= 0) return starts;
-  int64_t sum_l2 = 0, max_l2 = 0;
-  for (int64_t li = 0; li < n_long; ++li) {
-    const int64_t r = long_recs ? long_recs[li] : li;
-    const int64_t L2 = offsets[r + 1] - offsets[r];
-    sum_l2 += L2;
-    max_l2 = std::max(max_l2, L2 <= L1_ ? L2 : 0);
+// Packs starts | long_recs into the page-locked staging and queues their upload on `s` (no tiles: nothing).
+void HipEngine::upload_plan(const PlannedBatch& pb, void*& h_plan, size_t& h_cap, void*& d_plan, size_t& d_cap,
+                            hipStream_t s) {
+  if (pb.starts.empty()) return;
+  ensure(d_plan, d_cap, pb.plan_bytes());
+  ensure_host(h_plan, h_cap, std::max<size_t>(pb.lay.upload_bytes, 8));
+  std::memcpy(static_cast<char*>(h_plan) + pb.lay.starts_off, pb.starts.data(), pb.starts.size() * sizeof(dev::WaveStart));
+  if (pb.lrecs())
+    std::memcpy(static_cast<char*>(h_plan) + pb.lay.long_off, pb.lrecs(), static_cast<size_t>(pb.n_long) * sizeof(int32_t));
+  upload_staged(d_plan, h_plan, pb.lay.upload_bytes, s);
+}
+
+// Launches a planned batch on `s`: the short or swipe kernel over bv's records (letters at bv.codes, record i
+// at absolute offset offsets[i], the first at first_offset), then the tile kernel from the uploaded d_plan.
+HipEngine::Ran HipEngine::launch_planned(PlannedBatch& pb, const dev::BatchView& bv, int64_t first_offset, void* d_out,
+                                         unsigned* counter, void* d_plan, ResultFormat fmt, hipStream_t s) {
+  Ran ran;
+  const dev::ProblemView pv = problem_view(pb.cp.max_l2);
+  if (pb.short_ok) {
+    dev::ShortArgs& a = pb.a;
+    a.codes = bv.codes - first_offset;  // base: record i at base + offsets[i] (absolute offsets)
+    a.offsets = bv.offsets;
+    a.n = bv.n;
+    a.out = d_out;
+    a.counter = counter;
+    a.lane_direct = pb.swipe && lane_direct_enabled() ? 1 : 0;
+    if (pb.swipe)
+      dev::launch_swipe(pv, a, cfg_.num_cus, s);
+    else
+      dev::launch_short(pv, a, cfg_.num_cus, s);
+    ran.kernels |= pb.swipe ? 1 : 2;
+    ran.forms |= pb.swipe ? dev::swipe_launch_form(a) : dev::short_form(pv, a);
   }
-  int64_t W = prof16_window_;
-  bool wide = prof16_wide_ && !mfma_ && W == 0;
-  // a whole byte-pair image whose widened form does not fit (L1 ~ 1500..3050): short records take a widened
-  // WINDOW instead (one packed add per lane and step; the window holds U = 4 tiles plus the longest record)
-  if (W == 0 && d_prof16_ && !prof16_wide_ && !mfma_ && tile16_window_wide_ && tile_u_ <= 0 &&
-      max_l2 + 2 * 128 * 4 <= dev::tile16_max_window(true)) {
-    W = dev::tile16_max_window(true);
-    wide = true;
+  if (!pb.starts.empty()) {
+    const dev::Plan plan = device_plan(d_plan, pb.starts.size(), pb.lrecs() != nullptr, pb.n_long, pb.tp);
+    const dev::ProblemView tpv = tile_view(pb.cp.max_l2, pb.tp);  // the plan's image: whole / windowed, widened
+    dev::launch_tiles(tpv, bv, plan, d_out, static_cast<int>(fmt), s);
+    ran.kernels |= pb.tp.tile16 ? 8 : 4;
+    ran.forms |= dev::tile_form(tpv);
   }
-  // records too long for a widened window on a Seq1 whose widened image exceeds the LDS — with the byte pairs
-  // whole (limits: L1 3000, records up to 2000 letters), as windows (L1 past ~3050), or an int16 profile:
-  // sliding widened windows (limits 12.9 -> 16.8 T cells/s, L1 20 000 with input3's records 17.3 -> 20.7,
-  // L1 150 000 9.6 -> 15.9; profiles/tile16_r5/README.txt)
-  if ((W == 0 || max_l2 + 2 * 128 * 4 > dev::tile16_max_window(true)) && !wide && d_prof16_ && !mfma_ &&
-      tile16_slide_ && parts == 1 &&
-      (tile_u_ <= 0 || tile_u_ == 2 || tile_u_ == 4 || tile_u_ == 8))
-    if (plan_slide(offsets, long_recs, n_long, prof16_i16_ ? 0.25 : 0.8, tp, starts)) return starts;
-  tp.window = W;
-  tp.wide = wide;
-  tp.tile16 = d_prof16_ != nullptr && (W == 0 || max_l2 + 2 * 128 <= W) && (wide || !prof16_i16_);
-  // sub-tiles per wave tile: 4 amortises the per-tile setup over short records, 2 keeps more waves busy
-  // on long ones (measured, both kernels: profiles/tile_variants.log, profiles/tile16_variants.log) — unless
-  // the batch gives every resident wave >= 8 tiles of 4 sub-tiles: with a record's last tile cut to its
-  // valid sub-tiles (tile16_search_kernel) 4 then wins on long records too (input3: 17.2 -> 17.7 T cells/s;
-  // 4 tiles per wave, heavy3's bench batch, stays on 2: 14.8 vs 14.3; profiles/r6/README.txt)
-  int u = tile_u_ > 0 ? tile_u_ : (sum_l2 < 96 * n_long ? 4 : 2);
-  if (tile_u_ <= 0 && u == 2 && W == 0 && tp.tile16) {
-    int64_t tiles4 = 0;
-    for (int64_t li = 0; li < n_long; ++li) {
-      const int64_t r = long_recs ? long_recs[li] : li;
-      tiles4 += dev::tiles_of(dev::lanes_needed(L1_, offsets[r + 1] - offsets[r]), dev::tile_span(true, 4));
-    }
-    const int64_t lds = dev::tile16_lds_bytes((wide ? 2 : 1) * static_cast<int64_t>(prof16_bytes_), L1_);
-    const int64_t resident = static_cast<int64_t>(num_cus_) * dev::tile16_waves_per_cu(static_cast<int>(lds));
-    if (tiles4 >= 8 * resident * parts) u = 4;
-  }
-  if (tile_u_ <= 0 && u == 4 && tp.tile16 && W == 0 && 128 * 8 <= prof16_overhang_) u = 8;  // tile16: wider tiles
-  if (u > 4 && !(tp.tile16 && W == 0 && 128 * u <= prof16_overhang_)) u = 4;  // the overhang bounds the span
-  if (u > 2 && mfma_ && tp.tile16 && W == 0) u = 2;  // the matrix-core sweep's register budget (U = 4 spills)
-  if (tp.tile16 && W > 0) {
-    // windowed: the widest tiles a window holds twice (L1 = 20 000, input3 records: U = 4 -> 9.3 T cells/s,
-    // U = 2 -> 8.4, U = 1 -> 7.0; profiles/kernel_bench_long.log)
-    if (tile_u_ <= 0) u = 4;
-    while (u > 1 && max_l2 + 2 * 128 * u > W) u /= 2;
-    // widened windows (short records): 8 sub-tiles when one tile and the longest record fit the window
-    if (wide && tile_u_ <= 0 && short_window_u8_ && max_l2 + 128 * 8 <= W) u = 8;
-  }
-  tp.u = u;
-  const int span = dev::tile_span(tp.tile16, u);
-  std::vector<int64_t> tcost(static_cast<size_t>(n_long));
-  std::vector<int32_t> ntiles(static_cast<size_t>(n_long));
-  int64_t total_tiles = 0;
-  for (int64_t li = 0; li < n_long; ++li) {
-    const int64_t r = long_recs ? long_recs[li] : li;
-    const int64_t L2 = offsets[r + 1] - offsets[r];
-    ntiles[li] = static_cast<int32_t>(dev::tiles_of(dev::lanes_needed(L1_, L2), span));
-    tcost[li] = (L2 <= L1_ ? L2 : 0) + kTileOverheadSteps;
-    total_tiles += ntiles[li];
-  }
-  const int s1_len = tp.tile16 && W > 0 ? static_cast<int>(W) : static_cast<int>(L1_);
-  const int64_t prof_lds = (wide ? 2 : 1) * (W ? dev::tile16_window_bytes(W) : static_cast<int64_t>(prof16_bytes_));
-  const int waves_per_cu = tp.tile16 ? dev::tile16_waves_per_cu(static_cast<int>(dev::tile16_lds_bytes(prof_lds, s1_len)))
-                                     : tile_waves_per_cu_;
-  if (!(tp.tile16 && W > 0))
-    return balanced_runs(ntiles, tcost, total_tiles, part, parts, static_cast<int64_t>(num_cus_) * waves_per_cu);
-  // ---- windowed tile16: window-major runs, whole workgroups per window
-  // (a widened window, chosen for short records only, packs one more tile: its columns
-  // [0, T * span + max L2) still lie inside the window)
-  const int64_t T = std::max<int64_t>(1, (W - (wide ? 0 : span) - max_l2) / span);
-  tp.win_tiles = static_cast<int32_t>(T);
-  int32_t max_nt = 0;
-  for (int64_t li = 0; li < n_long; ++li) max_nt = std::max(max_nt, ntiles[li]);
-  const int64_t M = (max_nt + T - 1) / T;
-  auto count = [&](int64_t li, int64_t m) { return std::clamp<int64_t>(ntiles[li] - m * T, 0, T); };
-  std::vector<int64_t> wcost(static_cast<size_t>(M), 0);
-  for (int64_t li = 0; li < n_long; ++li)
-    for (int64_t m = 0; m * T < ntiles[li]; ++m) wcost[m] += count(li, m) * tcost[li];
-  std::vector<int64_t> wstart(static_cast<size_t>(M) + 1, 0);
-  for (int64_t m = 0; m < M; ++m) wstart[m + 1] = wstart[m] + wcost[m];
-  const int64_t C = wstart[M];
-  const int64_t lo = C * part / parts, hi = C * (part + 1) / parts;
-  constexpr int kWg = 16;  // waves per tile16 workgroup
-  const int64_t target_wgs = std::max<int64_t>(1, static_cast<int64_t>(num_cus_) * waves_per_cu / kWg);
-  // workgroups per window in proportion to its cost, largest remainders first, so that they add up to
-  // target_wgs: one workgroup over the resident count waits for a second round (ceil per window put input4's
-  // 3 windows at 3 x 86 = 258 on 256 CUs: 2.4 ms instead of 1.3)
-  std::vector<int64_t> wgs_of(static_cast<size_t>(M), 0);
-  {
-    std::vector<std::pair<double, int64_t>> frac;
-    int64_t used = 0;
-    for (int64_t m = 0; m < M; ++m) {
-      const int64_t a = std::max(lo, wstart[m]) - wstart[m], b = std::min(hi, wstart[m + 1]) - wstart[m];
-      if (b <= a) continue;
-      const double ideal = static_cast<double>(target_wgs) * static_cast<double>(b - a) /
-                           static_cast<double>(std::max<int64_t>(hi - lo, 1));
-      const int64_t share_tiles = std::max<int64_t>(1, (b - a) / std::max<int64_t>(1, C / std::max<int64_t>(total_tiles, 1)));
-      const int64_t cap = std::max<int64_t>(1, (share_tiles + kWg - 2) / (kWg - 1));
-      wgs_of[m] = std::clamp<int64_t>(static_cast<int64_t>(ideal), 1, cap);
-      used += wgs_of[m];
-      if (wgs_of[m] < cap) frac.emplace_back(ideal - static_cast<double>(wgs_of[m]), m);
-    }
-    std::sort(frac.begin(), frac.end(), [](const auto& x, const auto& y) { return x.first > y.first; });
-    for (const auto& f : frac) {
-      if (used >= target_wgs) break;
-      ++wgs_of[f.second];
-      ++used;
-    }
-  }
-  std::vector<int64_t> pre(static_cast<size_t>(n_long) + 1);
-  for (int64_t m = 0; m < M; ++m) {
-    const int64_t a = std::max(lo, wstart[m]) - wstart[m], b = std::min(hi, wstart[m + 1]) - wstart[m];
-    if (b <= a) continue;
-    pre[0] = 0;
-    for (int64_t li = 0; li < n_long; ++li) pre[li + 1] = pre[li] + count(li, m) * tcost[li];
-    const dev::WaveStart end_marker{static_cast<int32_t>(n_long), static_cast<int32_t>(m * T)};
-    auto locate = [&](int64_t X) {
-      if (X >= pre[n_long]) return end_marker;
-      const int64_t li = std::upper_bound(pre.begin(), pre.end(), X) - pre.begin() - 1;
-      const int64_t t = (X - pre[li] + tcost[li] - 1) / tcost[li];
-      if (t >= count(li, m)) return dev::WaveStart{static_cast<int32_t>(li + 1), static_cast<int32_t>(m * T)};
-      return dev::WaveStart{static_cast<int32_t>(li), static_cast<int32_t>(m * T + t)};
-    };
-    const int64_t wgs = wgs_of[m];
-    const int64_t real = wgs * kWg - 1;  // + one empty marker wave that ends the window's list
-    for (int64_t q = 0; q < real; ++q) starts.push_back(locate(a + (b - a) * q / real));
-    starts.push_back(locate(b));  // the last real wave ends at the share's end ...
-    starts.back() = b >= pre[n_long] ? end_marker : starts.back();
-    // ... and the marker wave [end, next window's first start) is empty: its start is the end of this window
-  }
-  if (starts.empty()) return starts;
-  // every window contributed wgs*16 entries: the real waves' starts + its end; the final entry ends the list
-  starts.push_back(starts.back());
-  return starts;
+  MOC_HIP_CHECK(hipGetLastError());
+  return ran;
 }
 
 namespace {
@@ -883,7 +563,7 @@ void HipEngine::solve_ex(const uint8_t* codes, const int64_t* offsets, const uin
 bool HipEngine::streams_packed(int64_t min_l2, int64_t max_l2) const {
   dev::ShortArgs a;
   a.packed33 = 1;  // the widest LDS layout of the letter forms
-  return have_problem_ && dev::configure_swipe(L1_, min_l2, max_l2, table_.max_abs(), a);
+  return have_problem_ && dev::configure_swipe(cfg_.L1, min_l2, max_l2, table_.max_abs(), a);
 }
 
 void HipEngine::solve_wire(const WireBatch& batch, void* out, ResultFormat fmt) { solve_wire_impl(batch, out, fmt, false); }
@@ -939,11 +619,11 @@ void HipEngine::solve_wire_impl(const WireBatch& batch, void* out, ResultFormat 
     throw Error("3-bit lengths cannot hold this batch's lengths");
   if (b.len_bits == kLenBase6 && b.lengths && (ls.mn < b.len_base || ls.mx > b.len_base + 5))
     throw Error("base-6 lengths cannot hold this batch's lengths");
-  if (fmt == ResultFormat::R4 && (L1_ > 255 || ls.mx > 255 || table_.max_abs() * ls.mx >= 32767))
+  if (fmt == ResultFormat::R4 && (cfg_.L1 > 255 || ls.mx > 255 || table_.max_abs() * ls.mx >= 32767))
     throw Error("result format R4 cannot hold this batch");
-  if (fmt == ResultFormat::R8 && (L1_ > 65535 || ls.mx > 65535)) throw Error("result format R8 cannot hold this batch");
+  if (fmt == ResultFormat::R8 && (cfg_.L1 > 65535 || ls.mx > 65535)) throw Error("result format R8 cannot hold this batch");
   r2_ = R2Params{};
-  if (fmt == ResultFormat::R2 && !r2_params(L1_, ls.mn, ls.mx, min_t_, max_t_, r2_))
+  if (fmt == ResultFormat::R2 && !r2_params(cfg_.L1, ls.mn, ls.mx, min_t_, max_t_, r2_))
     throw Error("result format R2 cannot hold this batch");
   stats_.r2 = r2_;
 
@@ -954,11 +634,11 @@ void HipEngine::solve_wire_impl(const WireBatch& batch, void* out, ResultFormat 
   a.counter = d_counter_;
   a.packed5 = b.packed5 ? 1 : 0;
   a.packed33 = b.packed33 ? 1 : 0;
-  const bool swipe = dev::configure_swipe(L1_, ls.mn, ls.mx, table_.max_abs(), a, b.device, sem_ == Semantics::Spec);
+  const bool swipe = dev::configure_swipe(cfg_.L1, ls.mn, ls.mx, table_.max_abs(), a, b.device, sem_ == Semantics::Spec);
   // packed letters stream straight into the swipe kernel only; other kernels read unpacked bytes. Sparse
   // offsets need whole tiles of 2^off_shift records (the swipe tiles are powers of two >= 64).
   const bool kernel_ok = (swipe || (!b.packed5 && !b.packed33 &&
-                                    dev::configure_short(L1_, ls.mn, ls.mx, a))) &&
+                                    dev::configure_short(cfg_.L1, ls.mn, ls.mx, a))) &&
                          (a.tile_records % (1 << b.off_shift)) == 0;
   if ((opt_.allow_direct || b.device) && kernel_ok && direct_pointers(b, out, fb, a)) {
     // device-resident: the wave-autonomous swipe kernel (byte letters with dense offsets, or P33 letters with
@@ -1039,9 +719,9 @@ bool HipEngine::prepare_direct(const dev::ProblemView& pv, const dev::ShortArgs&
   hipGraph_t g = nullptr;
   MOC_HIP_CHECK(hipStreamBeginCapture(s_compute_, hipStreamCaptureModeThreadLocal));
   if (swipe)
-    dev::launch_swipe(pv, a, num_cus_, s_compute_);
+    dev::launch_swipe(pv, a, cfg_.num_cus, s_compute_);
   else
-    dev::launch_short(pv, a, num_cus_, s_compute_);
+    dev::launch_short(pv, a, cfg_.num_cus, s_compute_);
   const hipError_t launch_err = hipGetLastError();
   MOC_HIP_CHECK(hipStreamEndCapture(s_compute_, &g));
   MOC_HIP_CHECK(launch_err);
@@ -1059,9 +739,9 @@ bool HipEngine::prepare_direct(const dev::ProblemView& pv, const dev::ShortArgs&
 void HipEngine::launch_direct(const dev::ProblemView& pv, const dev::ShortArgs& a, bool swipe, bool graph) {
   if (!graph) {
     if (swipe)
-      dev::launch_swipe(pv, a, num_cus_, s_compute_);
+      dev::launch_swipe(pv, a, cfg_.num_cus, s_compute_);
     else
-      dev::launch_short(pv, a, num_cus_, s_compute_);
+      dev::launch_short(pv, a, cfg_.num_cus, s_compute_);
     MOC_HIP_CHECK(hipGetLastError());
     return;
   }
@@ -1077,7 +757,7 @@ void HipEngine::run_staged(const uint8_t* codes, const int64_t* offsets, int64_t
   if (!one_chunk) ensure_side_streams();
   hipStream_t s_in = one_chunk ? s_compute_ : s_copy_, s_back = one_chunk ? s_compute_ : s_return_;
   const int fb = result_bytes(fmt);
-  ChunkPlan cp;
+  PlannedBatch pb;
   double kernel_ms = 0;
   auto retire = [&](Slot& s) {
     if (!s.busy) return;
@@ -1101,22 +781,8 @@ void HipEngine::run_staged(const uint8_t* codes, const int64_t* offsets, int64_t
     Slot& s = *slots_[chunk % 2];
     retire(s);
     TraceRange tr_chunk("moc.chunk");
-    plan_chunk(offsets + rb, cn, cp);
-    stats_.cells += cp.cells;
-    // records that the short kernel cannot hold (LDS budget) go to the tile kernel too
-    dev::ShortArgs a;
-    a.fmt = static_cast<int32_t>(fmt);
-    const bool swipe = cp.n_short > 0 && cp.long_recs.empty() &&
-                       dev::configure_swipe(L1_, cp.min_short, cp.max_l2, table_.max_abs(), a, true, sem_ == Semantics::Spec);
-    bool short_ok = swipe || (cp.n_short > 0 && dev::configure_short(L1_, cp.min_short, cp.max_l2, a));
-    // everything through the tile kernel (identity record list) when the short kernel cannot hold it
-    const bool all_tiles = cp.n_short > 0 && !short_ok;
-    const int32_t* lrecs = all_tiles ? nullptr : cp.long_recs.data();
-    const int64_t n_long = all_tiles ? cn : static_cast<int64_t>(cp.long_recs.size());
-    TilePlan tp;
-    const std::vector<dev::WaveStart> starts = plan_waves(offsets + rb, lrecs, n_long, 0, 1, tp);
-    const PlanLayout lay(starts.size(), lrecs ? static_cast<size_t>(n_long) : 0);
-    const size_t keys_extra = lrecs ? 0 : sizeof(unsigned long long) * static_cast<size_t>(n_long);
+    plan_batch(offsets + rb, cn, fmt, pb);
+    stats_.cells += pb.cp.cells;
     const size_t cbytes = static_cast<size_t>(offsets[re] - offsets[rb]);
     ensure(s.d_codes, s.d_codes_cap, std::max<size_t>(cbytes, 16) + 32);
     // packed chunk: bytes [pb0, pb1) of the 5-bit stream, char offsets[rb] at bit pbit within it
@@ -1125,13 +791,6 @@ void HipEngine::run_staged(const uint8_t* codes, const int64_t* offsets, int64_t
     if (packed5) ensure(s.d_packed, s.d_packed_cap, static_cast<size_t>(pb1 - pb0) + 16);
     ensure(s.d_offsets, s.d_offsets_cap, sizeof(int64_t) * static_cast<size_t>(cn + 1));
     ensure(s.d_out, s.d_out_cap, static_cast<size_t>(fb) * static_cast<size_t>(cn));
-    if (!starts.empty()) {
-      ensure(s.d_plan, s.d_plan_cap, lay.total + keys_extra);
-      ensure_host(s.h_plan, s.h_plan_cap, std::max<size_t>(lay.upload_bytes, 8));
-      std::memcpy(static_cast<char*>(s.h_plan) + lay.starts_off, starts.data(), starts.size() * sizeof(dev::WaveStart));
-      if (lrecs)
-        std::memcpy(static_cast<char*>(s.h_plan) + lay.long_off, lrecs, static_cast<size_t>(n_long) * sizeof(int32_t));
-    }
     // ---- copy stream: H2D
     size_t letter_bytes = cbytes;
     if (packed5) {
@@ -1142,45 +801,19 @@ void HipEngine::run_staged(const uint8_t* codes, const int64_t* offsets, int64_t
       copy_h2d(s.d_codes, codes + offsets[rb], cbytes, s_in);
     }
     copy_h2d(s.d_offsets, offsets + rb, sizeof(int64_t) * (cn + 1), s_in);
-    if (!starts.empty())
-      upload_staged(s.d_plan, s.h_plan, lay.upload_bytes, s_in);
+    upload_plan(pb, s.h_plan, s.h_plan_cap, s.d_plan, s.d_plan_cap, s_in);
     MOC_HIP_CHECK(hipEventRecord(s.ev_h2d, s_in));
-    stats_.h2d_bytes += static_cast<int64_t>(letter_bytes + sizeof(int64_t) * (cn + 1) + lay.upload_bytes);
+    stats_.h2d_bytes += static_cast<int64_t>(letter_bytes + sizeof(int64_t) * (cn + 1) + pb.lay.upload_bytes);
     // ---- compute stream
     MOC_HIP_CHECK(hipStreamWaitEvent(s_compute_, s.ev_h2d, 0));
     if (packed5)
       dev::launch_unpack5(static_cast<const uint8_t*>(s.d_packed), pbit, static_cast<int64_t>(cbytes),
                           static_cast<uint8_t*>(s.d_codes), s_compute_);
     MOC_HIP_CHECK(hipEventRecord(s.ev_k0, s_compute_));
-    const dev::ProblemView pv = problem_view(cp.max_l2);
-    const uint8_t* dcodes = static_cast<const uint8_t*>(s.d_codes);
-    const int64_t* doffs = static_cast<const int64_t*>(s.d_offsets);
-    if (short_ok) {
-      a.codes = dcodes - offsets[rb];  // base: record i at base + offsets[i] (absolute offsets)
-      a.offsets = doffs;
-      a.lengths8 = nullptr;
-      a.lengths4 = nullptr;
-      a.lengths3 = nullptr;
-      a.n = cn;
-      a.out = s.d_out;
-      a.counter = s.d_counter;
-      a.lane_direct = swipe && lane_direct_enabled() ? 1 : 0;
-      if (swipe)
-        dev::launch_swipe(pv, a, num_cus_, s_compute_);
-      else
-        dev::launch_short(pv, a, num_cus_, s_compute_);
-      stats_.kernels |= swipe ? 1 : 2;
-      stats_.forms |= swipe ? dev::swipe_launch_form(a) : dev::short_form(pv, a);
-    }
-    if (!starts.empty()) {
-      dev::Plan plan = device_plan(s.d_plan, starts.size(), lrecs != nullptr, n_long, tp);
-      dev::BatchView bv{dcodes, doffs, cn};
-      const dev::ProblemView tpv = tile_view(cp.max_l2, tp);  // the plan's image: whole / windowed, widened
-      dev::launch_tiles(tpv, bv, plan, s.d_out, static_cast<int>(fmt), s_compute_);
-      stats_.kernels |= tp.tile16 ? 8 : 4;
-      stats_.forms |= dev::tile_form(tpv);
-    }
-    MOC_HIP_CHECK(hipGetLastError());
+    const dev::BatchView bv{static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), cn};
+    const Ran ran = launch_planned(pb, bv, offsets[rb], s.d_out, s.d_counter, s.d_plan, fmt, s_compute_);
+    stats_.kernels |= ran.kernels;
+    stats_.forms |= ran.forms;
     MOC_HIP_CHECK(hipEventRecord(s.ev_k1, s_compute_));
     // ---- return stream: D2H straight into the caller's result array
     MOC_HIP_CHECK(hipStreamWaitEvent(s_back, s.ev_k1, 0));
@@ -1193,6 +826,12 @@ void HipEngine::run_staged(const uint8_t* codes, const int64_t* offsets, int64_t
   for (auto& s : slots_) retire(*s);
   stats_.kernel_ms = kernel_ms;
   stats_.chunks = chunk;
+}
+
+void HipEngine::ensure_device_events() {
+  if (ev_d0_) return;
+  MOC_HIP_CHECK(hipEventCreate(&ev_d0_));
+  MOC_HIP_CHECK(hipEventCreate(&ev_d1_));
 }
 
 double HipEngine::device_kernel_ms() {
@@ -1211,66 +850,22 @@ void HipEngine::solve_device(const uint8_t* d_codes, const int64_t* d_offsets, c
   if (n <= 0) return;
   if (!stream) stream = s_compute_;
   TraceRange tr("moc.solve_device");
-  ChunkPlan cp;
-  plan_chunk(h_offsets, n, cp);
-  dev::ShortArgs a;
-  a.fmt = static_cast<int32_t>(ResultFormat::R12);
-  const bool swipe = cp.n_short > 0 && cp.long_recs.empty() &&
-                     dev::configure_swipe(L1_, cp.min_short, cp.max_l2, table_.max_abs(), a, true, sem_ == Semantics::Spec);
-  bool short_ok = swipe || (cp.n_short > 0 && dev::configure_short(L1_, cp.min_short, cp.max_l2, a));
-  const bool all_tiles = cp.n_short > 0 && !short_ok;  // everything through the tile kernel
-  const int32_t* lrecs = all_tiles ? nullptr : cp.long_recs.data();
-  const int64_t n_long = all_tiles ? n : static_cast<int64_t>(cp.long_recs.size());
-  TilePlan tp;
-  const std::vector<dev::WaveStart> starts = plan_waves(h_offsets, lrecs, n_long, 0, 1, tp);
-  const PlanLayout lay(starts.size(), lrecs ? static_cast<size_t>(n_long) : 0);
-  const size_t keys_extra = lrecs ? 0 : sizeof(unsigned long long) * static_cast<size_t>(n_long);
+  PlannedBatch pb;
+  plan_batch(h_offsets, n, ResultFormat::R12, pb);
   MOC_HIP_CHECK(hipEventSynchronize(ev_plan_));  // previous call's plan buffers are free again
-  if (!starts.empty()) {
-    ensure(d_plan_, d_plan_cap_, lay.total + keys_extra);
-    ensure_host(h_plan_, h_plan_cap_, std::max<size_t>(lay.upload_bytes, 8));
-    std::memcpy(static_cast<char*>(h_plan_) + lay.starts_off, starts.data(), starts.size() * sizeof(dev::WaveStart));
-    if (lrecs)
-      std::memcpy(static_cast<char*>(h_plan_) + lay.long_off, lrecs, static_cast<size_t>(n_long) * sizeof(int32_t));
-    upload_staged(d_plan_, h_plan_, lay.upload_bytes, stream);
-  }
-  const dev::ProblemView pv = problem_view(cp.max_l2);
-  if (!ev_d0_) {
-    MOC_HIP_CHECK(hipEventCreate(&ev_d0_));
-    MOC_HIP_CHECK(hipEventCreate(&ev_d1_));
-  }
+  upload_plan(pb, h_plan_, h_plan_cap_, d_plan_, d_plan_cap_, stream);
+  ensure_device_events();
   MOC_HIP_CHECK(hipEventRecord(ev_d0_, stream));
-  if (short_ok) {
-    a.codes = d_codes;
-    a.offsets = d_offsets;
-    a.n = n;
-    a.out = d_out;
-    a.counter = d_counter_;
-    a.lane_direct = swipe && lane_direct_enabled() ? 1 : 0;
-    if (swipe)
-      dev::launch_swipe(pv, a, num_cus_, stream);
-    else
-      dev::launch_short(pv, a, num_cus_, stream);
-  }
-  if (!starts.empty()) {
-    dev::Plan plan = device_plan(d_plan_, starts.size(), lrecs != nullptr, n_long, tp);
-    dev::BatchView bv{d_codes + h_offsets[0], d_offsets, n};
-    dev::launch_tiles(tile_view(cp.max_l2, tp), bv, plan, d_out, static_cast<int>(ResultFormat::R12), stream);
-  }
-  MOC_HIP_CHECK(hipGetLastError());
+  const dev::BatchView bv{d_codes + h_offsets[0], d_offsets, n};
+  const Ran ran = launch_planned(pb, bv, h_offsets[0], d_out, d_counter_, d_plan_, ResultFormat::R12, stream);
   MOC_HIP_CHECK(hipEventRecord(ev_d1_, stream));
   MOC_HIP_CHECK(hipEventRecord(ev_plan_, stream));
   stats_ = EngineStats{};
-  stats_.cells = cp.cells;
+  stats_.cells = pb.cp.cells;
   stats_.records = n;
-  stats_.kernels = (short_ok ? (swipe ? 1 : 2) : 0) | (starts.empty() ? 0 : (tp.tile16 ? 8 : 4));
-  stats_.forms = (short_ok ? (swipe ? dev::swipe_launch_form(a) : dev::short_form(pv, a)) : 0) |
-                 (starts.empty() ? 0 : dev::tile_form(tile_view(cp.max_l2, tp)));
+  stats_.kernels = ran.kernels;
+  stats_.forms = ran.forms;
 }
-
-}  // namespace moc
-
-namespace moc {
 
 void HipEngine::search_keys_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
                                    int64_t n, int part, int parts, unsigned long long* d_keys, hipStream_t stream) {
@@ -1285,8 +880,8 @@ void HipEngine::search_keys_device(const uint8_t* d_codes, const int64_t* d_offs
   for (int64_t i = 0; i < n; ++i) max_l2 = std::max(max_l2, h_offsets[i + 1] - h_offsets[i]);
   if (max_l2 >= (int64_t{1} << 30)) throw Error("Seq2 lengths beyond 2^30 exceed the device engine's offset range");
   // the record-major tile list of all records; this part takes a contiguous, cost-balanced share of it
-  TilePlan tp;
-  const std::vector<dev::WaveStart> starts = plan_waves(h_offsets, nullptr, n, part, parts, tp);
+  plan::TilePlan tp;
+  const std::vector<dev::WaveStart> starts = plan::plan_waves(cfg_, h_offsets, nullptr, n, part, parts, tp);
   MOC_HIP_CHECK(hipEventSynchronize(ev_plan_));  // previous call's plan buffers are free again
   const size_t bytes = std::max<size_t>(starts.size() * sizeof(dev::WaveStart), 8);
   ensure(d_plan_, d_plan_cap_, bytes);
@@ -1295,18 +890,7 @@ void HipEngine::search_keys_device(const uint8_t* d_codes, const int64_t* d_offs
     std::memcpy(h_plan_, starts.data(), starts.size() * sizeof(dev::WaveStart));
     upload_staged(d_plan_, h_plan_, starts.size() * sizeof(dev::WaveStart), stream);
   }
-  dev::Plan plan;
-  plan.u = tp.u;
-  plan.win_tiles = tp.win_tiles;
-  plan.n_waves = starts.empty() ? 0
-                 : tp.slide   ? tp.slide_wgs * dev::kTile16WavesPerBlock
-                              : static_cast<int64_t>(starts.size()) - 1;
-  plan.slide_items = tp.slide_items;
-  plan.slide_members = tp.slide_members;
-  plan.starts = static_cast<const dev::WaveStart*>(d_plan_);
-  plan.long_recs = nullptr;
-  plan.n_long = n;
-  plan.keys = d_keys;
+  const dev::Plan plan = device_plan(d_plan_, starts.size(), false, n, tp, d_keys);
   dev::BatchView bv{d_codes + h_offsets[0], d_offsets, n};
   dev::launch_tile_keys(tile_view(max_l2, tp), bv, plan, stream);
   MOC_HIP_CHECK(hipGetLastError());
@@ -1336,6 +920,31 @@ void HipEngine::finalize_keys_device(const uint8_t* d_codes, const int64_t* d_of
   MOC_HIP_CHECK(hipGetLastError());
 }
 
+// Host batch -> slot 0's pooled device buffers on the compute stream, its d_out grown to out_bytes. Returns the
+// offsets rebased to 0, as uploaded: the device base pointer is the buffer itself (record i at d_codes +
+// rebased[i]).
+std::vector<int64_t> HipEngine::upload_batch(const uint8_t* codes, const int64_t* offsets, int64_t n, size_t out_bytes) {
+  Slot& s = *slots_[0];
+  std::vector<int64_t> rebased(static_cast<size_t>(n) + 1);
+  for (int64_t i = 0; i <= n; ++i) rebased[i] = offsets[i] - offsets[0];
+  const size_t cbytes = static_cast<size_t>(rebased[n]);
+  ensure(s.d_codes, s.d_codes_cap, std::max<size_t>(cbytes, 16) + 32);
+  ensure(s.d_offsets, s.d_offsets_cap, sizeof(int64_t) * static_cast<size_t>(n + 1));
+  ensure(s.d_out, s.d_out_cap, out_bytes);
+  if (cbytes) copy_h2d(s.d_codes, codes + offsets[0], cbytes, s_compute_);
+  MOC_HIP_CHECK(hipMemcpyAsync(s.d_offsets, rebased.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s_compute_));
+  return rebased;
+}
+
+// Stats of a synchronous call over a batch uploaded by upload_batch (`letters` letter bytes), once it is complete.
+void HipEngine::host_call_stats(Stopwatch& wall, double kernel_ms, int64_t letters, int64_t n, size_t d2h_bytes) {
+  stats_.kernel_ms = kernel_ms;
+  stats_.h2d_bytes = letters + static_cast<int64_t>(sizeof(int64_t)) * (n + 1);
+  stats_.d2h_bytes = static_cast<int64_t>(d2h_bytes);
+  wall.stop();
+  stats_.total_ms = wall.total_ms();
+}
+
 void HipEngine::search_keys(const uint8_t* codes, const int64_t* offsets, int64_t n, int part, int parts,
                             uint64_t* keys) {
   finish_wire();
@@ -1344,17 +953,7 @@ void HipEngine::search_keys(const uint8_t* codes, const int64_t* offsets, int64_
   Stopwatch wall;
   wall.start();
   Slot& s = *slots_[0];
-  const size_t cbytes = static_cast<size_t>(offsets[n] - offsets[0]);
-  ensure(s.d_codes, s.d_codes_cap, std::max<size_t>(cbytes, 16) + 32);
-  ensure(s.d_offsets, s.d_offsets_cap, sizeof(int64_t) * static_cast<size_t>(n + 1));
-  ensure(s.d_out, s.d_out_cap, sizeof(uint64_t) * static_cast<size_t>(n));
-  // offsets rebased to 0, so the device base pointer is the buffer itself (record i at d_codes + rebased[i])
-  std::vector<int64_t> rebased(static_cast<size_t>(n) + 1);
-  for (int64_t i = 0; i <= n; ++i) rebased[i] = offsets[i] - offsets[0];
-  if (cbytes)
-    copy_h2d(s.d_codes, codes + offsets[0], cbytes, s_compute_);
-  MOC_HIP_CHECK(hipMemcpyAsync(s.d_offsets, rebased.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice,
-                               s_compute_));
+  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, sizeof(uint64_t) * static_cast<size_t>(n));
   MOC_HIP_CHECK(hipEventRecord(ev_a_, s_compute_));
   search_keys_device(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(),
                      n, part, parts, static_cast<unsigned long long*>(s.d_out), s_compute_);
@@ -1363,11 +962,7 @@ void HipEngine::search_keys(const uint8_t* codes, const int64_t* offsets, int64_
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
   float ms = 0;
   MOC_HIP_CHECK(hipEventElapsedTime(&ms, ev_a_, ev_b_));
-  stats_.kernel_ms = ms;
-  stats_.h2d_bytes = static_cast<int64_t>(cbytes + sizeof(int64_t) * (n + 1));
-  stats_.d2h_bytes = static_cast<int64_t>(sizeof(uint64_t) * n);
-  wall.stop();
-  stats_.total_ms = wall.total_ms();
+  host_call_stats(wall, ms, rebased[n], n, sizeof(uint64_t) * n);
 }
 
 // ---- per-offset score profile and top-K alignments ------------------------------------------------------
@@ -1379,7 +974,7 @@ void HipEngine::set_profile_scratch(int64_t bytes) {
 void HipEngine::profile_offsets(const int64_t* offsets, int64_t n, int64_t* poffsets) const {
   if (!have_problem_) throw Error("HipEngine::profile_offsets before set_problem");
   poffsets[0] = 0;
-  for (int64_t i = 0; i < n; ++i) poffsets[i + 1] = poffsets[i] + candidate_offsets(L1_, offsets[i + 1] - offsets[i], sem_);
+  for (int64_t i = 0; i < n; ++i) poffsets[i + 1] = poffsets[i] + candidate_offsets(cfg_.L1, offsets[i + 1] - offsets[i], sem_);
 }
 
 double HipEngine::topk_select_ms() {
@@ -1413,18 +1008,13 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
     const int64_t L2 = h_offsets[i + 1] - h_offsets[i];
     sum_l2 += L2;
     max_l2 = std::max(max_l2, L2);
-    max_need = std::max(max_need, dev::lanes_needed(L1_, L2));
-    cells += record_cells(L1_, L2);
+    max_need = std::max(max_need, dev::lanes_needed(cfg_.L1, L2));
+    cells += record_cells(cfg_.L1, L2);
   }
-  if (L1_ >= (int64_t{1} << 30) || max_l2 >= (int64_t{1} << 30))
+  if (cfg_.L1 >= (int64_t{1} << 30) || max_l2 >= (int64_t{1} << 30))
     throw Error("Seq1 / Seq2 lengths beyond 2^30 exceed the device engine's offset range");
-  // sub-tiles per wave tile, as the LUT tile kernel picks them: 4 amortises the per-tile set-up over short
-  // records, 2 keeps more waves busy on long ones; MOC_TILE_U = 1 | 2 | 4 overrides (8 is tile16's: 4 here)
-  // — and never more sub-tiles than the batch's widest offset range fills (short records: one sub-tile)
-  int u = tile_u_ > 0 ? std::min(tile_u_, 4) : (sum_l2 < 96 * n ? 4 : 2);
-  if (tile_u_ <= 0)
-    while (u > 1 && max_need <= dev::kTileOffsets * (u / 2)) u /= 2;
-  const int span = dev::tile_span(false, u);
+  // sub-tiles per wave tile, as the LUT tile kernel picks them, narrowed to the batch's widest offset range
+  const int u = plan::profile_u(cfg_, sum_l2, n, max_need);
   // chunks of consecutive records: the whole batch for a profile, bounded scratch for top-K
   struct Chunk {
     int64_t r0, r1;
@@ -1442,22 +1032,9 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
     r0 = r1;
   }
   std::vector<dev::WaveStart> starts;
-  std::vector<int32_t> ntiles;
-  std::vector<int64_t> tcost;
   int64_t max_entries = 0;
   for (Chunk& c : chunks) {
-    const int64_t m = c.r1 - c.r0;
-    ntiles.resize(static_cast<size_t>(m));
-    tcost.resize(static_cast<size_t>(m));
-    int64_t total_tiles = 0;
-    for (int64_t li = 0; li < m; ++li) {
-      const int64_t L2 = h_offsets[c.r0 + li + 1] - h_offsets[c.r0 + li];
-      ntiles[li] = static_cast<int32_t>(dev::tiles_of(dev::lanes_needed(L1_, L2), span));
-      tcost[li] = (L2 <= L1_ ? L2 : 0) + kTileOverheadSteps;
-      total_tiles += ntiles[li];
-    }
-    const std::vector<dev::WaveStart> runs =
-        balanced_runs(ntiles, tcost, total_tiles, 0, 1, static_cast<int64_t>(num_cus_) * tile_waves_per_cu_);
+    const std::vector<dev::WaveStart> runs = plan::profile_runs(cfg_, h_offsets + c.r0, c.r1 - c.r0, u);
     c.starts_at = starts.size();
     c.n_starts = runs.size();
     starts.insert(starts.end(), runs.begin(), runs.end());
@@ -1476,10 +1053,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   pv.prof16 = nullptr;  // the LUT sweep: exact int32 for any weights
   pv.mfma_sweep = 0;
   const dev::BatchView bv{d_codes + h_offsets[0], d_offsets, n};
-  if (!ev_d0_) {
-    MOC_HIP_CHECK(hipEventCreate(&ev_d0_));
-    MOC_HIP_CHECK(hipEventCreate(&ev_d1_));
-  }
+  ensure_device_events();
   if (K && profile_timing_)
     while (ev_select_.size() < 2 * chunks.size()) {
       hipEvent_t e = nullptr;
@@ -1525,15 +1099,6 @@ void HipEngine::solve_topk_device(const uint8_t* d_codes, const int64_t* d_offse
   run_profile(d_codes, d_offsets, h_offsets, n, K, d_out, stream);
 }
 
-namespace {
-// host batch -> pooled device buffers of a slot (offsets rebased to 0: the device base pointer is the buffer)
-std::vector<int64_t> rebase_offsets(const int64_t* offsets, int64_t n) {
-  std::vector<int64_t> rebased(static_cast<size_t>(n) + 1);
-  for (int64_t i = 0; i <= n; ++i) rebased[i] = offsets[i] - offsets[0];
-  return rebased;
-}
-}  // namespace
-
 void HipEngine::solve_profile(const uint8_t* codes, const int64_t* offsets, int64_t n, ProfileEntry* prof_out,
                               int64_t* poffsets_out) {
   finish_wire();
@@ -1543,23 +1108,13 @@ void HipEngine::solve_profile(const uint8_t* codes, const int64_t* offsets, int6
   Stopwatch wall;
   wall.start();
   Slot& s = *slots_[0];
-  const size_t cbytes = static_cast<size_t>(offsets[n] - offsets[0]);
   const size_t pbytes = sizeof(ProfileEntry) * static_cast<size_t>(poffsets_out[n]);
-  ensure(s.d_codes, s.d_codes_cap, std::max<size_t>(cbytes, 16) + 32);
-  ensure(s.d_offsets, s.d_offsets_cap, sizeof(int64_t) * static_cast<size_t>(n + 1));
-  ensure(s.d_out, s.d_out_cap, std::max<size_t>(pbytes, 8));
-  const std::vector<int64_t> rebased = rebase_offsets(offsets, n);
-  if (cbytes) copy_h2d(s.d_codes, codes + offsets[0], cbytes, s_compute_);
-  MOC_HIP_CHECK(hipMemcpyAsync(s.d_offsets, rebased.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s_compute_));
+  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, std::max<size_t>(pbytes, 8));
   run_profile(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(), n, 0,
               s.d_out, s_compute_);
   if (pbytes) copy_d2h(prof_out, s.d_out, pbytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  stats_.kernel_ms = device_kernel_ms();
-  stats_.h2d_bytes = static_cast<int64_t>(cbytes + sizeof(int64_t) * (n + 1));
-  stats_.d2h_bytes = static_cast<int64_t>(pbytes);
-  wall.stop();
-  stats_.total_ms = wall.total_ms();
+  host_call_stats(wall, device_kernel_ms(), rebased[n], n, pbytes);
 }
 
 void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, Result* out) {
@@ -1570,23 +1125,13 @@ void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t
   Stopwatch wall;
   wall.start();
   Slot& s = *slots_[0];
-  const size_t cbytes = static_cast<size_t>(offsets[n] - offsets[0]);
   const size_t obytes = sizeof(Result) * static_cast<size_t>(n) * static_cast<size_t>(K);
-  ensure(s.d_codes, s.d_codes_cap, std::max<size_t>(cbytes, 16) + 32);
-  ensure(s.d_offsets, s.d_offsets_cap, sizeof(int64_t) * static_cast<size_t>(n + 1));
-  ensure(s.d_out, s.d_out_cap, obytes);
-  const std::vector<int64_t> rebased = rebase_offsets(offsets, n);
-  if (cbytes) copy_h2d(s.d_codes, codes + offsets[0], cbytes, s_compute_);
-  MOC_HIP_CHECK(hipMemcpyAsync(s.d_offsets, rebased.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s_compute_));
+  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, obytes);
   run_profile(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(), n, K,
               s.d_out, s_compute_);
   copy_d2h(out, s.d_out, obytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  stats_.kernel_ms = device_kernel_ms();
-  stats_.h2d_bytes = static_cast<int64_t>(cbytes + sizeof(int64_t) * (n + 1));
-  stats_.d2h_bytes = static_cast<int64_t>(obytes);
-  wall.stop();
-  stats_.total_ms = wall.total_ms();
+  host_call_stats(wall, device_kernel_ms(), rebased[n], n, obytes);
 }
 
 }  // namespace moc

@@ -1,6 +1,7 @@
 // Native unit tests of the host core (SURVEY.md §4.3 "unit (C++)"): score table vs the spec groups,
 // parser and streaming reader edge cases, partitioner, packed-key ordering, 5-bit packing, CPU engine vs
 // the brute-force replay of the reference loops. No GPU, no MPI. Run: `make unit` or `ctest`.
+#include <omp.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -8,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <memory>
 #include <random>
 #include <string>
@@ -23,6 +25,7 @@
 #include "moc/runtime/releaser.hpp"
 #include "moc/runtime/watchdog.hpp"
 #include "moc/score_table.hpp"
+#include "moc/tile_plan.hpp"
 #include "moc/wire.hpp"
 #include "../apps/text_cut.hpp"
 
@@ -445,7 +448,7 @@ void test_profile16_lds_bytes() {
       for (bool i16 : {false, true}) {
         const int32_t b = dev::tile16_profile_lds_bytes(L1, oh, i16);
         CHECK(b > 0 && b <= dev::kProf16MaxLds && b % 16 == 0);
-        // the widened-image check of HipEngine::set_problem only passes where the doubled image fits
+        // the widened-image check of plan::set_profile_geometry only passes where the doubled image fits
         const bool wide = dev::tile16_lds_bytes(2 * static_cast<int64_t>(b), L1) <= dev::kProf16MaxLds;
         if (wide) CHECK(2 * (26 * L1 + oh) <= dev::kProf16MaxLds);
       }
@@ -1499,7 +1502,436 @@ void test_tile16_key32_replay() {
   }
 }
 
-int main() {
+// ---- tile planner (moc/tile_plan.hpp) -----------------------------------------------------------------
+// Every configuration comes from plan::set_profile_geometry over a profile built the way HipEngine::set_problem
+// builds it, so the plans below are plans the engine can really make.
+namespace {
+enum PlanProblem { kLut400, kWhole1489, kMfma1489, kWide2000, kWin20000, kSlide3000, kSlideI16, kHuge60000 };
+
+const plan::Config& plan_problem(PlanProblem p) {
+  static std::map<int, plan::Config> made;
+  if (made.count(p)) return made[p];
+  static const int64_t lengths[] = {400, 1489, 1489, 2000, 20000, 3000, 3000, 60000};
+  const int64_t L1 = lengths[p];
+  // |Dt| <= w0 + max(w1, w2, w3): 14 fits the byte pairs, 240 needs the int16 profile
+  const Weights w = p == kSlideI16 ? Weights{{200, 20, 30, 40}} : Weights{{10, 2, 3, 4}};
+  std::mt19937 rng(static_cast<unsigned>(L1));
+  std::vector<uint8_t> s1(static_cast<size_t>(L1));
+  for (auto& x : s1) x = static_cast<uint8_t>(1 + rng() % 26);
+  Profile16 prof;
+  const bool t16 = p != kLut400 && build_profile16(ScoreTable::build(w), s1.data(), L1, plan::profile16_overhang(L1),
+                                                  prof, /*allow_i16=*/true);
+  plan::Config c;
+  plan::set_profile_geometry(c, L1, t16 ? &prof : nullptr, /*wide_env=*/true);
+  c.mfma = p == kMfma1489;
+  return made[p] = c;
+}
+
+// n records of lo..hi letters; with `mix`, every 5th has L1 letters and every 7th L1 + 3 (no candidate offsets)
+std::vector<int64_t> plan_batch(unsigned seed, int64_t n, int64_t lo, int64_t hi, int64_t mix = 0) {
+  std::mt19937 rng(seed);
+  std::vector<int64_t> off(static_cast<size_t>(n) + 1);
+  off[0] = 11;  // a chunk of a bigger batch: plans read differences only
+  for (int64_t i = 0; i < n; ++i) {
+    int64_t L2 = lo + static_cast<int64_t>(rng() % static_cast<uint32_t>(hi - lo + 1));
+    if (mix && i % 5 == 4) L2 = mix;
+    if (mix && i % 7 == 6) L2 = mix + 3;
+    off[i + 1] = off[i] + L2;
+  }
+  return off;
+}
+
+using Tiles = std::vector<std::pair<int32_t, int32_t>>;  // (li, t)
+
+// The (li, t) tiles the kernels visit for a plan, read as their loops read it: tile_search_kernel
+// (align_kernels.hip), tile16_search_kernel and tile16_slide_kernel (tile16_kernels.hip), the MFMA sweep
+// (tile_mfma_kernels.hip) and offset_profile_kernel (profile_kernels.hip). The window a workgroup stages must
+// hold every tile it visits: checked on the way.
+Tiles walk_plan(const plan::Config& c, const int64_t* off, const int32_t* lrecs, int64_t n_long,
+                const plan::TilePlan& tp, const std::vector<dev::WaveStart>& s) {
+  Tiles out;
+  constexpr int G = dev::kTile16WavesPerBlock;
+  const int span = dev::tile_span(tp.tile16, tp.u);
+  auto length = [&](int64_t li) {
+    const int64_t r = lrecs ? lrecs[li] : li;
+    return off[r + 1] - off[r];
+  };
+  auto tiles = [&](int64_t L2) { return ((L2 <= c.L1 ? c.L1 - L2 + 1 : 1) + span - 1) / span; };
+  if (s.empty()) return out;
+  if (tp.slide) {
+    for (int64_t b = 0; b < tp.slide_wgs; ++b)
+      for (int32_t k = s[b].li; k < s[b + 1].li; ++k) {
+        const dev::WaveStart ia = s[tp.slide_items + 2 * k], ib = s[tp.slide_items + 2 * k + 1];
+        for (int wave = 0; wave < G; ++wave) {
+          const dev::WaveStart mem = s[tp.slide_members + G * static_cast<int64_t>(ia.li) + wave];
+          const int64_t L2 = mem.t;
+          const int64_t steps = mem.li >= 0 && L2 <= c.L1 ? L2 : 0;
+          const int64_t own_tiles = steps > 0 ? tiles(L2) : 0;
+          for (int32_t t = ia.t; t < ib.t; ++t)
+            if (t < own_tiles) out.emplace_back(mem.li, t);
+        }
+      }
+    return out;
+  }
+  const bool win = tp.tile16 && tp.window > 0;
+  const int64_t n_waves = static_cast<int64_t>(s.size()) - 1;
+  for (int64_t w = 0; w < n_waves; ++w) {
+    const int64_t t_base = win ? s[w / G * G].t / tp.win_tiles * tp.win_tiles : 0;
+    const int64_t t_win_end = win ? t_base + tp.win_tiles : INT32_MAX;
+    int64_t li = s[w].li, t = s[w].t;
+    const int64_t end_li = s[w + 1].li, end_t = s[w + 1].t;
+    while (li < end_li || (li == end_li && t < end_t)) {
+      CHECK(li >= 0 && li < n_long);  // the kernels read the record's offsets here
+      if (li < 0 || li >= n_long) break;
+      const int64_t L2 = length(li);
+      const int64_t ntiles = std::min(tiles(L2), t_win_end);
+      const int64_t t_stop = li == end_li ? std::min(end_t, ntiles) : ntiles;
+      for (; t < t_stop && (!tp.tile16 || L2 <= c.L1); ++t) {
+        out.emplace_back(static_cast<int32_t>(li), static_cast<int32_t>(t));
+        // windowed: the tile's profile columns [t * span, t * span + span + L2) lie in the staged window
+        if (win) CHECK(t >= t_base && (t - t_base + 1) * span + L2 <= tp.window);
+      }
+      ++li;
+      t = t_base;
+    }
+  }
+  return out;
+}
+
+// What a plan must cover: every tile of every record (the tile16 sweeps skip records longer than Seq1, whose
+// keys stay "no candidate"; the sliding one also skips empty records).
+Tiles plan_tiles(const plan::Config& c, const int64_t* off, const int32_t* lrecs, int64_t n_long, const plan::TilePlan& tp) {
+  Tiles all;
+  const int span = dev::tile_span(tp.tile16, tp.u);
+  for (int64_t li = 0; li < n_long; ++li) {
+    const int64_t L2 = plan::long_length(off, lrecs, li);
+    if ((tp.tile16 && L2 > c.L1) || (tp.slide && L2 < 1)) continue;
+    for (int64_t t = 0; t < dev::tiles_of(dev::lanes_needed(c.L1, L2), span); ++t)
+      all.emplace_back(static_cast<int32_t>(li), static_cast<int32_t>(t));
+  }
+  return all;
+}
+
+// LDS image of a plan's workgroups, as launch_tile16_keys sizes it
+int64_t plan_lds_bytes(const plan::Config& c, const plan::TilePlan& tp) {
+  const int64_t prof = tp.window ? dev::tile16_window_bytes(tp.window) : c.prof16_bytes;
+  return dev::tile16_lds_bytes((tp.wide ? 2 : 1) * prof, tp.window ? tp.window : c.L1);
+}
+
+void check_plan_shape(const plan::Config& c, const int64_t* off, const int32_t* lrecs, int64_t n_long,
+                      const plan::TilePlan& tp, const std::vector<dev::WaveStart>& s) {
+  constexpr int G = dev::kTile16WavesPerBlock;
+  if (s.empty()) return;
+  const int span = dev::tile_span(tp.tile16, tp.u);
+  auto before = [](dev::WaveStart a, dev::WaveStart b) { return a.li < b.li || (a.li == b.li && a.t <= b.t); };
+  if (tp.slide) {
+    const int64_t n_wg = tp.slide_wgs, n_groups = (n_long + G - 1) / G, n_items = s[n_wg].li;
+    CHECK(tp.tile16 && tp.wide && tp.win_tiles == 0);
+    CHECK(n_wg >= 1 && n_wg <= static_cast<int64_t>(c.num_cus) * tp.slide_per_cu);
+    CHECK(tp.slide_items == n_wg + 1 && tp.slide_members == tp.slide_items + 2 * n_items);
+    CHECK(static_cast<int64_t>(s.size()) == tp.slide_members + G * n_groups);
+    CHECK(s[0].li == 0);
+    for (int64_t b = 0; b < n_wg; ++b) CHECK(s[b].li <= s[b + 1].li);
+    std::vector<int> seen(static_cast<size_t>(n_long), 0);
+    for (size_t k = static_cast<size_t>(tp.slide_members); k < s.size(); ++k) {
+      if (s[k].li < 0) continue;
+      CHECK(s[k].li < n_long && s[k].t == plan::long_length(off, lrecs, s[k].li));
+      if (s[k].li < n_long) ++seen[s[k].li];
+    }
+    CHECK(std::count(seen.begin(), seen.end(), 1) == n_long);
+    for (int64_t k = 0; k < n_items; ++k) {
+      const dev::WaveStart ia = s[tp.slide_items + 2 * k], ib = s[tp.slide_items + 2 * k + 1];
+      CHECK(ia.li >= 0 && ia.li < n_groups && ia.t >= 0 && ia.t < ib.t);
+      for (int wave = 0; wave < G; ++wave) {
+        const dev::WaveStart mem = s[tp.slide_members + G * static_cast<int64_t>(ia.li) + wave];
+        CHECK(ib.li >= (mem.li >= 0 && mem.t <= c.L1 ? mem.t : 0));  // lmax covers every member's steps
+      }
+    }
+    CHECK(tp.window - span >= 64 && (tp.window - span) % 64 == 0);
+    CHECK(dev::tile16_lds_bytes(2 * dev::tile16_window_bytes(tp.window), tp.window) <= dev::kProf16MaxLds / tp.slide_per_cu);
+    return;
+  }
+  const int64_t n_waves = static_cast<int64_t>(s.size()) - 1;
+  const int wpc = tp.tile16 ? dev::tile16_waves_per_cu(static_cast<int>(plan_lds_bytes(c, tp))) : c.tile_waves_per_cu;
+  if (tp.tile16) CHECK(plan_lds_bytes(c, tp) <= dev::kProf16MaxLds);
+  if (!(tp.tile16 && tp.window > 0)) {
+    CHECK(n_waves >= 1 && n_waves <= static_cast<int64_t>(c.num_cus) * wpc);
+    for (int64_t w = 0; w < n_waves; ++w) CHECK(before(s[w], s[w + 1]));
+    return;
+  }
+  // window-major: the windows in order, each a run list of its own in whole workgroups
+  CHECK(tp.win_tiles >= 1 && n_waves % G == 0);
+  int64_t windows = 1;
+  for (int64_t w = 0; w < n_waves; ++w) {
+    const int64_t m0 = s[w].t / tp.win_tiles, m1 = s[w + 1].t / tp.win_tiles;
+    CHECK(m0 < m1 || (m0 == m1 && before(s[w], s[w + 1])));
+    if (m0 != m1) {
+      CHECK((w + 1) % G == 0);
+      ++windows;
+    }
+  }
+  // num_cus * wpc waves is the target, not a bound: every window of the share gets at least one workgroup,
+  // however few the device holds at once (one CU and the 30 windows of a 60 000-letter Seq1: 30 workgroups).
+  // Workgroups are handed out by floor(target * cost share), at least one each: at most target + windows.
+  CHECK(n_waves <= G * (std::max<int64_t>(1, static_cast<int64_t>(c.num_cus) * wpc / G) + windows));
+}
+
+uint64_t fnv1a(uint64_t h, int64_t v) {
+  for (int i = 0; i < 8; ++i) h = (h ^ (static_cast<uint64_t>(v) >> (8 * i) & 0xff)) * 1099511628211ull;
+  return h;
+}
+uint64_t runs_digest(uint64_t h, const std::vector<dev::WaveStart>& s) {
+  h = fnv1a(h, static_cast<int64_t>(s.size()));
+  for (const dev::WaveStart& x : s) h = fnv1a(fnv1a(h, x.li), x.t);
+  return h;
+}
+uint64_t plan_digest(const plan::ChunkPlan& cp, const plan::TilePlan& tp, const std::vector<dev::WaveStart>& s) {
+  uint64_t h = 14695981039346656037ull;
+  for (int64_t v : {cp.min_short, cp.max_l2, cp.n_short, cp.cells, static_cast<int64_t>(cp.long_recs.size())}) h = fnv1a(h, v);
+  for (int32_t r : cp.long_recs) h = fnv1a(h, r);
+  for (int64_t v : {int64_t{tp.u}, int64_t{tp.win_tiles}, int64_t{tp.tile16}, tp.window, int64_t{tp.wide}, int64_t{tp.slide},
+                    tp.slide_items, tp.slide_members, tp.slide_wgs, int64_t{tp.slide_per_cu}})
+    h = fnv1a(h, v);
+  return runs_digest(h, s);
+}
+
+// Plans one batch every way the engine does — the long records of plan_chunk at parts = 1, and the identity
+// list in 1..64 context-parallel parts — checks each plan's shape and that the parts' tiles are disjoint and
+// together every tile. Returns the parts = 1 identity plan's TilePlan.
+plan::TilePlan check_batch_plans(const plan::Config& c, const std::vector<int64_t>& off, plan::TilePlan* long_tp = nullptr) {
+  const int64_t n = static_cast<int64_t>(off.size()) - 1;
+  plan::ChunkPlan cp;
+  plan::plan_chunk(c, off.data(), n, cp);
+  std::vector<int32_t> want_long;
+  int64_t mn = INT64_MAX, mx = 0, ns = 0, cells = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t L2 = off[i + 1] - off[i];
+    mx = std::max(mx, L2);
+    cells += L2 <= c.L1 ? (c.L1 - L2 + 1) * L2 : 0;
+    if (dev::lanes_needed(c.L1, L2) > dev::kWave) {
+      want_long.push_back(static_cast<int32_t>(i));
+    } else {
+      mn = std::min(mn, L2);
+      ++ns;
+    }
+  }
+  CHECK(cp.long_recs == want_long && cp.min_short == mn && cp.max_l2 == mx && cp.n_short == ns && cp.cells == cells);
+  plan::TilePlan tp, first;
+  auto cover = [&](const int32_t* lrecs, int64_t n_long, int parts) {
+    Tiles seen;
+    plan::TilePlan part0;
+    for (int part = 0; part < parts; ++part) {
+      const std::vector<dev::WaveStart> s = plan::plan_waves(c, off.data(), lrecs, n_long, part, parts, tp);
+      if (part == 0) part0 = tp;
+      CHECK(tp.u == part0.u && tp.tile16 == part0.tile16 && tp.window == part0.window && tp.win_tiles == part0.win_tiles);
+      check_plan_shape(c, off.data(), lrecs, n_long, tp, s);
+      const Tiles t = walk_plan(c, off.data(), lrecs, n_long, tp, s);
+      seen.insert(seen.end(), t.begin(), t.end());
+    }
+    std::sort(seen.begin(), seen.end());  // a tile visited twice, or by two parts, stays twice
+    CHECK(seen == plan_tiles(c, off.data(), lrecs, n_long, part0));
+    return part0;
+  };
+  const plan::TilePlan lt = cover(cp.long_recs.data(), static_cast<int64_t>(cp.long_recs.size()), 1);
+  if (long_tp) *long_tp = lt;
+  for (int parts : {1, 2, 3, 7, 16, 64}) {
+    const plan::TilePlan p = cover(nullptr, n, parts);
+    if (parts == 1) first = p;
+    if (parts > 1) CHECK(!p.slide);  // the sliding plan is one device's
+  }
+  return first;
+}
+
+plan::Config with(plan::Config c, int num_cus, int tile_u = 0) {
+  c.num_cus = num_cus;
+  c.tile_u = tile_u;
+  return c;
+}
+}  // namespace
+
+void test_tile_plan_cases() {
+  for (int cus : {1, 8, 256}) {
+    // LUT tile kernel (no profile)
+    for (int64_t n : {1, 2, 17, 300})
+      for (int tu : {0, 1, 2, 4})
+        for (int64_t mix : {0, 400}) {
+          const plan::TilePlan tp = check_batch_plans(with(plan_problem(kLut400), cus, tu), plan_batch(1, n, 1, 300, mix));
+          CHECK(!tp.tile16 && !tp.slide && !tp.wide && tp.window == 0 && tp.win_tiles == 0);
+          CHECK(tu ? tp.u == tu : tp.u == 2 || tp.u == 4);
+          if (!tu && n == 300) CHECK(tp.u == 2);  // 150 letters a record on average: the long-record choice
+        }
+    // whole-image tile16 (widened: the doubled image of a 1489-letter Seq1 fits one CU), and the auto U
+    CHECK(plan_problem(kWhole1489).prof16_wide && plan_problem(kWhole1489).prof16_window == 0);
+    for (int64_t n : {40, 600})
+      for (int64_t mix : {0, 1489}) {
+        const plan::TilePlan tp = check_batch_plans(with(plan_problem(kWhole1489), cus), plan_batch(2, n, 5, 1400, mix));
+        CHECK(tp.tile16 && tp.wide && !tp.slide && tp.window == 0 && tp.win_tiles == 0);
+        if (n == 40 && cus == 256) CHECK(tp.u == 2);
+        if (n == 600 && cus <= 8) CHECK(tp.u == 4);  // >= 8 tiles of 4 sub-tiles for every resident wave
+        const plan::TilePlan mf = check_batch_plans(with(plan_problem(kMfma1489), cus), plan_batch(2, n, 5, 1400, mix));
+        CHECK(mf.tile16 && !mf.wide && !mf.slide && mf.window == 0 && mf.u == 2);
+      }
+    // short records on a Seq1 whose widened whole image does not fit: widened windows of 8 sub-tiles
+    {
+      CHECK(!plan_problem(kWide2000).prof16_wide && plan_problem(kWide2000).prof16_window == 0);
+      const plan::TilePlan tp = check_batch_plans(with(plan_problem(kWide2000), cus), plan_batch(3, 50, 1, 100));
+      CHECK(tp.tile16 && tp.wide && !tp.slide && tp.window == dev::tile16_max_window(true) && tp.win_tiles >= 1 && tp.u == 8);
+    }
+    // Seq1 past one LDS image: sliding windows on one device, byte-pair windows for a context-parallel share or
+    // with the sliding plan switched off
+    for (int64_t mix : {0, 20000}) {
+      CHECK(plan_problem(kWin20000).prof16_window == dev::tile16_max_window());
+      const std::vector<int64_t> off = plan_batch(4, 120, 100, 2000, mix);
+      const plan::TilePlan tp = check_batch_plans(with(plan_problem(kWin20000), cus), off);
+      CHECK(tp.slide);
+      plan::Config c = with(plan_problem(kWin20000), cus);
+      plan::TilePlan cp_tp;
+      plan::plan_waves(c, off.data(), nullptr, 120, 1, 3, cp_tp);
+      // (a record as long as Seq1 fits no window: the batch then takes the LUT tile kernel)
+      auto windowed = [&](const plan::TilePlan& t) {
+        return !t.slide && !t.wide && t.window == c.prof16_window &&
+               (mix ? !t.tile16 && t.win_tiles == 0 : t.tile16 && t.win_tiles >= 1 && t.u == 4);
+      };
+      CHECK(windowed(cp_tp));
+      c.tile16_slide = false;
+      CHECK(windowed(check_batch_plans(c, off)));
+    }
+    // sliding windows: whole byte-pair image, records too long for a widened window
+    for (PlanProblem p : {kSlide3000, kSlideI16})
+      for (int64_t n : {16, 17, 100})
+        for (int64_t mix : {0, 3000}) {
+          const plan::Config c = with(plan_problem(p), cus);
+          CHECK(c.has_prof16 && c.prof16_i16 == (p == kSlideI16) && !c.prof16_wide && c.prof16_window == 0);
+          plan::TilePlan lt;
+          const plan::TilePlan tp = check_batch_plans(c, plan_batch(5, n, 600, 2000, mix), &lt);
+          // byte pairs ask for groups 80 % full: 17 records (two groups) stay on the whole byte-pair image
+          const bool slides = p == kSlideI16 || n != 17;
+          CHECK(tp.slide == slides && tp.tile16 && tp.wide == slides && tp.u == (slides ? 4 : 2));
+          if (!mix) CHECK(lt.slide == slides);
+          if (slides) CHECK(tp.slide_per_cu == 2 && tp.window > 0 && tp.win_tiles == 0);
+        }
+    // one lone record on an int16 profile does not slide (a group 1/16 full): the LUT tile kernel takes it
+    {
+      const plan::TilePlan tp = check_batch_plans(with(plan_problem(kSlideI16), cus), plan_batch(6, 1, 1500, 1500));
+      CHECK(!tp.slide && !tp.tile16 && tp.u == 2);
+    }
+    // a single huge record split over up to 64 parts
+    {
+      const plan::Config c = with(plan_problem(kHuge60000), cus);
+      const plan::TilePlan tp = check_batch_plans(c, plan_batch(7, 1, 10, 10));
+      CHECK(tp.tile16 && !tp.slide && !tp.wide && tp.window == c.prof16_window && tp.u == 4);
+    }
+  }
+}
+
+void test_plan_chunk_threaded() {
+  const plan::Config& c = plan_problem(kLut400);
+  const std::vector<int64_t> off = plan_batch(8, 70000, 1, 420);  // > 65 536 records: one part per thread
+  const int threads = omp_get_max_threads();
+  plan::ChunkPlan serial, threaded;
+  omp_set_num_threads(1);
+  plan::plan_chunk(c, off.data(), 70000, serial);
+  omp_set_num_threads(std::max(threads, 4));
+  plan::plan_chunk(c, off.data(), 70000, threaded);
+  omp_set_num_threads(threads);
+  CHECK(std::is_sorted(serial.long_recs.begin(), serial.long_recs.end()));
+  CHECK(serial.long_recs == threaded.long_recs && serial.min_short == threaded.min_short && serial.max_l2 == threaded.max_l2 &&
+        serial.n_short == threaded.n_short && serial.cells == threaded.cells);
+  CHECK(serial.n_short > 0 && serial.n_short + static_cast<int64_t>(serial.long_recs.size()) == 70000);
+}
+
+void test_plan_layout() {
+  for (size_t n_starts : {size_t{2}, size_t{3}, size_t{8193}})
+    for (size_t n_long : {size_t{0}, size_t{1}, size_t{2}, size_t{301}}) {
+      const plan::PlanLayout lay(n_starts, n_long);
+      CHECK(lay.starts_off == 0 && lay.long_off == n_starts * sizeof(dev::WaveStart));
+      CHECK(lay.upload_bytes == lay.long_off + n_long * sizeof(int32_t));
+      CHECK(lay.keys_off % 8 == 0 && lay.keys_off >= lay.upload_bytes && lay.keys_off < lay.upload_bytes + 8);
+      CHECK(lay.total == lay.keys_off + n_long * sizeof(unsigned long long));
+      if (n_long == 0) CHECK(lay.keys_off == lay.long_off);  // identity list: the keys right after the starts
+    }
+}
+
+// The refactor that moved the planner out of HipEngine must not change a plan: digests (FNV-1a over the
+// ChunkPlan scalars and long_recs, every TilePlan field and the starts) recorded from commit ccaca0d's
+// HipEngine::plan_chunk / plan_waves / set_problem geometry / run_profile, compiled verbatim in a scratch
+// harness against a hand-filled copy of the engine's fields and fed these same inputs.
+void test_tile_plan_digests() {
+  struct Case {
+    PlanProblem p;
+    unsigned seed;
+    int64_t n, lo, hi, mix;
+    int cus, tile_u, part, parts;
+    bool identity;
+    uint64_t want;
+  };
+  const Case cases[] = {
+      {kLut400, 1, 300, 1, 300, 0, 256, 0, 0, 1, false, 0x0f65820cda314deeull},
+      {kLut400, 1, 300, 1, 300, 400, 8, 4, 2, 7, true, 0x2016dafd5b73c982ull},
+      {kLut400, 1, 17, 1, 300, 0, 1, 1, 0, 1, false, 0xb85d3a104a8b9765ull},
+      {kWhole1489, 2, 600, 5, 1400, 0, 8, 0, 0, 1, false, 0x7383eca64b903814ull},
+      {kWhole1489, 2, 40, 5, 1400, 1489, 256, 0, 1, 3, true, 0x18aab3ea5332148dull},
+      {kMfma1489, 2, 600, 5, 1400, 0, 256, 0, 0, 1, false, 0x8ab73025ccda3ba0ull},
+      {kWide2000, 3, 50, 1, 100, 0, 256, 0, 0, 1, false, 0x29e111c9d7191764ull},
+      {kWide2000, 3, 50, 1, 100, 0, 8, 0, 15, 16, true, 0x87c6153ea0bdfa36ull},
+      {kWin20000, 4, 120, 100, 2000, 0, 256, 0, 0, 1, false, 0x4e567ea89cf897e9ull},
+      {kWin20000, 4, 120, 100, 2000, 20000, 256, 0, 1, 2, true, 0xcf7022b79fef5601ull},
+      {kWin20000, 4, 120, 100, 2000, 0, 8, 0, 6, 7, true, 0x423ae063d0c38828ull},
+      {kSlide3000, 5, 100, 600, 2000, 0, 256, 0, 0, 1, false, 0xf1b10064fe539059ull},
+      {kSlide3000, 5, 17, 600, 2000, 3000, 8, 0, 0, 1, true, 0xaf654485e0175168ull},
+      {kSlideI16, 5, 100, 600, 2000, 0, 256, 0, 0, 1, false, 0xf1b10064fe539059ull},
+      {kSlideI16, 5, 17, 600, 2000, 0, 1, 2, 0, 1, true, 0xc9375311b2e173fdull},
+      {kSlideI16, 6, 1, 1500, 1500, 0, 256, 0, 0, 1, true, 0xfd33ebc82650869cull},
+      {kHuge60000, 7, 1, 10, 10, 0, 256, 0, 63, 64, true, 0xc183f72a7b163e81ull},
+      {kHuge60000, 7, 1, 10, 10, 0, 8, 0, 0, 1, false, 0x2648f4c091cb9faaull},
+  };
+  int at = 0;
+  for (const Case& k : cases) {
+    const plan::Config c = with(plan_problem(k.p), k.cus, k.tile_u);
+    const std::vector<int64_t> off = plan_batch(k.seed, k.n, k.lo, k.hi, k.mix);
+    plan::ChunkPlan cp;
+    plan::plan_chunk(c, off.data(), k.n, cp);
+    plan::TilePlan tp;
+    const std::vector<dev::WaveStart> s =
+        plan::plan_waves(c, off.data(), k.identity ? nullptr : cp.long_recs.data(),
+                         k.identity ? k.n : static_cast<int64_t>(cp.long_recs.size()), k.part, k.parts, tp);
+    const uint64_t got = plan_digest(cp, tp, s);
+    CHECK(got == k.want);
+    if (got != k.want) std::fprintf(stderr, "  plan digest %d: 0x%016llxull\n", at, static_cast<unsigned long long>(got));
+    ++at;
+  }
+  // the per-offset profile's sub-tiles and a chunk's runs (HipEngine::run_profile)
+  struct ProfCase {
+    PlanProblem p;
+    unsigned seed;
+    int64_t n, lo, hi;
+    int cus, tile_u;
+    uint64_t want;
+  };
+  const ProfCase prof_cases[] = {{kLut400, 9, 200, 1, 420, 256, 0, 0x6773b8f1ed8b0a78ull}, {kWhole1489, 9, 33, 1400, 1489, 8, 0, 0x63d3e3d3695721c7ull},
+                                 {kSlide3000, 9, 64, 20, 90, 1, 8, 0x11108bd2ab9a3405ull}};
+  for (const ProfCase& k : prof_cases) {
+    const plan::Config c = with(plan_problem(k.p), k.cus, k.tile_u);
+    const std::vector<int64_t> off = plan_batch(k.seed, k.n, k.lo, k.hi);
+    int64_t max_need = 1;
+    for (int64_t i = 0; i < k.n; ++i) max_need = std::max(max_need, dev::lanes_needed(c.L1, off[i + 1] - off[i]));
+    const int u = plan::profile_u(c, off[k.n] - off[0], k.n, max_need);
+    const std::vector<dev::WaveStart> s = plan::profile_runs(c, off.data(), k.n, u);
+    // the profile kernel walks its chunk like the LUT tile kernel walks a batch
+    plan::TilePlan tp;
+    tp.u = u;
+    check_plan_shape(c, off.data(), nullptr, k.n, tp, s);
+    Tiles seen = walk_plan(c, off.data(), nullptr, k.n, tp, s);
+    std::sort(seen.begin(), seen.end());
+    CHECK(seen == plan_tiles(c, off.data(), nullptr, k.n, tp));
+    const uint64_t got = runs_digest(fnv1a(14695981039346656037ull, u), s);
+    CHECK(got == k.want);
+    if (got != k.want) std::fprintf(stderr, "  profile digest %d: 0x%016llxull\n", at, static_cast<unsigned long long>(got));
+    ++at;
+  }
+}
+
+int main(int argc, char** argv) {
   const std::vector<std::pair<const char*, std::function<void()>>> tests = {
       {"score_table", test_score_table}, {"parser", test_parser},     {"stream_reader", test_stream_reader},
       {"partition", test_partition},     {"keys", test_keys},         {"pack5", test_pack5},
@@ -1511,8 +1943,11 @@ int main() {
       {"cutter_count_ahead", test_cutter_count_ahead}, {"swipe_replay_bounds", test_swipe_replay_bounds},
       {"short_replay_bounds", test_short_replay_bounds}, {"tile16_replay_bounds", test_tile16_replay_bounds},
       {"tile16_key32_replay", test_tile16_key32_replay}, {"tile16_i16_replay", test_tile16_i16_replay},
-      {"profile16_lds_bytes", test_profile16_lds_bytes}, {"watchdog", test_watchdog}};
+      {"profile16_lds_bytes", test_profile16_lds_bytes}, {"watchdog", test_watchdog},
+      {"tile_plan_cases", test_tile_plan_cases}, {"tile_plan_digests", test_tile_plan_digests},
+      {"plan_chunk_threaded", test_plan_chunk_threaded}, {"plan_layout", test_plan_layout}};
   for (const auto& t : tests) {
+    if (argc > 1 && !std::strstr(t.first, argv[1])) continue;  // test_core NAME: only the tests named *NAME*
     const int before = g_failed;
     t.second();
     std::printf("%-24s %s\n", t.first, g_failed == before ? "ok" : "FAILED");
