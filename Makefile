@@ -54,7 +54,7 @@ COMM_OBJS := $(OBJ)/comm/comm.o $(OBJ)/comm/mpi_device_comm.o
 RCCL_OBJS := $(OBJ)/comm/rccl_comm.o
 HEADERS   := $(shell find csrc/include -name '*.h' -o -name '*.hpp')
 
-.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san
+.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san
 
 all: build
 build: lib final $(GPU_PLUGIN)
@@ -223,6 +223,13 @@ tile-plan-san: $(BUILD)/tile_plan_san
 	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/tile_plan_san plan
 $(BUILD)/tile_plan_san: csrc/tests/test_core.cpp csrc/apps/text_cut.cpp csrc/apps/text_cut.hpp $(PSAN_OBJS) $(HEADERS)
 	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/test_core.cpp csrc/apps/text_cut.cpp $(PSAN_OBJS) -ldl
+
+# stand-alone ASan/UBSan check of the alignment report's host code: report_batch_cpu over the goldens' rows and
+# hostile rows, and the report planner (own main, host code only; run from the repository root)
+report-san: $(BUILD)/report_san
+	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/report_san
+$(BUILD)/report_san: csrc/tests/report_san.cpp $(PSAN_OBJS) $(HEADERS)
+	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/report_san.cpp $(PSAN_OBJS) -ldl
 
 # parser throughput (count vs fill, SIMD A/B): build/fill_bench [records]
 $(BUILD)/fill_bench: tools/fill_bench.cpp $(CPU_OBJS) $(HEADERS)

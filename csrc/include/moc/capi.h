@@ -82,6 +82,15 @@ int moc_cpu_profile(const int32_t* weights4, const uint8_t* seq1, int64_t L1, co
 int moc_cpu_topk(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
                  const int64_t* offsets, int64_t n, int semantics, int threads, int K, moc_result* out);
 
+/* ---- alignment report (moc/cpu_engine.hpp report_batch_cpu) ----
+ * rows: [n, K] result rows, K in 1..64. counts: int32 [n, K, 4] sign counts ($ % # space) of each row — 0 for an
+ * empty row (score INT32_MIN), -1 for a row whose n / k do not place the record inside Seq1. marks (NULL = none):
+ * K * letters bytes, row j of record i at K * (offsets[i] - offsets[0]) + j * L2_i, one of '$' '%' '#' ' ' per
+ * letter (0 for empty and invalid rows). The row's score is not checked against the counts. */
+int moc_cpu_report(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                   const int64_t* offsets, int64_t n, int threads, int K, const moc_result* rows, int32_t* counts,
+                   uint8_t* marks);
+
 /* ---- partition ---- */
 int moc_partition(const int64_t* lengths, int64_t n, int64_t L1, int parts, double cell_w, double byte_w,
                   double record_w, int64_t* bounds_out /* parts+1 */);
@@ -160,6 +169,13 @@ int moc_engine_solve_topk_device(void* e, const uint8_t* d_codes, const int64_t*
 int moc_engine_set_profile_scratch(void* e, int64_t bytes);
 /* device time (ms) of the last top-K call's select launches (engines started with MOC_PROFILE_TIMING=1; else 0) */
 int moc_engine_topk_select_ms(void* e, double* ms);
+/* Alignment report on the GPU (byte letters, dense offsets): as moc_cpu_report. The host form is synchronous; the
+ * device form queues on `stream` without a sync (d_counts 16-byte aligned; d_marks NULL or K * letters bytes). */
+int moc_engine_report(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int K, const moc_result* rows,
+                      int32_t* counts, uint8_t* marks);
+int moc_engine_report_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                             int64_t n, int K, const moc_result* d_rows, int32_t* d_counts, uint8_t* d_marks,
+                             void* stream);
 /* stats: kernel_ms, total_ms, h2d_bytes, d2h_bytes, chunks, cells, records, direct, format, kernels,
  * r2 smin, r2 kw, r2 j, forms (moc::bounds::FormBits of the last solve) */
 int moc_engine_stats(void* e, double* out14);

@@ -79,6 +79,24 @@ void profile_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const
 void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
                     Semantics sem, int num_threads = 0);
 
+// ---- alignment report: the signs under a result row's letter pairs
+// A row is a Result {score, n, k} of record i (L2 letters) against Seq1; rows[i*K .. i*K+K) belong to record i.
+//   empty row   (score == kNoCandidateScore, e.g. top-K padding): counts {0,0,0,0}, marker bytes 0, nothing read
+//   valid row   (report_row_valid): letter i faces Seq1[n + i] when k == 0 or i < k, else Seq1[n + i + 1] (the
+//               hyphen faces Seq1[n + k] and is not counted); counts[PairClass] of those pairs, summing to L2;
+//               marker byte i = ScoreTable::class_char of pair i
+//   invalid row (anything else): counts {-1,-1,-1,-1}, marker bytes 0; n and k never form an address
+// W1*c[0] - W2*c[1] - W3*c[2] - W4*c[3] is a valid row's true score; it is NOT compared with row.score here.
+// Validity does not depend on the semantics: the spec-only final offset (L1 - L2, 0) is valid.
+inline bool report_row_valid(int64_t L1, int64_t L2, const Result& r) {
+  return L2 >= 1 && L2 <= L1 && r.k >= 0 && static_cast<int64_t>(r.k) <= L2 - 1 && r.n >= 0 &&
+         static_cast<int64_t>(r.n) + L2 + (r.k > 0 ? 1 : 0) <= L1;
+}
+// counts: int32 [n*K*4]. marks (nullable): K * (total letters) bytes; row j of record i is the L2_i bytes at
+// K * (offset of record i in the batch) + j * L2_i (64-bit indices). OpenMP over rows.
+void report_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, const Result* rows,
+                      int K, int32_t* counts, uint8_t* marks, int num_threads = 0);
+
 // Literal O(L1*L2^2) emulation of calc_result's loops (cudaFunctions.cu:74-172), race-free.
 // Test oracle only.
 Result brute_force_record(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2,

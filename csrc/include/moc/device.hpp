@@ -283,6 +283,43 @@ void launch_offset_profile(const ProblemView& pv, const BatchView& bv, const Pro
 // record index r), padded with no_candidate(); 1 <= K <= kMaxTopK.
 void launch_topk_select(const ProfileArgs& pa, int64_t n_rec, int K, Result* out, hipStream_t stream);
 
+// ---- alignment report (report_kernels.hip; definitions: moc/cpu_engine.hpp report_batch_cpu)
+// The 32x32 pair classes (ScoreTable::cls), two bits each: entry e in word e / 16 at bit 2 * (e % 16). They do
+// not depend on the weights and travel as a kernel argument (256 bytes); every block expands them into LDS.
+struct ReportClassBits {
+  uint32_t w[kLutStride * kLutStride / 16];
+};
+// One wave of the lane-per-row kernel: records [r0, r0 + cnt) of the batch, all of at most
+// bounds::kReportShortMaxL2 letters, cnt * K <= 64 rows.
+struct ReportItem {
+  int32_t r0;
+  int32_t cnt;
+};
+struct ReportArgs {
+  int32_t K = 1;                       // rows per record
+  const Result* rows = nullptr;        // device, [n * K]; any content (every row is bounds-checked)
+  int32_t* counts = nullptr;           // device, [n * K * 4], 16-byte aligned
+  uint8_t* marks = nullptr;            // device or null: K * letters bytes, record i's row j at
+                                       // K * (offsets[i] - offsets[0]) + j * L2_i
+  // lane-per-row kernel: n_items waves; items == null means wave w takes records [w * rpw, w * rpw + rpw) of
+  // the batch (every record short), rpw = 64 / K
+  const ReportItem* items = nullptr;
+  int64_t n_items = 0;
+  // wave-per-row kernel: n_long * K waves over the records long_recs[0 .. n_long)
+  const int32_t* long_recs = nullptr;
+  int64_t n_long = 0;
+  int32_t num_cus = 256;
+  int64_t marks_bytes = 0;             // debug builds: bytes of `marks` (store indices are checked against it)
+};
+inline ReportClassBits report_class_bits(const uint8_t* cls /* ScoreTable::cls */) {
+  ReportClassBits b{};
+  for (int e = 0; e < kLutStride * kLutStride; ++e) b.w[e >> 4] |= static_cast<uint32_t>(cls[e] & 3u) << (2 * (e & 15));
+  return b;
+}
+// Queues the two kernels (either may have no work) on `stream`; pv supplies Seq1 (padded) and L1 only.
+void launch_alignment_report(const ProblemView& pv, const BatchView& bv, const ReportClassBits& cb, const ReportArgs& ra,
+                             hipStream_t stream);
+
 // Loads every kernel file's code object onto the current device now (HIP loads them lazily, at the first
 // launch from each file: milliseconds inside the first timed search of a job otherwise).
 void preload_align_kernels();
@@ -292,6 +329,7 @@ void preload_swipe_p33_kernels();
 void preload_tile16_kernels();
 void preload_mfma_kernels();
 void preload_profile_kernels();
+void preload_report_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -302,6 +340,7 @@ enum PreloadSet : unsigned {
   kPreloadMfma = 32,  // the measured-slower MFMA variant: only when it is selected (MOC_MFMA=1)
   kPreloadAll = 31,   // all but MFMA and the profile file: existing jobs' start-up stays as it is
   kPreloadProfile = 64,  // profile_kernels.hip: loads at its first launch unless named
+  kPreloadReport = 128,  // report_kernels.hip: likewise
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -311,9 +350,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadSwipeP33) preload_swipe_p33_kernels();
   if (set & kPreloadTile16) preload_tile16_kernels();
   if (set & kPreloadProfile) preload_profile_kernels();
+  if (set & kPreloadReport) preload_report_kernels();
 }
 // "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
-// profile;
+// profile, report;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

@@ -60,7 +60,7 @@ struct EngineStats {
   int32_t direct = 0;    // 1 if the last solve streamed from pinned host memory (zero-copy)
   int32_t format = 0;    // ResultFormat of the last solve
   int32_t kernels = 0;   // bitmask of kernels used: 1 swipe (lane/record), 2 short (lane/offset), 4 tiles
-                         // (LUT tile kernel), 8 tile16, 16 profile (per-offset profile / top-K)
+                         // (LUT tile kernel), 8 tile16, 16 profile (per-offset profile / top-K), 32 report
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -144,6 +144,18 @@ class HipEngine {
   // Device time (ms) of the select launches of the last top-K call; recorded only when MOC_PROFILE_TIMING=1
   // was set at engine start (an event pair per chunk), else 0. Waits for them.
   double topk_select_ms();
+
+  // ---- alignment report (definitions: moc/cpu_engine.hpp report_batch_cpu; kernels:
+  // csrc/src/hip/report_kernels.hip): the sign counts and, optionally, the marker bytes of caller-supplied rows.
+  // Byte letters and dense int64 offsets only; no Semantics (row validity does not depend on it).
+  // Device form: d_rows [n*K] rows, d_counts [n*K*4] int32 (16-byte aligned), d_marks null or K * letters bytes;
+  // queued on `stream` (0 = engine compute stream) with no sync — directly behind solve_device /
+  // solve_topk_device on the same stream. 1 <= K <= kMaxTopK.
+  void report_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n, int K,
+                     const Result* d_rows, int32_t* d_counts, uint8_t* d_marks, hipStream_t stream);
+  // Host form (uploads through the pooled buffers; synchronous; fills stats()). marks may be null.
+  void report(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, const Result* rows, int32_t* counts,
+              uint8_t* marks);
 
   // Context-parallel search: this engine evaluates part `part` of `parts` of the batch's
   // global list of offset tiles and writes one packed 64-bit key per record (moc::encode_key; 0 =

@@ -100,6 +100,14 @@ inline int tile16_key32_bits(int64_t L1, int32_t max_abs_t, int64_t max_l2) {
   return static_cast<int64_t>(max_abs_t) * max_l2 < (int64_t{1} << (31 - ib)) ? ib : 0;
 }
 
+// ---- alignment report (report_kernels.hip): rows of records up to kReportShortMaxL2 letters take one lane
+// each, their four sign counters packed as the bytes of one register — exact while a count (<= L2) fits a
+// byte; longer records take one wave per row with int32 counters (any length).
+constexpr int64_t kReportShortMaxL2 = 64;
+constexpr int64_t kReportPackedCountMax = 255;
+static_assert(kReportShortMaxL2 <= kReportPackedCountMax, "report: packed byte counters of the lane-per-row regime");
+inline bool report_short_row(int64_t L2) { return L2 <= kReportShortMaxL2; }
+
 // Form bits reported per solve (EngineStats::forms; Python: stats()["forms"]).
 enum FormBits : int32_t {
   kFormSwipeKBits = 1,    // swipe, int16 keys with k bits

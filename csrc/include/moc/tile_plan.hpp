@@ -100,5 +100,21 @@ std::vector<dev::WaveStart> plan_waves(const Config& c, const int64_t* offsets, 
 int profile_u(const Config& c, int64_t sum_l2, int64_t n, int64_t max_need);
 std::vector<dev::WaveStart> profile_runs(const Config& c, const int64_t* offsets, int64_t n, int u);
 
+// ---- alignment report (report_kernels.hip): which records' rows take a lane each and which a wave each.
+// Records of at most bounds::kReportShortMaxL2 letters are short. A wave of the lane-per-row kernel takes up to
+// rpw = 64 / K consecutive short records (whole records: their K rows share the staged letters). When every
+// record is short the waves are implicit — wave w takes records [w * rpw, min(n, w * rpw + rpw)) — and `items`
+// stays empty; otherwise `items` lists each wave's run (never across a long record) and `long_recs` the rest.
+struct ReportPlan {
+  int K = 1;
+  int rpw = 64;
+  bool implicit = true;
+  int64_t n_items = 0;
+  std::vector<dev::ReportItem> items;
+  std::vector<int32_t> long_recs;
+};
+// Throws Error unless 1 <= K <= kMaxTopK and n < 2^31 - 1.
+ReportPlan plan_report(const int64_t* offsets, int64_t n, int K);
+
 }  // namespace plan
 }  // namespace moc

@@ -221,6 +221,16 @@ int moc_cpu_topk(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const
   });
 }
 
+int moc_cpu_report(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                   const int64_t* offsets, int64_t n, int threads, int K, const moc_result* rows, int32_t* counts,
+                   uint8_t* marks) {
+  return guard([&] {
+    const moc::ScoreTable t = moc::ScoreTable::build(weights_of(weights4));
+    const moc::RecordBatch b = view_batch(codes, offsets, n);
+    moc::report_batch_cpu(t, seq1, L1, b, reinterpret_cast<const moc::Result*>(rows), K, counts, marks, threads);
+  });
+}
+
 int moc_partition(const int64_t* lengths, int64_t n, int64_t L1, int parts, double cell_w, double byte_w,
                   double record_w, int64_t* bounds_out) {
   return guard([&] {
@@ -502,6 +512,24 @@ int moc_engine_set_profile_scratch(void* e, int64_t bytes) {
 
 int moc_engine_topk_select_ms(void* e, double* ms) {
   return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->topk_select_ms(); });
+}
+
+int moc_engine_report(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int K, const moc_result* rows,
+                      int32_t* counts, uint8_t* marks) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->report(codes, offsets, n, K, reinterpret_cast<const moc::Result*>(rows), counts,
+                                            marks);
+  });
+}
+
+int moc_engine_report_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                             int64_t n, int K, const moc_result* d_rows, int32_t* d_counts, uint8_t* d_marks,
+                             void* stream) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->report_device(d_codes, d_offsets, h_offsets, n, K,
+                                                   reinterpret_cast<const moc::Result*>(d_rows), d_counts, d_marks,
+                                                   static_cast<hipStream_t>(stream));
+  });
 }
 
 int moc_engine_stats(void* e, double* out14) {

@@ -326,6 +326,35 @@ Result brute_force_record(const ScoreTable& t, const uint8_t* s1, int64_t L1, co
   return best;
 }
 
+void report_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, const Result* rows,
+                      int K, int32_t* counts, uint8_t* marks, int num_threads) {
+  if (K < 1 || K > kMaxTopK) throw Error("report: K must be in 1.." + std::to_string(kMaxTopK));
+  const int64_t n = batch.size(), n_rows = n * K;
+  const int nt = std::max(1, num_threads > 0 ? num_threads : omp_get_max_threads());
+#pragma omp parallel for schedule(static) num_threads(nt) if (nt > 1 && n_rows > 256)
+  for (int64_t q = 0; q < n_rows; ++q) {
+    const int64_t i = q / K, j = q % K, L2 = batch.length(i);
+    const Result r = rows[q];
+    int32_t* c = counts + 4 * q;
+    uint8_t* m = marks ? marks + K * (batch.offsets[i] - batch.offsets[0]) + j * L2 : nullptr;
+    const bool empty = r.score == kNoCandidateScore;
+    if (empty || !report_row_valid(L1, L2, r)) {
+      c[0] = c[1] = c[2] = c[3] = empty ? 0 : -1;
+      if (m) std::fill(m, m + std::max<int64_t>(L2, 0), uint8_t{0});
+      continue;
+    }
+    const uint8_t* s2 = batch.record(i);
+    int32_t cnt[4] = {0, 0, 0, 0};
+    for (int64_t l = 0; l < L2; ++l) {
+      const int64_t at = (r.k == 0 || l < r.k) ? r.n + l : r.n + l + 1;
+      const uint8_t cl = t.cls[s2[l] * kLutStride + s1[at]];
+      ++cnt[cl];
+      if (m) m[l] = static_cast<uint8_t>(ScoreTable::class_char(static_cast<PairClass>(cl)));
+    }
+    c[0] = cnt[0], c[1] = cnt[1], c[2] = cnt[2], c[3] = cnt[3];
+  }
+}
+
 Result resolve_key(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2, uint64_t key) {
   if (key == 0) return no_candidate();
   const int32_t score = static_cast<int32_t>(static_cast<uint32_t>(key >> 32) ^ 0x80000000u);

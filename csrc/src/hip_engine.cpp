@@ -110,7 +110,7 @@ int parse_preload_set(const char* s) {
   } names[] = {{"all", kPreloadAll}, {"none", 0}, {"align", kPreloadAlign}, {"short", kPreloadShort},
                {"swipe", kPreloadSwipeByte | kPreloadSwipeP33}, {"swipe8", kPreloadSwipeByte},
                {"swipe33", kPreloadSwipeP33}, {"tile16", kPreloadTile16}, {"mfma", kPreloadMfma},
-               {"profile", kPreloadProfile}};
+               {"profile", kPreloadProfile}, {"report", kPreloadReport}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -1132,6 +1132,81 @@ void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t
   copy_d2h(out, s.d_out, obytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
   host_call_stats(wall, device_kernel_ms(), rebased[n], n, obytes);
+}
+
+// ---- alignment report -----------------------------------------------------------------------------------
+// Plan buffer (mixed batches only): wave items | long_recs. A batch of short records uploads nothing.
+void HipEngine::report_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                              int K, const Result* d_rows, int32_t* d_counts, uint8_t* d_marks, hipStream_t stream) {
+  if (!have_problem_) throw Error("HipEngine::report_device before set_problem");
+  const plan::ReportPlan rp = plan::plan_report(h_offsets, std::max<int64_t>(n, 0), K);  // checks K and n
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  if (n <= 0) return;
+  if (reinterpret_cast<uintptr_t>(d_counts) & 15) throw Error("report: the counts buffer must be 16-byte aligned");
+  if (!stream) stream = s_compute_;
+  TraceRange tr("moc.report_device");
+  dev::ReportArgs ra;
+  ra.K = K;
+  ra.rows = d_rows;
+  ra.counts = d_counts;
+  ra.marks = d_marks;
+  ra.marks_bytes = static_cast<int64_t>(K) * (h_offsets[n] - h_offsets[0]);
+  ra.n_items = rp.n_items;
+  ra.n_long = static_cast<int64_t>(rp.long_recs.size());
+  ra.num_cus = cfg_.num_cus;
+  if (!rp.implicit) {
+    const size_t items_bytes = sizeof(dev::ReportItem) * rp.items.size();
+    const size_t bytes = items_bytes + sizeof(int32_t) * rp.long_recs.size();
+    MOC_HIP_CHECK(hipEventSynchronize(ev_plan_));  // previous call's plan buffers are free again
+    ensure(d_plan_, d_plan_cap_, bytes);
+    ensure_host(h_plan_, h_plan_cap_, bytes);
+    std::memcpy(h_plan_, rp.items.data(), items_bytes);
+    std::memcpy(static_cast<char*>(h_plan_) + items_bytes, rp.long_recs.data(), bytes - items_bytes);
+    upload_staged(d_plan_, h_plan_, bytes, stream);
+    ra.items = static_cast<const dev::ReportItem*>(d_plan_);
+    ra.long_recs = reinterpret_cast<const int32_t*>(static_cast<const char*>(d_plan_) + items_bytes);
+  }
+  dev::ProblemView pv{};  // the report reads Seq1 and its length only
+  pv.seq1 = d_seq1_;
+  pv.L1 = static_cast<int32_t>(cfg_.L1);
+  const dev::BatchView bv{d_codes + h_offsets[0], d_offsets, n};
+  ensure_device_events();
+  MOC_HIP_CHECK(hipEventRecord(ev_d0_, stream));
+  dev::launch_alignment_report(pv, bv, dev::report_class_bits(table_.cls.data()), ra, stream);
+  MOC_HIP_CHECK(hipGetLastError());
+  MOC_HIP_CHECK(hipEventRecord(ev_d1_, stream));
+  if (!rp.implicit) MOC_HIP_CHECK(hipEventRecord(ev_plan_, stream));
+  stats_ = EngineStats{};
+  stats_.records = n;
+  stats_.chunks = (ra.n_items > 0 ? 1 : 0) + (ra.n_long > 0 ? 1 : 0);  // launches
+  stats_.kernels = 32;
+}
+
+void HipEngine::report(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, const Result* rows,
+                       int32_t* counts, uint8_t* marks) {
+  if (K < 1 || K > kMaxTopK) throw Error("report: K must be in 1.." + std::to_string(kMaxTopK));
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  if (n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  Slot& s = *slots_[0];
+  // d_out: counts (16-byte aligned at the start) | rows | marker bytes
+  const size_t n_rows = static_cast<size_t>(n) * static_cast<size_t>(K);
+  const size_t cbytes = 16 * n_rows, rbytes = sizeof(Result) * n_rows;
+  const size_t mbytes = marks ? static_cast<size_t>(K) * static_cast<size_t>(offsets[n] - offsets[0]) : 0;
+  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, cbytes + rbytes + std::max<size_t>(mbytes, 16));
+  char* d = static_cast<char*>(s.d_out);
+  copy_h2d(d + cbytes, rows, rbytes, s_compute_);
+  report_device(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(), n, K,
+                reinterpret_cast<const Result*>(d + cbytes), reinterpret_cast<int32_t*>(d),
+                marks ? reinterpret_cast<uint8_t*>(d + cbytes + rbytes) : nullptr, s_compute_);
+  copy_d2h(counts, d, cbytes, s_compute_);
+  if (mbytes) copy_d2h(marks, d + cbytes + rbytes, mbytes, s_compute_);
+  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+  host_call_stats(wall, device_kernel_ms(), rebased[n], n, cbytes + mbytes);
+  stats_.h2d_bytes += static_cast<int64_t>(rbytes);
 }
 
 }  // namespace moc

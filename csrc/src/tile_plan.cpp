@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <queue>
+#include <string>
 
 #include "moc/problem.hpp"
 
@@ -403,6 +404,42 @@ std::vector<dev::WaveStart> profile_runs(const Config& c, const int64_t* offsets
   std::vector<int64_t> tcost;
   const int64_t total_tiles = tile_costs(c, offsets, nullptr, n, dev::tile_span(false, u), ntiles, tcost);
   return balanced_runs(ntiles, tcost, total_tiles, 0, 1, static_cast<int64_t>(c.num_cus) * c.tile_waves_per_cu);
+}
+
+ReportPlan plan_report(const int64_t* offsets, int64_t n, int K) {
+  if (K < 1 || K > kMaxTopK) throw Error("report: K must be in 1.." + std::to_string(kMaxTopK));
+  if (n >= (int64_t{1} << 31) - 1) throw Error("report: more than 2^31 - 2 records in one call");
+  ReportPlan rp;
+  rp.K = K;
+  rp.rpw = dev::kWave / K;
+  if (n <= 0) return rp;
+  int64_t max_l2 = 0, min_l2 = 0;  // one pass over the lengths decides the common, all-short case
+  const int nt = n > (1 << 16) ? omp_get_max_threads() : 1;
+#pragma omp parallel for schedule(static) reduction(max : max_l2) reduction(min : min_l2) num_threads(nt) if (nt > 1)
+  for (int64_t i = 0; i < n; ++i) {
+    max_l2 = std::max(max_l2, offsets[i + 1] - offsets[i]);
+    min_l2 = std::min(min_l2, offsets[i + 1] - offsets[i]);
+  }
+  if (min_l2 < 0) throw Error("report: record offsets must not decrease");
+  if (max_l2 >= (int64_t{1} << 30)) throw Error("report: Seq2 lengths beyond 2^30 exceed the device engine's offset range");
+  if (bounds::report_short_row(max_l2)) {
+    rp.n_items = (n + rp.rpw - 1) / rp.rpw;
+    return rp;
+  }
+  rp.implicit = false;
+  rp.items.reserve(static_cast<size_t>(n / rp.rpw + 1));
+  for (int64_t i = 0; i < n;) {
+    if (!bounds::report_short_row(offsets[i + 1] - offsets[i])) {
+      rp.long_recs.push_back(static_cast<int32_t>(i++));
+      continue;
+    }
+    int64_t e = i + 1;
+    while (e < n && e - i < rp.rpw && bounds::report_short_row(offsets[e + 1] - offsets[e])) ++e;
+    rp.items.push_back(dev::ReportItem{static_cast<int32_t>(i), static_cast<int32_t>(e - i)});
+    i = e;
+  }
+  rp.n_items = static_cast<int64_t>(rp.items.size());
+  return rp;
 }
 
 }  // namespace plan

@@ -7,10 +7,11 @@ window. See README.md and SURVEY.md.
 """
 from .models.problem import Problem
 from .models.scoring import PairClass, Semantics, Weights
-from .ops.align import (PROFILE_DTYPE, HipSearchEngine, align_profile_device, align_search, align_search_device,
-                        align_topk_device, brute_force_native, decode_keys, device_count, profile_offsets, search_cpu,
-                        search_hip, search_keys_cpu, search_profile_cpu, search_topk_cpu)
-from .utils.io import format_results, format_topk, write_results
+from .ops.align import (PROFILE_DTYPE, HipSearchEngine, align_profile_device, align_report_device, align_search,
+                        align_search_device, align_topk_device, brute_force_native, decode_keys, device_count,
+                        profile_offsets, report_scores, search_cpu, search_hip, search_keys_cpu, search_profile_cpu,
+                        search_report_cpu, search_topk_cpu)
+from .utils.io import format_report, format_results, format_topk, write_results
 from .utils.synthetic import make_synthetic
 
 __version__ = "0.1.0"
@@ -19,4 +20,5 @@ __all__ = [
     "brute_force_native", "device_count", "search_cpu", "search_hip", "format_results", "write_results",
     "make_synthetic", "search_keys_cpu", "decode_keys", "PROFILE_DTYPE", "profile_offsets", "search_profile_cpu",
     "search_topk_cpu", "align_profile_device", "align_topk_device", "format_topk",
+    "search_report_cpu", "report_scores", "align_report_device", "format_report",
 ]

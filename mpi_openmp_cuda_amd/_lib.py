@@ -78,6 +78,11 @@ def _decl(lib):
                                                  c_void_p]),
         "moc_engine_set_profile_scratch": (c_int, [c_void_p, c_int64]),
         "moc_engine_topk_select_ms": (c_int, [c_void_p, c_void_p]),
+        "moc_cpu_report": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p]),
+        "moc_engine_report": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+        "moc_engine_report_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
         "moc_partition": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_double, c_void_p]),
         "moc_device_count": (c_int, []),
         "moc_host_register": (c_int, [c_void_p, c_size_t]),

@@ -16,7 +16,7 @@ from .models.problem import Problem
 from .models.scoring import Semantics
 from .parallel import dist as D
 from .parallel.search import DistributedSearch
-from .utils.io import format_topk, write_results
+from .utils.io import format_report, format_topk, write_results
 
 
 def main(argv=None) -> int:
@@ -39,6 +39,10 @@ def main(argv=None) -> int:
     ap.add_argument("--top", type=int, default=1, metavar="K",
                     help="print every record's K best offsets (1..64): rank 1 as always, ranks j >= 2 as "
                          "'#i.j: score: S, n: N, k: K'. Record slices on one node only (--partition records)")
+    ap.add_argument("--show-alignment", action="store_true",
+                    help="after every result line print the alignment it stands for: the sign counts, the piece of "
+                         "Seq1, the marker line and the record with its hyphen. With --top K or without; record "
+                         "slices on one node only (--partition records)")
     a = ap.parse_args(argv)
     if not 1 <= a.top <= 64:
         ap.error("--top K: K must be in 1..64")
@@ -72,12 +76,25 @@ def main(argv=None) -> int:
                   "one candidate per record", file=sys.stderr)
         D.finalize(ctx)
         return 2
+    if a.show_alignment and search.partition != "records":
+        if ctx.is_root:
+            print("--show-alignment needs record slices (--partition records, one node); --partition offsets "
+                  "combines one packed key per record", file=sys.stderr)
+        D.finalize(ctx)
+        return 2
     if a.top > 1:
         results = search.run_topk(problem, a.top, Semantics.parse(a.semantics))
     else:
         results = search.run(problem, Semantics.parse(a.semantics))
     if ctx.is_root:
-        if a.top > 1:
+        if a.show_alignment:
+            from .ops.align import as_triples
+
+            rows = results if a.top > 1 else as_triples(results)
+            counts, marks = search.report(problem, rows)
+            sys.stdout.write(format_report(problem, rows, counts, marks))
+            sys.stdout.flush()
+        elif a.top > 1:
             sys.stdout.write(format_topk(results))
             sys.stdout.flush()
         else:

@@ -140,6 +140,53 @@ def search_topk_cpu(problem: Problem, K: int, semantics=Semantics.REFERENCE, thr
     return out
 
 
+# ---- alignment report: sign counts and marker bytes of result rows (csrc/include/moc/cpu_engine.hpp)
+REPORT_EMPTY = int(np.iinfo(np.int64).min)        # report_scores of an empty row (score INT32_MIN, top-K padding)
+REPORT_INVALID = int(np.iinfo(np.int64).min) + 1  # ... of a row whose (n, k) does not place the record in Seq1
+
+
+def _report_rows(rows, n: int):
+    """``rows`` as [n, 3] / [n, K, 3] integers or RESULT_DTYPE [n] / [n, K] -> (int32 [n, K, 3], K, was_flat)."""
+    r = np.asarray(rows)
+    if r.dtype == RESULT_DTYPE:
+        r = np.ascontiguousarray(r)
+        r = r.view(np.int32).reshape(r.shape + (3,))
+    flat = r.ndim == 2
+    if flat:
+        r = r[:, None, :]
+    if r.ndim != 3 or r.shape[0] != n or r.shape[2] != 3:
+        raise ValueError(f"report: rows must be [n, 3] or [n, K, 3] for the batch's n = {n}, got {np.shape(rows)}")
+    return np.ascontiguousarray(r, dtype=np.int32), _check_k(r.shape[1]), flat
+
+
+def search_report_cpu(problem: Problem, rows, marks: bool = False, threads: int = 0):
+    """Sign counts of result rows on the CPU engine. ``rows``: [n, 3] or [n, K, 3] (score, n, k), e.g. from
+    search_cpu / search_topk_cpu. Returns int32 counts [n, 4] or [n, K, 4] in PairClass order ($, %, #, space):
+    zeros for an empty row (score INT32_MIN), -1 for a row whose n / k do not place the record inside Seq1, else
+    the classes of the record's letter pairs (they sum to its length; :func:`report_scores` gives the score they
+    stand for — the row's own score is not checked). With ``marks`` also a flat uint8 array of K * total
+    marker bytes ('$', '%', '#', ' '; 0 for empty and invalid rows): row j of record i is the L2_i bytes at
+    ``K * offsets[i] + j * L2_i``. No semantics: the spec-only final offset is a valid row."""
+    r, K, flat = _report_rows(rows, problem.n)
+    counts = np.zeros((problem.n, K, 4), np.int32)
+    m = np.zeros(max(K * problem.total_chars, 1), np.uint8) if marks else None
+    _lib.check(_lib.lib().moc_cpu_report(
+        _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+        _lib.ptr(problem.offsets), problem.n, int(threads), K, _lib.ptr(r), _lib.ptr(counts), _lib.ptr(m)))
+    counts = counts[:, 0] if flat else counts
+    return (counts, m[:K * problem.total_chars]) if marks else counts
+
+
+def report_scores(counts, weights) -> np.ndarray:
+    """int64 W1*c[0] - W2*c[1] - W3*c[2] - W4*c[3] of report counts [..., 4]: the score a valid row's alignment
+    really has. Empty rows give REPORT_EMPTY and invalid rows REPORT_INVALID (both outside the int32 range)."""
+    c = np.asarray(counts, dtype=np.int64)
+    w = Weights.of(weights)
+    s = w.w1 * c[..., 0] - w.w2 * c[..., 1] - w.w3 * c[..., 2] - w.w4 * c[..., 3]
+    s = np.where(c.sum(axis=-1) == 0, REPORT_EMPTY, s)
+    return np.where(c[..., 0] < 0, REPORT_INVALID, s)
+
+
 def brute_force_native(problem: Problem, semantics=Semantics.REFERENCE) -> np.ndarray:
     """Literal O(L1*L2^2) replay of the reference loops, in C++ (test oracle)."""
     out = empty_results(problem.n)
@@ -454,6 +501,53 @@ class HipSearchEngine:
         _lib.check(_lib.lib().moc_engine_topk_select_ms(self._h, ctypes.addressof(ms)))
         return float(ms.value)
 
+    # ---- alignment report (byte letters, dense offsets; csrc/src/hip/report_kernels.hip)
+    def report(self, codes: np.ndarray, offsets: np.ndarray, rows, marks: bool = False):
+        """Host CSR + result rows ([n, 3] or [n, K, 3]) -> the counts (and marker bytes) :func:`search_report_cpu`
+        returns, computed by the report kernels against the engine's Seq1. Synchronous; fills ``stats()``."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        r, K, flat = _report_rows(rows, n)
+        total = int(offsets[-1] - offsets[0])
+        counts = np.zeros((n, K, 4), np.int32)
+        m = np.zeros(max(K * total, 1), np.uint8) if marks else None
+        _lib.check(_lib.lib().moc_engine_report(self._h, _lib.ptr(codes), _lib.ptr(offsets), n, K, _lib.ptr(r),
+                                                _lib.ptr(counts), _lib.ptr(m)))
+        counts = counts[:, 0] if flat else counts
+        return (counts, m[:K * total]) if marks else counts
+
+    def report_device(self, codes_t, offsets_t, h_offsets: np.ndarray, rows_t, counts_t=None, marks_t=None,
+                      stream=None):
+        """Device-resident batch (as :meth:`solve_device`) and rows ``rows_t`` (int32 [n, 3] or [n, K, 3], e.g.
+        straight from :meth:`solve_device` / :meth:`solve_topk_device` on the same stream) -> ``counts_t``, an
+        int32 tensor [n, 4] / [n, K, 4] (allocated when None). ``marks_t``: None for counts alone, or a uint8
+        tensor of K * letters bytes that receives the marker bytes. Queued on ``stream`` (default: the current
+        stream); returns immediately."""
+        import torch
+
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        n = h_offsets.shape[0] - 1
+        assert rows_t.dtype == torch.int32 and rows_t.is_contiguous() and rows_t.shape[0] == n and rows_t.shape[-1] == 3
+        assert rows_t.dim() in (2, 3)
+        K = _check_k(1 if rows_t.dim() == 2 else rows_t.shape[1])
+        shape = (n, 4) if rows_t.dim() == 2 else (n, K, 4)
+        if counts_t is None:
+            counts_t = torch.empty(shape, dtype=torch.int32, device=codes_t.device)
+        assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        assert counts_t.dtype == torch.int32 and tuple(counts_t.shape) == shape and counts_t.is_contiguous()
+        if marks_t is not None:
+            total = int(h_offsets[-1] - h_offsets[0])
+            assert marks_t.dtype == torch.uint8 and marks_t.is_contiguous() and marks_t.numel() >= K * total
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        _lib.check(_lib.lib().moc_engine_report_device(
+            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
+            n, K, ctypes.c_void_p(rows_t.data_ptr()), ctypes.c_void_p(counts_t.data_ptr()),
+            ctypes.c_void_p(marks_t.data_ptr()) if marks_t is not None else None,
+            ctypes.c_void_p(stream.cuda_stream)))
+        return counts_t
+
     def kernel_times(self) -> tuple:
         """(kernel_ms, total_ms) of the last solve: the two fields a timed loop reads, without stats()'s dict."""
         v = self._stats_buf
@@ -472,7 +566,8 @@ class HipSearchEngine:
         d = dict(zip(keys, list(v)[:10]))
         d["r2"] = tuple(int(x) for x in list(v)[10:13])
         d["format"] = _lib.FORMAT_NAMES[int(d["format"])]
-        d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16"), (16, "profile")) if int(d["kernels"]) & b]
+        d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16"), (16, "profile"),
+                                             (32, "report")) if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
 
@@ -540,3 +635,19 @@ def align_topk_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, K:
     out = torch.empty((n, _check_k(K), 3), dtype=torch.int32, device=codes_t.device)
     engine.solve_topk_device(codes_t, offsets_t, h_offsets, K, out, stream)
     return out
+
+
+def align_report_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, rows_t, marks: bool = False,
+                        stream=None):
+    """torch-facing op: the sign counts of device rows (int32 [n, 3] or [n, K, 3]) as an int32 [n, 4] / [n, K, 4]
+    tensor on the codes' device; with ``marks`` also the uint8 marker bytes (K * letters, layout as
+    :func:`search_report_cpu`): ``(counts_t, marks_t)``."""
+    import torch
+
+    marks_t = None
+    if marks:
+        K = 1 if rows_t.dim() == 2 else int(rows_t.shape[1])
+        total = int(h_offsets[-1] - h_offsets[0])
+        marks_t = torch.empty(max(K * total, 1), dtype=torch.uint8, device=codes_t.device)
+    counts_t = engine.report_device(codes_t, offsets_t, h_offsets, rows_t, None, marks_t, stream)
+    return (counts_t, marks_t) if marks else counts_t

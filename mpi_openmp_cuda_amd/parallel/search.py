@@ -28,7 +28,7 @@ from .. import _lib
 from ..models.problem import Problem
 from ..models.scoring import Semantics
 from ..ops.align import (HipSearchEngine, decode_keys, device_count, keys_to_ordered_int64, ordered_int64_to_keys,
-                        search_cpu, search_keys_cpu, search_topk_cpu)
+                        search_cpu, search_keys_cpu, search_report_cpu, search_topk_cpu)
 from ..utils.timer import PhaseTimer
 from . import dist as D
 from .partition import CPU_COST, GPU_COST, partition
@@ -181,6 +181,14 @@ class DistributedSearch:
             D.barrier(ctx)
             win.close(unlink=ctx.is_root)
         return rows.astype(np.int32) if ctx.is_root else None
+
+    def report(self, problem: Problem, rows: np.ndarray):
+        """Root only: ``(counts, marks)`` of the search's rows (ops.align.search_report_cpu's outputs, with the
+        marker bytes), on this rank's engine — the GPU's report kernels or the CPU engine. The report is one pass
+        over the letters, so the ranks do not share it."""
+        if self.engine is not None:  # the search's _setup left this problem in the engine
+            return self.engine.report(problem.codes, problem.offsets, rows, marks=True)
+        return search_report_cpu(problem, rows, marks=True, threads=self.threads)
 
     def _run_shm(self, problem, prob, sem, n, total, b, e):
         ctx, T = self.ctx, self.timer

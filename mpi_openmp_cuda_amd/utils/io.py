@@ -50,6 +50,52 @@ def format_topk(topk, first_index: int = 0) -> str:
     return "".join(out)
 
 
+def format_report(problem, rows, counts, marks, first_index: int = 0) -> str:
+    """Results with their alignments. ``rows`` [n, 3] print as :func:`format_results` does and [n, K, 3] as
+    :func:`format_topk` does; after the line of every real row — not an empty one (score INT32_MIN), nor one
+    whose counts are -1 — come four lines, indented by two spaces: the counts (``counts``: [n, 4] / [n, K, 4]
+    from the report calls), Seq1[n .. n + L2 + (k > 0)), the marker line (``marks``: the report calls' marker
+    bytes) with '-' at position k when k > 0, and the record with '-' after its k-th letter."""
+    from ..models.scoring import decode
+
+    t = np.asarray(rows)
+    if t.dtype == _lib.RESULT_DTYPE:
+        t = np.ascontiguousarray(t).view(np.int32).reshape(t.shape + (3,))
+    t = t.astype(np.int64)
+    flat = t.ndim == 2
+    if flat:
+        t = t[:, None, :]
+    if t.ndim != 3 or t.shape[2] != 3 or t.shape[0] != problem.n:
+        raise ValueError("format_report needs [n, 3] or [n, K, 3] rows of the problem's records")
+    n, K = t.shape[0], t.shape[1]
+    c = np.asarray(counts, dtype=np.int64).reshape(n, K, 4)
+    m = np.asarray(marks, dtype=np.uint8).reshape(-1)
+    seq1 = decode(problem.seq1)
+    offsets = np.asarray(problem.offsets, dtype=np.int64)
+    none = np.iinfo(np.int32).min
+    out = []
+    for i in range(n):
+        seq2 = decode(problem.codes[offsets[i]:offsets[i + 1]])
+        L2 = len(seq2)
+        for j in range(K):
+            s, o, k = (int(v) for v in t[i, j])
+            if j == 0:
+                out.append(f"#{i + first_index}: score: {s}, n: {o}, k: {k}\n")
+            elif s != none:
+                out.append(f"#{i + first_index}.{j + 1}: score: {s}, n: {o}, k: {k}\n")
+            if s == none or c[i, j, 0] < 0:
+                continue
+            at = K * int(offsets[i] - offsets[0]) + j * L2
+            line = m[at:at + L2].tobytes().decode("ascii")
+            if k > 0:
+                line = line[:k] + "-" + line[k:]
+            out.append(f"  $: {c[i, j, 0]}, %: {c[i, j, 1]}, #: {c[i, j, 2]}, space: {c[i, j, 3]}\n")
+            out.append(f"  {seq1[o:o + L2 + (1 if k > 0 else 0)]}\n")
+            out.append(f"  {line}\n")
+            out.append(f"  {seq2[:k] + '-' + seq2[k:] if k > 0 else seq2}\n")
+    return "".join(out)
+
+
 def write_results(results: np.ndarray, stream=None, first_index: int = 0):
     stream = stream or sys.stdout
     stream.write(format_results(results, first_index))
