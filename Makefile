@@ -54,7 +54,7 @@ COMM_OBJS := $(OBJ)/comm/comm.o $(OBJ)/comm/mpi_device_comm.o
 RCCL_OBJS := $(OBJ)/comm/rccl_comm.o
 HEADERS   := $(shell find csrc/include -name '*.h' -o -name '*.hpp')
 
-.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san
+.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san hits-san
 
 all: build
 build: lib final $(GPU_PLUGIN)
@@ -230,6 +230,13 @@ report-san: $(BUILD)/report_san
 	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/report_san
 $(BUILD)/report_san: csrc/tests/report_san.cpp $(PSAN_OBJS) $(HEADERS)
 	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/report_san.cpp $(PSAN_OBJS) -ldl
+
+# stand-alone ASan/UBSan check of the CPU engine's threshold hits: hits_batch_cpu against a letter-by-letter count
+# at every threshold edge, rows in heap blocks of exactly cap rows (own main, host code only)
+hits-san: $(BUILD)/hits_san
+	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/hits_san
+$(BUILD)/hits_san: csrc/tests/hits_san.cpp $(PSAN_OBJS) $(HEADERS)
+	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/hits_san.cpp $(PSAN_OBJS) -ldl
 
 # parser throughput (count vs fill, SIMD A/B): build/fill_bench [records]
 $(BUILD)/fill_bench: tools/fill_bench.cpp $(CPU_OBJS) $(HEADERS)

@@ -82,6 +82,19 @@ int moc_cpu_profile(const int32_t* weights4, const uint8_t* seq1, int64_t L1, co
 int moc_cpu_topk(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
                  const int64_t* offsets, int64_t n, int semantics, int threads, int K, moc_result* out);
 
+/* ---- threshold hits (moc/cpu_engine.hpp hits_batch_cpu) ----
+ * Every offset o of record i whose profile score is >= its threshold (thresholds[i], or min_score for all records
+ * when thresholds is NULL; INT32_MIN selects the whole profile), as rows (score, n = o, k) in ascending o.
+ * hoffsets: int64 [n + 1], filled completely whatever cap is: hoffsets[0] = 0, record i's rows are
+ * rows[hoffsets[i] .. hoffsets[i + 1]), hoffsets[n] is the total. A row is written iff its flat index is < cap;
+ * nothing at or past rows + cap is touched; cap = 0 with rows = NULL counts only. */
+int moc_cpu_hits(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes, const int64_t* offsets,
+                 int64_t n, int semantics, int threads, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets,
+                 moc_result* rows, int64_t cap);
+/* out2: records per scan block and block sums per pass of the single scanning block of the GPU's prefix sum
+ * (moc/kernel_bounds.hpp); no GPU needed */
+int moc_hits_geometry(int32_t* out2);
+
 /* ---- alignment report (moc/cpu_engine.hpp report_batch_cpu) ----
  * rows: [n, K] result rows, K in 1..64. counts: int32 [n, K, 4] sign counts ($ % # space) of each row — 0 for an
  * empty row (score INT32_MIN), -1 for a row whose n / k do not place the record inside Seq1. marks (NULL = none):
@@ -176,6 +189,23 @@ int moc_engine_report(void* e, const uint8_t* codes, const int64_t* offsets, int
 int moc_engine_report_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
                              int64_t n, int K, const moc_result* d_rows, int32_t* d_counts, uint8_t* d_marks,
                              void* stream);
+/* Threshold hits on the GPU (byte letters, dense offsets; moc/hip_engine.hpp), as moc_cpu_hits. The device form
+ * queues on `stream` without a sync (d_thresholds: device int32 [n] or NULL; d_hoffsets: device int64 [n + 1];
+ * d_rows: cap rows, NULL with cap = 0). The host form is synchronous and optimistic: it runs with room for
+ * max(max_rows_hint, 1) rows (hint < 0: 4 n) and once more with the exact total when that was too few
+ * (moc_engine_hits_passes); it fills hoffsets, keeps the rows for this thread's next moc_engine_hits_rows and
+ * copies the first min(total, cap) of them to rows (NULL with cap = 0: none). */
+int moc_engine_solve_hits(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t min_score,
+                          const int32_t* thresholds, int64_t max_rows_hint, int64_t* hoffsets, moc_result* rows,
+                          int64_t cap);
+/* the first min(total, cap) rows of this thread's last moc_engine_solve_hits; releases them */
+int moc_engine_hits_rows(moc_result* rows, int64_t cap);
+int moc_engine_hits_passes(void* e);
+int moc_engine_solve_hits_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                 int64_t n, int32_t min_score, const int32_t* d_thresholds, int64_t* d_hoffsets,
+                                 moc_result* d_rows, int64_t cap, void* stream);
+/* device time (ms) of the last hits call's count + scan + compact launches (MOC_PROFILE_TIMING=1; else 0) */
+int moc_engine_hits_select_ms(void* e, double* ms);
 /* stats: kernel_ms, total_ms, h2d_bytes, d2h_bytes, chunks, cells, records, direct, format, kernels,
  * r2 smin, r2 kw, r2 j, forms (moc::bounds::FormBits of the last solve) */
 int moc_engine_stats(void* e, double* out14);

@@ -79,6 +79,18 @@ void profile_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const
 void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
                     Semantics sem, int num_threads = 0);
 
+// ---- threshold hits: every offset that scores at least a threshold
+// Hits of record i under threshold t_i (thresholds[i], or min_score for every record when thresholds is null): the
+// offsets o of its profile with profile[o].score >= t_i, in ascending o, each as a row (score, n = o, k =
+// profile[o].k). INT32_MIN selects the whole profile; a record without candidate offsets has no hits.
+// hoffsets (int64 [n + 1], always complete and exact): hoffsets[0] = 0, hoffsets[i + 1] - hoffsets[i] = record i's
+// hit count; record i's rows are rows[hoffsets[i] .. hoffsets[i + 1]). Capacity contract: a row is written iff its
+// flat index is < cap and nothing at or past rows + cap is touched; cap == 0 (rows may be null) counts only.
+// Two phases, counts then fill; one record's profile exists at a time per thread, never the batch's.
+void hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int32_t min_score,
+                    const int32_t* thresholds, int64_t* hoffsets, Result* rows, int64_t cap, Semantics sem,
+                    int num_threads = 0);
+
 // ---- alignment report: the signs under a result row's letter pairs
 // A row is a Result {score, n, k} of record i (L2 letters) against Seq1; rows[i*K .. i*K+K) belong to record i.
 //   empty row   (score == kNoCandidateScore, e.g. top-K padding): counts {0,0,0,0}, marker bytes 0, nothing read

@@ -320,6 +320,28 @@ inline ReportClassBits report_class_bits(const uint8_t* cls /* ScoreTable::cls *
 void launch_alignment_report(const ProblemView& pv, const BatchView& bv, const ReportClassBits& cb, const ReportArgs& ra,
                              hipStream_t stream);
 
+// ---- threshold hits (hits_kernels.hip; definitions: moc/cpu_engine.hpp hits_batch_cpu)
+// One chunk of consecutive records [rec0, rec0 + n_rec) whose profile lies where topk_select_kernel reads it:
+// prof[poffsets[r] - base + o]. hoffsets is the batch's int64 [n + 1] hit index: the count kernel leaves record
+// r's count in hoffsets[r + 1] (and 0 in hoffsets[0] when the chunk starts the batch), the scan turns the chunk's
+// counts into running totals on top of hoffsets[rec0] — complete since the previous chunk's scan on the same
+// stream — and the compaction stores record r's hits, ascending in o, at rows[hoffsets[r] ..) below `cap`.
+struct HitsArgs {
+  const ProfileEntry* prof = nullptr;
+  const int64_t* poffsets = nullptr;
+  int64_t base = 0;
+  int64_t prof_entries = 0;             // entries of `prof` (debug builds check the load index against it)
+  int64_t rec0 = 0, n_rec = 0;
+  const int32_t* thresholds = nullptr;  // device int32 [n] (batch-wide record index), or null: min_score for all
+  int32_t min_score = 0;
+  int64_t* hoffsets = nullptr;          // device int64 [n + 1]
+  int64_t* sums = nullptr;              // scan scratch: ceil(n_rec / bounds::kHitsScanBlockRecords) entries
+  Result* rows = nullptr;               // device, `cap` rows; null with cap == 0 counts only
+  int64_t cap = 0;
+};
+// Queues count, scan (one or three launches) and, when cap > 0, the compaction on `stream`.
+void launch_hits(const HitsArgs& ha, hipStream_t stream);
+
 // Loads every kernel file's code object onto the current device now (HIP loads them lazily, at the first
 // launch from each file: milliseconds inside the first timed search of a job otherwise).
 void preload_align_kernels();
@@ -330,6 +352,7 @@ void preload_tile16_kernels();
 void preload_mfma_kernels();
 void preload_profile_kernels();
 void preload_report_kernels();
+void preload_hits_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -341,6 +364,7 @@ enum PreloadSet : unsigned {
   kPreloadAll = 31,   // all but MFMA and the profile file: existing jobs' start-up stays as it is
   kPreloadProfile = 64,  // profile_kernels.hip: loads at its first launch unless named
   kPreloadReport = 128,  // report_kernels.hip: likewise
+  kPreloadHits = 256,    // hits_kernels.hip: likewise
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -351,9 +375,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadTile16) preload_tile16_kernels();
   if (set & kPreloadProfile) preload_profile_kernels();
   if (set & kPreloadReport) preload_report_kernels();
+  if (set & kPreloadHits) preload_hits_kernels();
 }
 // "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
-// profile, report;
+// profile, report, hits;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

@@ -60,7 +60,8 @@ struct EngineStats {
   int32_t direct = 0;    // 1 if the last solve streamed from pinned host memory (zero-copy)
   int32_t format = 0;    // ResultFormat of the last solve
   int32_t kernels = 0;   // bitmask of kernels used: 1 swipe (lane/record), 2 short (lane/offset), 4 tiles
-                         // (LUT tile kernel), 8 tile16, 16 profile (per-offset profile / top-K), 32 report
+                         // (LUT tile kernel), 8 tile16, 16 profile (per-offset profile / top-K), 32 report,
+                         // 64 hits (count / scan / compact, next to 16)
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -144,6 +145,27 @@ class HipEngine {
   // Device time (ms) of the select launches of the last top-K call; recorded only when MOC_PROFILE_TIMING=1
   // was set at engine start (an event pair per chunk), else 0. Waits for them.
   double topk_select_ms();
+
+  // ---- threshold hits (definitions: moc/cpu_engine.hpp hits_batch_cpu; kernels: csrc/src/hip/hits_kernels.hip):
+  // every offset whose profile score is >= the record's threshold, as rows (score, n = o, k) in ascending o, record
+  // i's at rows[hoffsets[i] .. hoffsets[i + 1]). Limits as top-K: byte letters, dense int64 offsets, n < 2^31 - 1.
+  // Device form: queued on `stream` (0 = engine compute stream) with no sync, in the chunks of top-K under
+  // profile_scratch_bytes — per chunk the profile kernel, then count, prefix sum and compaction. d_thresholds:
+  // device int32 [n], or null for min_score on every record. d_hoffsets (int64 [n + 1]) is always complete and
+  // exact; a row is stored iff its flat index is < cap, and nothing at or past d_rows + cap is touched (cap == 0
+  // with a null d_rows counts only).
+  void solve_hits_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                         int32_t min_score, const int32_t* d_thresholds, int64_t* d_hoffsets, Result* d_rows,
+                         int64_t cap, hipStream_t stream);
+  // Host form (uploads through the pooled buffers; synchronous; fills stats()). thresholds: host int32 [n] or null.
+  // Optimistic: one pass with room for max(max_rows_hint, 1) rows (hint < 0: 4 n), and exactly one more with
+  // hoffsets[n] rows when that was too few (the counts are exact, so the second pass fits). hits_passes() tells.
+  void solve_hits(const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t min_score,
+                  const int32_t* thresholds, int64_t* hoffsets_out, std::vector<Result>& rows_out,
+                  int64_t max_rows_hint = -1);
+  int hits_passes() const { return hits_passes_; }  // passes of the last solve_hits (1 or 2; 0 for n <= 0)
+  // Device time (ms) of the count + scan + compact launches of the last hits call; as topk_select_ms().
+  double hits_select_ms() { return topk_select_ms(); }
 
   // ---- alignment report (definitions: moc/cpu_engine.hpp report_batch_cpu; kernels:
   // csrc/src/hip/report_kernels.hip): the sign counts and, optionally, the marker bytes of caller-supplied rows.
@@ -236,8 +258,15 @@ class HipEngine {
   void run_staged(const uint8_t* codes, const int64_t* offsets, int64_t n, void* out, ResultFormat fmt,
                   bool packed5);
   void solve_wire_impl(const WireBatch& b, void* out, ResultFormat fmt, bool async);
+  struct HitsCall {  // what run_profile's chunks do instead of a select when the call is for hits
+    int32_t min_score;
+    const int32_t* d_thresholds;
+    int64_t* d_hoffsets;
+    Result* d_rows;
+    int64_t cap;
+  };
   void run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n, int K,
-                   void* d_dst, hipStream_t stream);
+                   void* d_dst, hipStream_t stream, const HitsCall* hits = nullptr);
 
   EngineOptions opt_;
   int device_ = 0;
@@ -275,12 +304,19 @@ class HipEngine {
   size_t h_plan_cap_ = 0;
   hipEvent_t ev_plan_ = nullptr;
   hipEvent_t ev_d0_ = nullptr, ev_d1_ = nullptr;  // around solve_device's launches (device_kernel_ms)
-  // top-K: the chunks' profile scratch, and event pairs around the select launches (MOC_PROFILE_TIMING=1)
+  // top-K / hits: the chunks' profile scratch, and event pairs around the select / hits launches
+  // (MOC_PROFILE_TIMING=1)
   void* d_prof_scratch_ = nullptr;
   size_t d_prof_scratch_cap_ = 0;
   bool profile_timing_ = false;
   std::vector<hipEvent_t> ev_select_;
   size_t ev_select_used_ = 0;
+  // hits: the scan's block sums, the host form's row buffer, and its pass count
+  void* d_hits_sums_ = nullptr;
+  size_t d_hits_sums_cap_ = 0;
+  void* d_hits_rows_ = nullptr;
+  size_t d_hits_rows_cap_ = 0;
+  int hits_passes_ = 0;
   std::vector<void*> pinned_;
   struct DirectKey {
     dev::ProblemView pv;

@@ -108,6 +108,14 @@ constexpr int64_t kReportPackedCountMax = 255;
 static_assert(kReportShortMaxL2 <= kReportPackedCountMax, "report: packed byte counters of the lane-per-row regime");
 inline bool report_short_row(int64_t L2) { return L2 <= kReportShortMaxL2; }
 
+// ---- threshold hits (hits_kernels.hip): the prefix sum over a chunk's per-record hit counts is reduce-then-scan
+// in separate launches: blocks of kHitsScanBlockRecords records are summed, ONE block scans those sums
+// kHitsScanSumsPerPass at a time with a running carry, then every block rescans its records from its sum. A chunk
+// of at most kHitsScanBlockRecords records is one rescan launch from the chunk's base. All of it in int64.
+constexpr int32_t kHitsScanThreads = 256;
+constexpr int32_t kHitsScanBlockRecords = 4 * kHitsScanThreads;  // four consecutive counts per thread
+constexpr int32_t kHitsScanSumsPerPass = 2 * kHitsScanThreads;   // two consecutive sums per thread and pass
+
 // Form bits reported per solve (EngineStats::forms; Python: stats()["forms"]).
 enum FormBits : int32_t {
   kFormSwipeKBits = 1,    // swipe, int16 keys with k bits

@@ -221,6 +221,25 @@ int moc_cpu_topk(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const
   });
 }
 
+int moc_cpu_hits(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes, const int64_t* offsets,
+                 int64_t n, int semantics, int threads, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets,
+                 moc_result* rows, int64_t cap) {
+  return guard([&] {
+    moc::Weights w = weights_of(weights4);
+    moc::RecordBatch b = view_batch(codes, offsets, n);
+    moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
+    moc::ScoreTable t = moc::ScoreTable::build(w);
+    moc::hits_batch_cpu(t, seq1, L1, b, min_score, thresholds, hoffsets, reinterpret_cast<moc::Result*>(rows), cap,
+                        static_cast<moc::Semantics>(semantics), threads);
+  });
+}
+
+int moc_hits_geometry(int32_t* out2) {
+  out2[0] = moc::bounds::kHitsScanBlockRecords;
+  out2[1] = moc::bounds::kHitsScanSumsPerPass;
+  return 0;
+}
+
 int moc_cpu_report(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
                    const int64_t* offsets, int64_t n, int threads, int K, const moc_result* rows, int32_t* counts,
                    uint8_t* marks) {
@@ -512,6 +531,47 @@ int moc_engine_set_profile_scratch(void* e, int64_t bytes) {
 
 int moc_engine_topk_select_ms(void* e, double* ms) {
   return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->topk_select_ms(); });
+}
+
+namespace {
+thread_local std::vector<moc::Result> g_hits_rows;  // moc_engine_solve_hits -> moc_engine_hits_rows
+}
+
+int moc_engine_solve_hits(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t min_score,
+                          const int32_t* thresholds, int64_t max_rows_hint, int64_t* hoffsets, moc_result* rows,
+                          int64_t cap) {
+  return guard([&] {
+    if (cap < 0 || (cap > 0 && !rows)) throw moc::Error("hits: cap rows need a rows buffer");
+    static_cast<moc::HipEngine*>(e)->solve_hits(codes, offsets, n, min_score, thresholds, hoffsets, g_hits_rows,
+                                                max_rows_hint);
+    const size_t m = std::min(g_hits_rows.size(), static_cast<size_t>(cap));
+    if (m) std::memcpy(rows, g_hits_rows.data(), sizeof(moc::Result) * m);
+  });
+}
+
+int moc_engine_hits_rows(moc_result* rows, int64_t cap) {
+  return guard([&] {
+    if (cap < 0 || (cap > 0 && !rows)) throw moc::Error("hits: cap rows need a rows buffer");
+    const size_t m = std::min(g_hits_rows.size(), static_cast<size_t>(cap));
+    if (m) std::memcpy(rows, g_hits_rows.data(), sizeof(moc::Result) * m);
+    std::vector<moc::Result>().swap(g_hits_rows);
+  });
+}
+
+int moc_engine_hits_passes(void* e) { return static_cast<moc::HipEngine*>(e)->hits_passes(); }
+
+int moc_engine_solve_hits_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                 int64_t n, int32_t min_score, const int32_t* d_thresholds, int64_t* d_hoffsets,
+                                 moc_result* d_rows, int64_t cap, void* stream) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_hits_device(d_codes, d_offsets, h_offsets, n, min_score, d_thresholds,
+                                                       d_hoffsets, reinterpret_cast<moc::Result*>(d_rows), cap,
+                                                       static_cast<hipStream_t>(stream));
+  });
+}
+
+int moc_engine_hits_select_ms(void* e, double* ms) {
+  return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->hits_select_ms(); });
 }
 
 int moc_engine_report(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int K, const moc_result* rows,

@@ -257,30 +257,31 @@ void profile_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const
   }
 }
 
-void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
-                    Semantics sem, int num_threads) {
-  if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+namespace {
+// fn(i, prof, C) for every record i with its C-entry profile. One record's profile exists at a time per thread,
+// never the batch's: records in parallel when there are many, else one record at a time with its offset chunks in
+// parallel (fn then runs on the calling thread, in record order).
+template <class Fn>
+void for_each_profile(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, Semantics sem,
+                      int num_threads, Fn&& fn) {
   const int64_t n = batch.size();
   const int nt = threads_for(batch, L1, sem, num_threads > 0 ? num_threads : omp_get_max_threads());
-  if (n >= 4 * nt || nt == 1) {  // one record's profile per thread at a time
+  if (n >= 4 * nt || nt == 1) {
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(1024, n / (64 * nt)));
 #pragma omp parallel num_threads(nt) if (nt > 1)
     {
       std::vector<ProfileEntry> prof;
-      std::vector<uint64_t> keys;
 #pragma omp for schedule(dynamic, chunk)
       for (int64_t i = 0; i < n; ++i) {
         const int64_t C = candidate_offsets(L1, batch.length(i), sem);
         prof.resize(static_cast<size_t>(C));
         profile_range(t, s1, L1, batch.record(i), batch.length(i), 0, C, sem, prof.data());
-        select_topk(prof.data(), C, K, out + i * K, keys);
+        fn(i, prof.data(), C);
       }
     }
     return;
   }
-  // few records: one record's profile at a time, its offset chunks in parallel
   std::vector<ProfileEntry> prof;
-  std::vector<uint64_t> keys;
   std::vector<OffsetItem> items;
   for (int64_t i = 0; i < n; ++i) {
     const int64_t C = candidate_offsets(L1, batch.length(i), sem);
@@ -290,8 +291,44 @@ void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const Re
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nt) if (nt > 1)
     for (int64_t j = 0; j < static_cast<int64_t>(items.size()); ++j)
       profile_range(t, s1, L1, batch.record(i), batch.length(i), items[j].ob, items[j].oe, sem, prof.data());
-    select_topk(prof.data(), C, K, out + i * K, keys);
+    fn(i, prof.data(), C);
   }
+}
+}  // namespace
+
+void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
+                    Semantics sem, int num_threads) {
+  if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
+    thread_local std::vector<uint64_t> keys;
+    select_topk(prof, C, K, out + i * K, keys);
+  });
+}
+
+void hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int32_t min_score,
+                    const int32_t* thresholds, int64_t* hoffsets, Result* rows, int64_t cap, Semantics sem,
+                    int num_threads) {
+  if (cap < 0 || (cap > 0 && !rows)) throw Error("hits: cap rows need a rows buffer (cap = 0 counts only)");
+  const int64_t n = batch.size();
+  auto threshold = [&](int64_t i) { return thresholds ? thresholds[i] : min_score; };
+  // phase 1: counts into hoffsets[i + 1], then their running totals
+  hoffsets[0] = 0;
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
+    const int32_t ti = threshold(i);
+    int64_t c = 0;
+    for (int64_t o = 0; o < C; ++o) c += prof[o].score >= ti ? 1 : 0;
+    hoffsets[i + 1] = c;
+  });
+  for (int64_t i = 0; i < n; ++i) hoffsets[i + 1] += hoffsets[i];
+  if (cap == 0 || hoffsets[n] == 0) return;
+  // phase 2: fill, every row under the capacity contract
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
+    int64_t at = hoffsets[i];
+    if (at >= cap || at == hoffsets[i + 1]) return;
+    const int32_t ti = threshold(i);
+    for (int64_t o = 0; o < C && at < cap; ++o)
+      if (prof[o].score >= ti) rows[at++] = Result{prof[o].score, static_cast<int32_t>(o), prof[o].k};
+  });
 }
 
 Result brute_force_record(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2,

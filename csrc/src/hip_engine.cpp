@@ -110,7 +110,7 @@ int parse_preload_set(const char* s) {
   } names[] = {{"all", kPreloadAll}, {"none", 0}, {"align", kPreloadAlign}, {"short", kPreloadShort},
                {"swipe", kPreloadSwipeByte | kPreloadSwipeP33}, {"swipe8", kPreloadSwipeByte},
                {"swipe33", kPreloadSwipeP33}, {"tile16", kPreloadTile16}, {"mfma", kPreloadMfma},
-               {"profile", kPreloadProfile}, {"report", kPreloadReport}};
+               {"profile", kPreloadProfile}, {"report", kPreloadReport}, {"hits", kPreloadHits}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -218,6 +218,8 @@ HipEngine::~HipEngine() {
   (void)hipFree(d_counter_);
   (void)hipFree(d_plan_);
   (void)hipFree(d_prof_scratch_);
+  (void)hipFree(d_hits_sums_);
+  (void)hipFree(d_hits_rows_);
   for (hipEvent_t e : ev_select_) (void)hipEventDestroy(e);
   (void)hipHostFree(h_plan_);
   (void)hipEventDestroy(ev_plan_);
@@ -989,9 +991,11 @@ double HipEngine::topk_select_ms() {
 }
 
 // K == 0: the whole batch's profile -> d_dst (ProfileEntry, one chunk). K >= 1: top-K rows -> d_dst (Result
-// [n, K]), chunk by chunk through the bounded scratch. Plan buffer: poffsets (n + 1) | every chunk's wave starts.
+// [n, K]), chunk by chunk through the bounded scratch. hits (with K == 0, d_dst unused): the same chunks, each
+// followed by count, prefix sum and compaction into the call's buffers. Plan buffer: poffsets (n + 1) | every
+// chunk's wave starts.
 void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
-                            int K, void* d_dst, hipStream_t stream) {
+                            int K, void* d_dst, hipStream_t stream, const HitsCall* hits) {
   if (!have_problem_) throw Error("HipEngine: profile / top-K before set_problem");
   if (K < 0 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
   finish_wire();
@@ -1000,7 +1004,8 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   if (n <= 0) return;
   if (n >= (int64_t{1} << 31) - 1) throw Error("profile / top-K: more than 2^31 - 2 records in one call");
   if (!stream) stream = s_compute_;
-  TraceRange tr(K ? "moc.solve_topk_device" : "moc.solve_profile_device");
+  TraceRange tr(hits ? "moc.solve_hits_device" : K ? "moc.solve_topk_device" : "moc.solve_profile_device");
+  const bool chunked = K || hits;  // through the bounded scratch
   std::vector<int64_t> poff(static_cast<size_t>(n) + 1);
   profile_offsets(h_offsets, n, poff.data());
   int64_t sum_l2 = 0, max_l2 = 0, cells = 0, max_need = 1;
@@ -1015,7 +1020,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
     throw Error("Seq1 / Seq2 lengths beyond 2^30 exceed the device engine's offset range");
   // sub-tiles per wave tile, as the LUT tile kernel picks them, narrowed to the batch's widest offset range
   const int u = plan::profile_u(cfg_, sum_l2, n, max_need);
-  // chunks of consecutive records: the whole batch for a profile, bounded scratch for top-K
+  // chunks of consecutive records: the whole batch for a profile, bounded scratch for top-K and hits
   struct Chunk {
     int64_t r0, r1;
     size_t starts_at, n_starts;
@@ -1024,7 +1029,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   const int64_t cap_entries = std::max<int64_t>(1, opt_.profile_scratch_bytes / static_cast<int64_t>(sizeof(ProfileEntry)));
   for (int64_t r0 = 0; r0 < n;) {
     int64_t r1 = r0 + 1;
-    if (K == 0)
+    if (!chunked)
       r1 = n;
     else
       while (r1 < n && poff[r1 + 1] - poff[r0] <= cap_entries) ++r1;
@@ -1032,20 +1037,24 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
     r0 = r1;
   }
   std::vector<dev::WaveStart> starts;
-  int64_t max_entries = 0;
+  int64_t max_entries = 0, max_records = 0;
   for (Chunk& c : chunks) {
     const std::vector<dev::WaveStart> runs = plan::profile_runs(cfg_, h_offsets + c.r0, c.r1 - c.r0, u);
     c.starts_at = starts.size();
     c.n_starts = runs.size();
     starts.insert(starts.end(), runs.begin(), runs.end());
     max_entries = std::max(max_entries, poff[c.r1] - poff[c.r0]);
+    max_records = std::max(max_records, c.r1 - c.r0);
   }
   const size_t poff_bytes = sizeof(int64_t) * poff.size();
   const size_t plan_bytes = poff_bytes + sizeof(dev::WaveStart) * starts.size();
   MOC_HIP_CHECK(hipEventSynchronize(ev_plan_));  // previous call's plan buffers are free again
   ensure(d_plan_, d_plan_cap_, plan_bytes);
   ensure_host(h_plan_, h_plan_cap_, plan_bytes);
-  if (K) ensure(d_prof_scratch_, d_prof_scratch_cap_, sizeof(ProfileEntry) * static_cast<size_t>(std::max<int64_t>(max_entries, 1)));
+  if (chunked) ensure(d_prof_scratch_, d_prof_scratch_cap_, sizeof(ProfileEntry) * static_cast<size_t>(std::max<int64_t>(max_entries, 1)));
+  if (hits)
+    ensure(d_hits_sums_, d_hits_sums_cap_,
+           sizeof(int64_t) * static_cast<size_t>((max_records + bounds::kHitsScanBlockRecords - 1) / bounds::kHitsScanBlockRecords));
   std::memcpy(h_plan_, poff.data(), poff_bytes);
   std::memcpy(static_cast<char*>(h_plan_) + poff_bytes, starts.data(), sizeof(dev::WaveStart) * starts.size());
   upload_staged(d_plan_, h_plan_, plan_bytes, stream);
@@ -1054,7 +1063,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   pv.mfma_sweep = 0;
   const dev::BatchView bv{d_codes + h_offsets[0], d_offsets, n};
   ensure_device_events();
-  if (K && profile_timing_)
+  if (chunked && profile_timing_)
     while (ev_select_.size() < 2 * chunks.size()) {
       hipEvent_t e = nullptr;
       MOC_HIP_CHECK(hipEventCreate(&e));
@@ -1068,13 +1077,30 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
     pa.u = u;
     pa.rec0 = c.r0;
     pa.poffsets = static_cast<const int64_t*>(d_plan_);
-    pa.base = K ? poff[c.r0] : 0;
-    pa.prof = K ? static_cast<ProfileEntry*>(d_prof_scratch_) : static_cast<ProfileEntry*>(d_dst);
-    pa.prof_entries = K ? poff[c.r1] - poff[c.r0] : poff[n];
+    pa.base = chunked ? poff[c.r0] : 0;
+    pa.prof = chunked ? static_cast<ProfileEntry*>(d_prof_scratch_) : static_cast<ProfileEntry*>(d_dst);
+    pa.prof_entries = chunked ? poff[c.r1] - poff[c.r0] : poff[n];
     dev::launch_offset_profile(pv, bv, pa, stream);
-    if (K) {
+    if (chunked) {
       if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
-      dev::launch_topk_select(pa, c.r1 - c.r0, K, static_cast<Result*>(d_dst), stream);
+      if (hits) {
+        dev::HitsArgs ha;
+        ha.prof = pa.prof;
+        ha.poffsets = pa.poffsets;
+        ha.base = pa.base;
+        ha.prof_entries = pa.prof_entries;
+        ha.rec0 = c.r0;
+        ha.n_rec = c.r1 - c.r0;
+        ha.thresholds = hits->d_thresholds;
+        ha.min_score = hits->min_score;
+        ha.hoffsets = hits->d_hoffsets;
+        ha.sums = static_cast<int64_t*>(d_hits_sums_);
+        ha.rows = hits->d_rows;
+        ha.cap = hits->cap;
+        dev::launch_hits(ha, stream);
+      } else {
+        dev::launch_topk_select(pa, c.r1 - c.r0, K, static_cast<Result*>(d_dst), stream);
+      }
       if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
     }
   }
@@ -1085,7 +1111,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   stats_.cells = cells;
   stats_.records = n;
   stats_.chunks = static_cast<int64_t>(chunks.size());
-  stats_.kernels = 16;
+  stats_.kernels = hits ? 16 | 64 : 16;
 }
 
 void HipEngine::solve_profile_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
@@ -1132,6 +1158,68 @@ void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t
   copy_d2h(out, s.d_out, obytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
   host_call_stats(wall, device_kernel_ms(), rebased[n], n, obytes);
+}
+
+// ---- threshold hits -------------------------------------------------------------------------------------
+void HipEngine::solve_hits_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                                  int32_t min_score, const int32_t* d_thresholds, int64_t* d_hoffsets, Result* d_rows,
+                                  int64_t cap, hipStream_t stream) {
+  if (!have_problem_) throw Error("HipEngine: hits before set_problem");
+  if (cap < 0 || (cap > 0 && !d_rows)) throw Error("hits: cap rows need a rows buffer (cap = 0 counts only)");
+  if (!d_hoffsets) throw Error("hits: no hoffsets buffer");
+  if (n <= 0) {  // no launch: the index of an empty batch is its single 0
+    finish_wire();
+    MOC_HIP_CHECK(hipSetDevice(device_));
+    MOC_HIP_CHECK(hipMemsetAsync(d_hoffsets, 0, sizeof(int64_t), stream ? stream : s_compute_));
+    ev_select_used_ = 0;
+    return;
+  }
+  const HitsCall hc{min_score, d_thresholds, d_hoffsets, d_rows, d_rows ? cap : 0};
+  run_profile(d_codes, d_offsets, h_offsets, n, 0, nullptr, stream, &hc);
+}
+
+void HipEngine::solve_hits(const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t min_score,
+                           const int32_t* thresholds, int64_t* hoffsets_out, std::vector<Result>& rows_out,
+                           int64_t max_rows_hint) {
+  if (!have_problem_) throw Error("HipEngine: hits before set_problem");
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  rows_out.clear();
+  hits_passes_ = 0;
+  hoffsets_out[0] = 0;
+  if (n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  Slot& s = *slots_[0];
+  // d_out: hoffsets (n + 1) | thresholds (n); the rows have a buffer of their own, which the second pass may grow
+  const size_t hbytes = sizeof(int64_t) * static_cast<size_t>(n + 1), tbytes = sizeof(int32_t) * static_cast<size_t>(n);
+  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, hbytes + tbytes);
+  char* d = static_cast<char*>(s.d_out);
+  if (thresholds) copy_h2d(d + hbytes, thresholds, tbytes, s_compute_);
+  int64_t cap = std::max<int64_t>(max_rows_hint < 0 ? 4 * n : max_rows_hint, 1);
+  double kernel_ms = 0;
+  for (;;) {
+    ensure(d_hits_rows_, d_hits_rows_cap_, sizeof(Result) * static_cast<size_t>(cap));
+    solve_hits_device(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(),
+                      n, min_score, thresholds ? reinterpret_cast<const int32_t*>(d + hbytes) : nullptr,
+                      reinterpret_cast<int64_t*>(d), static_cast<Result*>(d_hits_rows_), cap, s_compute_);
+    copy_d2h(hoffsets_out, d, hbytes, s_compute_);
+    MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+    kernel_ms += device_kernel_ms();
+    ++hits_passes_;
+    if (hoffsets_out[n] <= cap || hits_passes_ == 2) break;
+    cap = hoffsets_out[n];  // exact: the second pass fits
+  }
+  const int64_t total = hoffsets_out[n];
+  if (total > cap) throw Error("hits: the second pass did not fit its own count");
+  rows_out.resize(static_cast<size_t>(total));
+  const size_t rbytes = sizeof(Result) * static_cast<size_t>(total);
+  if (rbytes) {
+    copy_d2h(rows_out.data(), d_hits_rows_, rbytes, s_compute_);
+    MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+  }
+  host_call_stats(wall, kernel_ms, rebased[n], n, hbytes * static_cast<size_t>(hits_passes_) + rbytes);
+  if (thresholds) stats_.h2d_bytes += static_cast<int64_t>(tbytes);
 }
 
 // ---- alignment report -----------------------------------------------------------------------------------

@@ -7,11 +7,12 @@ window. See README.md and SURVEY.md.
 """
 from .models.problem import Problem
 from .models.scoring import PairClass, Semantics, Weights
-from .ops.align import (PROFILE_DTYPE, HipSearchEngine, align_profile_device, align_report_device, align_search,
-                        align_search_device, align_topk_device, brute_force_native, decode_keys, device_count,
-                        profile_offsets, report_scores, search_cpu, search_hip, search_keys_cpu, search_profile_cpu,
-                        search_report_cpu, search_topk_cpu)
-from .utils.io import format_report, format_results, format_topk, write_results
+from .ops.align import (PROFILE_DTYPE, HipSearchEngine, align_hits_device, align_profile_device,
+                        align_report_device, align_search, align_search_device, align_topk_device,
+                        brute_force_native, decode_keys, device_count, profile_offsets, report_scores, search_cpu,
+                        search_hip, search_hits_cpu, search_keys_cpu, search_profile_cpu, search_report_cpu,
+                        search_topk_cpu)
+from .utils.io import format_hits, format_report, format_results, format_topk, write_results
 from .utils.synthetic import make_synthetic
 
 __version__ = "0.1.0"
@@ -21,4 +22,5 @@ __all__ = [
     "make_synthetic", "search_keys_cpu", "decode_keys", "PROFILE_DTYPE", "profile_offsets", "search_profile_cpu",
     "search_topk_cpu", "align_profile_device", "align_topk_device", "format_topk",
     "search_report_cpu", "report_scores", "align_report_device", "format_report",
+    "search_hits_cpu", "align_hits_device", "format_hits",
 ]

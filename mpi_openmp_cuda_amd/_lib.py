@@ -83,6 +83,16 @@ def _decl(lib):
         "moc_engine_report": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
         "moc_engine_report_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                                              c_void_p, c_void_p]),
+        "moc_cpu_hits": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int32,
+                                 c_void_p, c_void_p, c_void_p, c_int64]),
+        "moc_hits_geometry": (c_int, [c_void_p]),
+        "moc_engine_solve_hits": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p,
+                                          c_void_p, c_int64]),
+        "moc_engine_hits_rows": (c_int, [c_void_p, c_int64]),
+        "moc_engine_hits_passes": (c_int, [c_void_p]),
+        "moc_engine_solve_hits_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                                 c_void_p, c_void_p, c_int64, c_void_p]),
+        "moc_engine_hits_select_ms": (c_int, [c_void_p, c_void_p]),
         "moc_partition": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_double, c_void_p]),
         "moc_device_count": (c_int, []),
         "moc_host_register": (c_int, [c_void_p, c_size_t]),

@@ -16,7 +16,7 @@ from .models.problem import Problem
 from .models.scoring import Semantics
 from .parallel import dist as D
 from .parallel.search import DistributedSearch
-from .utils.io import format_report, format_topk, write_results
+from .utils.io import format_hits, format_report, format_topk, write_results
 
 
 def main(argv=None) -> int:
@@ -43,9 +43,23 @@ def main(argv=None) -> int:
                     help="after every result line print the alignment it stands for: the sign counts, the piece of "
                          "Seq1, the marker line and the record with its hyphen. With --top K or without; record "
                          "slices on one node only (--partition records)")
+    hits = ap.add_mutually_exclusive_group()
+    hits.add_argument("--min-score", type=int, default=None, metavar="T",
+                      help="after every result line print that record's threshold hits, every offset whose best "
+                           "candidate scores at least T, as '  hit: score: S, n: N, k: K' in ascending n. Not with "
+                           "--top K > 1 or --show-alignment; record slices on one node only (--partition records)")
+    hits.add_argument("--within", type=int, default=None, metavar="D",
+                      help="the same for every offset within D >= 0 of the record's own best score")
     a = ap.parse_args(argv)
     if not 1 <= a.top <= 64:
         ap.error("--top K: K must be in 1..64")
+    want_hits = a.min_score is not None or a.within is not None
+    if want_hits and (a.top > 1 or a.show_alignment):
+        ap.error("--min-score / --within do not combine with --top K > 1 or --show-alignment")
+    if a.within is not None and a.within < 0:
+        ap.error("--within D: D must be >= 0")
+    if a.min_score is not None and not -2 ** 31 <= a.min_score < 2 ** 31:
+        ap.error("--min-score T: T must be an int32")
 
     from .ops.align import device_count
 
@@ -82,7 +96,17 @@ def main(argv=None) -> int:
                   "combines one packed key per record", file=sys.stderr)
         D.finalize(ctx)
         return 2
-    if a.top > 1:
+    if want_hits and search.partition != "records":
+        if ctx.is_root:
+            print("--min-score / --within need record slices (--partition records, one node); --partition offsets "
+                  "combines one packed key per record", file=sys.stderr)
+        D.finalize(ctx)
+        return 2
+    hit_rows = None
+    if want_hits:
+        got = search.run_hits(problem, a.min_score, a.within, Semantics.parse(a.semantics))
+        results, hit_rows = (got[0], got[1:]) if ctx.is_root else (None, None)
+    elif a.top > 1:
         results = search.run_topk(problem, a.top, Semantics.parse(a.semantics))
     else:
         results = search.run(problem, Semantics.parse(a.semantics))
@@ -96,6 +120,9 @@ def main(argv=None) -> int:
             sys.stdout.flush()
         elif a.top > 1:
             sys.stdout.write(format_topk(results))
+            sys.stdout.flush()
+        elif want_hits:
+            sys.stdout.write(format_hits(results, *hit_rows))
             sys.stdout.flush()
         else:
             write_results(results)

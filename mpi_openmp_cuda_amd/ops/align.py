@@ -140,6 +140,77 @@ def search_topk_cpu(problem: Problem, K: int, semantics=Semantics.REFERENCE, thr
     return out
 
 
+# ---- threshold hits: every offset that scores at least a threshold (csrc/include/moc/cpu_engine.hpp)
+_I32 = np.iinfo(np.int32)
+
+
+def hits_geometry() -> tuple:
+    """(records per scan block, block sums per pass of the single scanning block) of the GPU's prefix sum over hit
+    counts (csrc/include/moc/kernel_bounds.hpp); no GPU needed."""
+    g = np.zeros(2, np.int32)
+    _lib.check(_lib.lib().moc_hits_geometry(_lib.ptr(g)))
+    return int(g[0]), int(g[1])
+
+
+def within_thresholds(best_scores, within) -> np.ndarray:
+    """int32 thresholds "within D of the record's best": best − D, subtracted in int64 and clipped to int32."""
+    d = int(within)
+    if d < 0:
+        raise ValueError(f"hits: within must be >= 0, got {d}")
+    t = np.asarray(best_scores).astype(np.int64).reshape(-1) - d
+    return np.clip(t, _I32.min, _I32.max).astype(np.int32)
+
+
+def _hits_thresholds(n: int, min_score, thresholds, within, best_scores):
+    """Checks that exactly one of the three is given -> (scalar int, int32 [n] array or None). ``best_scores``:
+    a call returning the records' best scores (``within`` only)."""
+    given = [x is not None for x in (min_score, thresholds, within)]
+    if sum(given) != 1:
+        raise ValueError("hits: give exactly one of min_score, thresholds, within")
+    if min_score is not None:
+        m = int(min_score)
+        if not _I32.min <= m <= _I32.max:
+            raise ValueError(f"hits: min_score {m} is not an int32")
+        return m, None
+    if thresholds is not None:
+        t = np.asarray(thresholds)
+        if t.ndim != 1 or t.shape[0] != n or not np.issubdtype(t.dtype, np.integer):
+            raise ValueError(f"hits: thresholds must be {n} integers (one per record), got shape {t.shape}")
+        if t.size and (t.min() < _I32.min or t.max() > _I32.max):
+            raise ValueError("hits: thresholds must fit int32")
+        return 0, np.ascontiguousarray(t, dtype=np.int32)
+    if int(within) < 0:
+        raise ValueError(f"hits: within must be >= 0, got {int(within)}")
+    return 0, within_thresholds(best_scores(), within)
+
+
+def search_hits_cpu(problem: Problem, min_score=None, thresholds=None, within=None, semantics=Semantics.REFERENCE,
+                    threads: int = 0):
+    """Threshold hits on the CPU engine: ``(rows, hoffsets)``. Record i's hits are the offsets o whose profile score
+    (:func:`search_profile_cpu`) is >= its threshold (inclusive), ascending in o, as int32 rows (score, n = o, k of
+    that profile entry) at ``rows[hoffsets[i]:hoffsets[i + 1]]``; ``hoffsets`` is int64 [n + 1] and
+    ``hoffsets[-1]`` the total H. Exactly one of ``min_score`` (one int32 for the batch; INT32_MIN selects the whole
+    profile), ``thresholds`` (int32 [n]) and ``within`` (D >= 0: every offset within D of the record's best score,
+    from a search on the same engine) must be given."""
+    sem = Semantics.parse(semantics)
+    m, t = _hits_thresholds(problem.n, min_score, thresholds, within,
+                            lambda: search_cpu(problem, sem, threads)["score"])
+    hoffsets = np.zeros(problem.n + 1, np.int64)
+
+    def call(rows, cap):
+        _lib.check(_lib.lib().moc_cpu_hits(
+            _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+            _lib.ptr(problem.offsets), problem.n, int(sem), int(threads), m, _lib.ptr(t), _lib.ptr(hoffsets),
+            _lib.ptr(rows), cap))
+
+    call(None, 0)  # counts
+    total = int(hoffsets[-1])
+    rows = np.zeros((total, 3), np.int32)
+    if total:
+        call(rows, total)
+    return rows, hoffsets
+
+
 # ---- alignment report: sign counts and marker bytes of result rows (csrc/include/moc/cpu_engine.hpp)
 REPORT_EMPTY = int(np.iinfo(np.int64).min)        # report_scores of an empty row (score INT32_MIN, top-K padding)
 REPORT_INVALID = int(np.iinfo(np.int64).min) + 1  # ... of a row whose (n, k) does not place the record in Seq1
@@ -501,6 +572,91 @@ class HipSearchEngine:
         _lib.check(_lib.lib().moc_engine_topk_select_ms(self._h, ctypes.addressof(ms)))
         return float(ms.value)
 
+    # ---- threshold hits (byte letters, dense offsets; csrc/src/hip/hits_kernels.hip)
+    def solve_hits(self, codes: np.ndarray, offsets: np.ndarray, min_score=None, thresholds=None, within=None,
+                   max_rows: Optional[int] = None):
+        """Host CSR -> ``(rows, hoffsets)`` as :func:`search_hits_cpu` returns them (exactly one of ``min_score``,
+        ``thresholds``, ``within``), through the chunks of :meth:`solve_topk` with count, prefix sum and compaction
+        kernels behind each chunk's profile. Optimistic: one pass with room for ``max_rows`` rows (default 4 n) and
+        exactly one more when more offsets qualify (:meth:`hits_passes`). Synchronous."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        m, t = _hits_thresholds(n, min_score, thresholds, within, lambda: self.solve(codes, offsets)["score"])
+        hoffsets = np.zeros(n + 1, np.int64)
+        _lib.check(_lib.lib().moc_engine_solve_hits(self._h, _lib.ptr(codes), _lib.ptr(offsets), n, m, _lib.ptr(t),
+                                                    -1 if max_rows is None else int(max_rows), _lib.ptr(hoffsets),
+                                                    None, 0))
+        total = int(hoffsets[-1])
+        rows = np.zeros((total, 3), np.int32)
+        _lib.check(_lib.lib().moc_engine_hits_rows(_lib.ptr(rows) if total else None, total))
+        return rows, hoffsets
+
+    def hits_passes(self) -> int:
+        """Passes the last :meth:`solve_hits` took: 1, or 2 when its first capacity was too small."""
+        return int(_lib.lib().moc_engine_hits_passes(self._h))
+
+    def hits_select_ms(self) -> float:
+        """Device time (ms) of the count, scan and compact launches of the last hits call; 0 unless the engine was
+        created with MOC_PROFILE_TIMING=1 in the environment. Waits for them."""
+        ms = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().moc_engine_hits_select_ms(self._h, ctypes.addressof(ms)))
+        return float(ms.value)
+
+    def solve_hits_device(self, codes_t, offsets_t, h_offsets: np.ndarray, min_score=None, thresholds_t=None,
+                          within=None, cap: Optional[int] = None, rows_t=None, hoffsets_t=None, stream=None):
+        """Device-resident batch (as :meth:`solve_device`) -> ``(rows_t, hoffsets_t)``: ``hoffsets_t`` an int64
+        [n + 1] tensor, always complete and exact; ``rows_t`` an int32 [cap, 3] tensor (``cap`` default 4 n) of
+        which the rows with a flat index < cap are written and nothing else is touched — compare
+        ``hoffsets_t[-1]`` with ``cap`` after a sync. ``cap = 0`` counts only. Exactly one of ``min_score``,
+        ``thresholds_t`` (an int32 [n] tensor on the same device, e.g. built from a search's scores) and ``within``
+        (a search queued on the same stream first). Both tensors are allocated when None. Queued on ``stream``
+        (default: the current stream); returns immediately."""
+        import torch
+
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        n = h_offsets.shape[0] - 1
+        if sum(x is not None for x in (min_score, thresholds_t, within)) != 1:
+            raise ValueError("hits: give exactly one of min_score, thresholds, within")
+        assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        if within is not None:
+            d = int(within)
+            if d < 0:
+                raise ValueError(f"hits: within must be >= 0, got {d}")
+            best = torch.empty((n, 3), dtype=torch.int32, device=codes_t.device)
+            self.solve_device(codes_t, offsets_t, h_offsets, best, stream)
+            with torch.cuda.stream(stream):
+                thresholds_t = (best[:, 0].to(torch.int64) - d).clamp(_I32.min, _I32.max).to(torch.int32).contiguous()
+        m = 0
+        if min_score is not None:
+            m = int(min_score)
+            if not _I32.min <= m <= _I32.max:
+                raise ValueError(f"hits: min_score {m} is not an int32")
+        if thresholds_t is not None:
+            if thresholds_t.dtype != torch.int32 or tuple(thresholds_t.shape) != (n,):
+                raise ValueError(f"hits: thresholds must be an int32 tensor of {n} entries (one per record)")
+            assert thresholds_t.is_contiguous() and thresholds_t.device == codes_t.device
+        if cap is None:
+            cap = max(4 * n, 1) if rows_t is None else rows_t.shape[0]
+        cap = int(cap)
+        if cap < 0:
+            raise ValueError("hits: cap must be >= 0")
+        if rows_t is None:
+            rows_t = torch.empty((cap, 3), dtype=torch.int32, device=codes_t.device)
+        if hoffsets_t is None:
+            hoffsets_t = torch.empty(n + 1, dtype=torch.int64, device=codes_t.device)
+        assert rows_t.dtype == torch.int32 and rows_t.is_contiguous() and rows_t.dim() == 2 and rows_t.shape[1] == 3
+        assert rows_t.shape[0] >= cap
+        assert hoffsets_t.dtype == torch.int64 and hoffsets_t.is_contiguous() and hoffsets_t.numel() == n + 1
+        _lib.check(_lib.lib().moc_engine_solve_hits_device(
+            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
+            n, m, ctypes.c_void_p(thresholds_t.data_ptr()) if thresholds_t is not None else None,
+            ctypes.c_void_p(hoffsets_t.data_ptr()), ctypes.c_void_p(rows_t.data_ptr()) if cap else None, cap,
+            ctypes.c_void_p(stream.cuda_stream)))
+        return rows_t, hoffsets_t
+
     # ---- alignment report (byte letters, dense offsets; csrc/src/hip/report_kernels.hip)
     def report(self, codes: np.ndarray, offsets: np.ndarray, rows, marks: bool = False):
         """Host CSR + result rows ([n, 3] or [n, K, 3]) -> the counts (and marker bytes) :func:`search_report_cpu`
@@ -567,7 +723,7 @@ class HipSearchEngine:
         d["r2"] = tuple(int(x) for x in list(v)[10:13])
         d["format"] = _lib.FORMAT_NAMES[int(d["format"])]
         d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16"), (16, "profile"),
-                                             (32, "report")) if int(d["kernels"]) & b]
+                                             (32, "report"), (64, "hits")) if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
 
@@ -635,6 +791,14 @@ def align_topk_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, K:
     out = torch.empty((n, _check_k(K), 3), dtype=torch.int32, device=codes_t.device)
     engine.solve_topk_device(codes_t, offsets_t, h_offsets, K, out, stream)
     return out
+
+
+def align_hits_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, min_score=None, thresholds_t=None,
+                      within=None, cap: Optional[int] = None, stream=None):
+    """torch-facing op: threshold hits as ``(rows_t, hoffsets_t)`` on the codes' device — int32 [cap, 3] rows
+    (score, n, k) and the int64 [n + 1] index; see :meth:`HipSearchEngine.solve_hits_device`."""
+    return engine.solve_hits_device(codes_t, offsets_t, h_offsets, min_score, thresholds_t, within, cap, None, None,
+                                    stream)
 
 
 def align_report_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, rows_t, marks: bool = False,

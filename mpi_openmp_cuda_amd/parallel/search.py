@@ -28,7 +28,8 @@ from .. import _lib
 from ..models.problem import Problem
 from ..models.scoring import Semantics
 from ..ops.align import (HipSearchEngine, decode_keys, device_count, keys_to_ordered_int64, ordered_int64_to_keys,
-                        search_cpu, search_keys_cpu, search_report_cpu, search_topk_cpu)
+                        search_cpu, search_hits_cpu, search_keys_cpu, search_report_cpu, search_topk_cpu,
+                        within_thresholds)
 from ..utils.timer import PhaseTimer
 from . import dist as D
 from .partition import CPU_COST, GPU_COST, partition
@@ -181,6 +182,60 @@ class DistributedSearch:
             D.barrier(ctx)
             win.close(unlink=ctx.is_root)
         return rows.astype(np.int32) if ctx.is_root else None
+
+    def run_hits(self, problem: Optional[Problem], min_score=None, within=None, semantics=Semantics.REFERENCE):
+        """Threshold hits (ops.align.search_hits_cpu's ``(rows, hoffsets)``; exactly one of ``min_score`` and
+        ``within``, the same on every rank) together with the search's own rows, for the ``records`` partition:
+        every rank computes its cost-balanced slice of the node-shared input window; the root collects the counts and then the rows, each
+        with one MAX all-reduce of an int64 array that a rank fills only in its own slice, INT64_MIN elsewhere (no
+        new transport). Returns ``(results, rows, hoffsets)`` on the root, else None. One node; byte letters
+        through the engines' hits calls."""
+        if self.partition != "records":
+            raise ValueError("hits run on record slices (--partition records, one node): the offsets partition "
+                             "combines one packed key per record and cannot carry a list of rows")
+        if (min_score is None) == (within is None):
+            raise ValueError("hits: give exactly one of min_score, within")
+        if within is not None and int(within) < 0:
+            raise ValueError(f"hits: within must be >= 0, got {int(within)}")
+        ctx, T = self.ctx, self.timer
+        with T.phase("bcast"):
+            prob, sem, n, total, bounds = self._setup(problem, semantics)
+        b, e = int(bounds[ctx.rank]), int(bounds[ctx.rank + 1])
+        with T.phase("distribute"):
+            win = self._open_window(problem, n, total)
+        lo = np.iinfo(np.int64).min
+
+        def kw(scores):  # the slice's thresholds from the search just done: no second search for `within`
+            return {"min_score": int(min_score)} if min_score is not None else \
+                {"thresholds": within_thresholds(scores, within)}
+
+        with T.phase("compute"):
+            best = np.full((n, 3), lo, np.int64)
+            counts = np.full(n, lo, np.int64)
+            mine = np.zeros((0, 3), np.int32)
+            if e > b:
+                offsets = np.asarray(win.offsets[b:e + 1])
+                if self.engine is not None:
+                    codes = np.asarray(win.codes)
+                    best[b:e] = self.engine.solve(codes, offsets).view(np.int32).reshape(-1, 3)
+                    mine, h = self.engine.solve_hits(codes, offsets, **kw(best[b:e, 0]))
+                else:
+                    sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
+                                  offsets - offsets[0])
+                    best[b:e] = search_cpu(sub, sem, self.threads).view(np.int32).reshape(-1, 3)
+                    mine, h = search_hits_cpu(sub, semantics=sem, threads=self.threads, **kw(best[b:e, 0]))
+                counts[b:e] = np.diff(h)
+        with T.phase("gather"):
+            counts = D.allreduce_max_int64(ctx, counts)
+            best = D.allreduce_max_int64(ctx, best.reshape(-1)).reshape(n, 3)
+            hoffsets = np.zeros(n + 1, np.int64)
+            np.cumsum(counts, out=hoffsets[1:])
+            rows = np.full((int(hoffsets[-1]), 3), lo, np.int64)
+            rows[hoffsets[b]:hoffsets[e]] = mine
+            rows = D.allreduce_max_int64(ctx, rows.reshape(-1)).reshape(-1, 3)
+            D.barrier(ctx)
+            win.close(unlink=ctx.is_root)
+        return (best.astype(np.int32), rows.astype(np.int32), hoffsets) if ctx.is_root else None
 
     def report(self, problem: Problem, rows: np.ndarray):
         """Root only: ``(counts, marks)`` of the search's rows (ops.align.search_report_cpu's outputs, with the

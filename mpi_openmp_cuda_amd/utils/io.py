@@ -50,6 +50,25 @@ def format_topk(topk, first_index: int = 0) -> str:
     return "".join(out)
 
 
+def format_hits(results, rows, hoffsets, first_index: int = 0) -> str:
+    """Results with their threshold hits: record i's line as :func:`format_results` prints it, then one line per
+    hit (``rows[hoffsets[i]:hoffsets[i + 1]]`` from the hits calls), indented by two spaces:
+    "  hit: score: S, n: N, k: K"."""
+    from ..ops.align import as_triples
+
+    res = np.asarray(as_triples(results), dtype=np.int64)
+    r = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+    h = np.asarray(hoffsets, dtype=np.int64).reshape(-1)
+    if h.shape[0] != res.shape[0] + 1 or (h.size and (h[0] != 0 or h[-1] != r.shape[0])) or np.any(np.diff(h) < 0):
+        raise ValueError("format_hits needs hoffsets [n + 1] that index the rows of the results' n records")
+    out = []
+    for i, (s, n, k) in enumerate(res):
+        out.append(f"#{i + first_index}: score: {s}, n: {n}, k: {k}\n")
+        for hs, hn, hk in r[h[i]:h[i + 1]]:
+            out.append(f"  hit: score: {hs}, n: {hn}, k: {hk}\n")
+    return "".join(out)
+
+
 def format_report(problem, rows, counts, marks, first_index: int = 0) -> str:
     """Results with their alignments. ``rows`` [n, 3] print as :func:`format_results` does and [n, K, 3] as
     :func:`format_topk` does; after the line of every real row — not an empty one (score INT32_MIN), nor one
