@@ -206,6 +206,42 @@ int moc_engine_solve_hits_device(void* e, const uint8_t* d_codes, const int64_t*
                                  moc_result* d_rows, int64_t cap, void* stream);
 /* device time (ms) of the last hits call's count + scan + compact launches (MOC_PROFILE_TIMING=1; else 0) */
 int moc_engine_hits_select_ms(void* e, double* ms);
+/* ---- wire-format batches (moc/wire.hpp) ----
+ * One batch in the wire formats: letters as P33 fields (packed 3), 5-bit packed (1) or bytes (0), record i at letter
+ * offsets[i]; offsets dense (off_shift 0, n + 1 entries) or sparse (one per 2^off_shift records and the batch end;
+ * lengths required); lengths NULL or narrow (len_bits 8 / 4 / 3, or 6 = base-6 octets, value + len_base). device 1:
+ * every pointer is device memory of the engine's GPU. */
+typedef struct moc_wire_batch {
+  const uint8_t* letters;
+  const int64_t* offsets;
+  const uint8_t* lengths;
+  int64_t n;
+  int64_t len_base;
+  int32_t packed;
+  int32_t off_shift;
+  int32_t len_bits;
+  int32_t device;
+} moc_wire_batch;
+/* Host reference decode (moc::decode_wire_cpu): sizes2 = {bytes of codes_out, bytes of offsets_out}; with
+ * codes_out and offsets_out NULL only the sizes are computed. codes_out: one byte per letter of
+ * [offsets[0], end); offsets_out: n + 1 absolute dense offsets. An inconsistent batch is an error. */
+int moc_cpu_decode_wire(const moc_wire_batch* b, uint8_t* codes_out, int64_t* offsets_out, int64_t* sizes2);
+/* The decode on the GPU (moc::HipEngine::decode_wire_device), queued on `stream` without a sync into buffers of the
+ * engine that stay valid until its next decode. host_meta: for a device-resident batch, the same batch with host
+ * copies of its offsets and lengths (letters unused); NULL for a host batch. out3: the device addresses of the
+ * letters' base (record i at base + offsets[i]) and of the n + 1 dense offsets, and the letter count.
+ * h_offsets_out: n + 1 entries, the host copy of the dense offsets. d_codes_dst / d_offsets_dst: NULL, or device
+ * buffers of the caller (letter count bytes / n + 1 entries) that receive the decode instead of the engine's. */
+int moc_engine_decode_wire_device(void* e, const moc_wire_batch* b, const moc_wire_batch* host_meta, void* stream,
+                                  uint64_t* out3, int64_t* h_offsets_out, uint8_t* d_codes_dst, int64_t* d_offsets_dst);
+/* Profile, top-K, hits and report of a host wire batch: the decode above, then moc_engine_solve_profile /
+ * _solve_topk / _solve_hits / _report on the decoded buffers, with their arguments and contracts. Synchronous. */
+int moc_engine_solve_profile_wire(void* e, const moc_wire_batch* b, int64_t* poffsets, moc_profile_entry* prof);
+int moc_engine_solve_topk_wire(void* e, const moc_wire_batch* b, int K, moc_result* out);
+int moc_engine_solve_hits_wire(void* e, const moc_wire_batch* b, int32_t min_score, const int32_t* thresholds,
+                               int64_t max_rows_hint, int64_t* hoffsets, moc_result* rows, int64_t cap);
+int moc_engine_report_wire(void* e, const moc_wire_batch* b, int K, const moc_result* rows, int32_t* counts,
+                           uint8_t* marks);
 /* stats: kernel_ms, total_ms, h2d_bytes, d2h_bytes, chunks, cells, records, direct, format, kernels,
  * r2 smin, r2 kw, r2 j, forms (moc::bounds::FormBits of the last solve) */
 int moc_engine_stats(void* e, double* out14);

@@ -197,6 +197,33 @@ bool kernel_copy_fits(const void* dst, const void* src, size_t bytes);
 // Unpacks n chars of a 5-bit packed stream (device memory) starting at bit `bit0` into byte codes.
 void launch_unpack5(const uint8_t* packed, int64_t bit0, int64_t n, uint8_t* out, hipStream_t stream);
 
+// ---- wire-format decode (wire_kernels.hip; host reference: moc::decode_wire_cpu) ------------------------
+// Every source pointer is device memory or page-locked host memory given by its device address (read in place).
+// Narrow lengths + sparse offsets -> dense[0..n] (absolute). Wave w owns records [64w, 64w + 64): its base is
+// sparse[(64w) >> shift] (64 is a multiple of 2^shift), a wave scan of the lanes' lengths gives the rest, and the
+// last wave also stores dense[n] = sparse[sparse_count(n, shift) - 1]. No cross-block dependency.
+struct WireOffsetsArgs {
+  const int64_t* sparse = nullptr;  // sparse_count(n, shift) entries
+  int32_t shift = 0;                // 0..6
+  int32_t bits = 8;                 // 8, 4, 3 or kLenBase6
+  const uint8_t* lengths = nullptr; // narrow_lengths_bytes(n, bits) bytes; base-6: 8-byte aligned
+  int64_t base = 0;
+  int64_t n = 0;
+  int64_t* dense = nullptr;         // n + 1 entries
+  int64_t lengths_bytes = 0;        // debug builds: readable bytes of `lengths` and entries of `sparse`
+  int64_t sparse_entries = 0;
+};
+void launch_wire_offsets(const WireOffsetsArgs& a, hipStream_t stream);
+// P33 letters [c0, c1) of a stream -> out[0 .. c1 - c0). `src` points at byte p33_first_byte(c0) of the stream and
+// the kernel loads only bytes of [p33_first_byte(c0), p33_end_byte(c1)): dwords inside, single bytes at the ends.
+struct Unpack33Args {
+  const uint8_t* src = nullptr;
+  int64_t c0 = 0, c1 = 0;
+  uint8_t* out = nullptr;
+  int64_t src_bytes = 0;            // p33_end_byte(c1) - p33_first_byte(c0)
+};
+void launch_unpack33(const Unpack33Args& a, hipStream_t stream);
+
 // Lanes a record needs in the short kernel (offsets 0..L1-L2 incl. the helper diagonal).
 inline int64_t lanes_needed(int64_t L1, int64_t L2) { return L2 <= L1 ? L1 - L2 + 1 : 1; }
 
@@ -353,6 +380,7 @@ void preload_mfma_kernels();
 void preload_profile_kernels();
 void preload_report_kernels();
 void preload_hits_kernels();
+void preload_wire_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -365,6 +393,7 @@ enum PreloadSet : unsigned {
   kPreloadProfile = 64,  // profile_kernels.hip: loads at its first launch unless named
   kPreloadReport = 128,  // report_kernels.hip: likewise
   kPreloadHits = 256,    // hits_kernels.hip: likewise
+  kPreloadWire = 512,    // wire_kernels.hip: likewise
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -376,9 +405,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadProfile) preload_profile_kernels();
   if (set & kPreloadReport) preload_report_kernels();
   if (set & kPreloadHits) preload_hits_kernels();
+  if (set & kPreloadWire) preload_wire_kernels();
 }
 // "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
-// profile, report, hits;
+// profile, report, hits, wire;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

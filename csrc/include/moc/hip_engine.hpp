@@ -61,7 +61,7 @@ struct EngineStats {
   int32_t format = 0;    // ResultFormat of the last solve
   int32_t kernels = 0;   // bitmask of kernels used: 1 swipe (lane/record), 2 short (lane/offset), 4 tiles
                          // (LUT tile kernel), 8 tile16, 16 profile (per-offset profile / top-K), 32 report,
-                         // 64 hits (count / scan / compact, next to 16)
+                         // 64 hits (count / scan / compact, next to 16), 128 wire (decode kernels of a *_wire call)
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -123,8 +123,8 @@ class HipEngine {
                     Result* d_out, hipStream_t stream);
 
   // ---- per-offset score profile and top-K alignments (definitions: moc/cpu_engine.hpp; kernels:
-  // csrc/src/hip/profile_kernels.hip). Byte letters and dense int64 offsets only: wire-format and packed-letter
-  // inputs, the zero-copy path and the context-parallel split are not part of these calls.
+  // csrc/src/hip/profile_kernels.hip). Byte letters and dense int64 offsets; wire-format batches go through the
+  // *_wire forms below (a device-side decode first). The context-parallel split is not part of these calls.
   // Device-resident forms, queued on `stream` (0 = engine compute stream) with no sync, like solve_device:
   // d_prof receives the batch's flat profile (sum of candidate_offsets entries, record i's at the host-computed
   // profile offset i), d_out the int32 [n, K, 3] top-K rows, 1 <= K <= kMaxTopK. Top-K never materialises the
@@ -148,7 +148,8 @@ class HipEngine {
 
   // ---- threshold hits (definitions: moc/cpu_engine.hpp hits_batch_cpu; kernels: csrc/src/hip/hits_kernels.hip):
   // every offset whose profile score is >= the record's threshold, as rows (score, n = o, k) in ascending o, record
-  // i's at rows[hoffsets[i] .. hoffsets[i + 1]). Limits as top-K: byte letters, dense int64 offsets, n < 2^31 - 1.
+  // i's at rows[hoffsets[i] .. hoffsets[i + 1]). Limits as top-K: byte letters and dense int64 offsets (wire batches:
+  // solve_hits_wire), n < 2^31 - 1.
   // Device form: queued on `stream` (0 = engine compute stream) with no sync, in the chunks of top-K under
   // profile_scratch_bytes — per chunk the profile kernel, then count, prefix sum and compaction. d_thresholds:
   // device int32 [n], or null for min_score on every record. d_hoffsets (int64 [n + 1]) is always complete and
@@ -169,7 +170,8 @@ class HipEngine {
 
   // ---- alignment report (definitions: moc/cpu_engine.hpp report_batch_cpu; kernels:
   // csrc/src/hip/report_kernels.hip): the sign counts and, optionally, the marker bytes of caller-supplied rows.
-  // Byte letters and dense int64 offsets only; no Semantics (row validity does not depend on it).
+  // Byte letters and dense int64 offsets (wire batches: report_wire); no Semantics (row validity does not depend on
+  // it).
   // Device form: d_rows [n*K] rows, d_counts [n*K*4] int32 (16-byte aligned), d_marks null or K * letters bytes;
   // queued on `stream` (0 = engine compute stream) with no sync — directly behind solve_device /
   // solve_topk_device on the same stream. 1 <= K <= kMaxTopK.
@@ -178,6 +180,40 @@ class HipEngine {
   // Host form (uploads through the pooled buffers; synchronous; fills stats()). marks may be null.
   void report(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, const Result* rows, int32_t* counts,
               uint8_t* marks);
+
+  // ---- wire-format input (moc/wire.hpp; kernels: csrc/src/hip/wire_kernels.hip; host reference: decode_wire_cpu)
+  // A wire batch as the byte letters and dense int64 offsets the calls above take, decoded on the GPU.
+  struct DecodedWire {
+    const uint8_t* d_codes;    // base pointer: record i starts at d_codes + offsets[i] (offsets stay absolute)
+    const int64_t* d_offsets;  // device, n + 1 entries
+    const int64_t* h_offsets;  // host copy, for planning
+    int64_t n;
+  };
+  // Queues the decode on `stream` (0 = engine compute stream) with no sync, into buffers of the engine that grow
+  // and are never freed per call (letters + 8 (n + 1) bytes); the result stays valid until the engine's next decode.
+  // P33 letters go through launch_unpack33, 5-bit ones through launch_unpack5 (the stream then needs one readable
+  // byte after its last letter's, as packed5_bytes leaves), byte letters on the device and dense device offsets are
+  // used in place; sparse offsets are expanded by launch_wire_offsets. A host batch's packed letters, lengths and
+  // sparse offsets are read in place by those kernels when they are page-locked (and allow_direct is on), else
+  // copied to the device in packed form first; its byte letters and dense offsets are uploaded. b.device: every
+  // pointer of `b` is device memory and `host_meta` carries host copies of its offsets (sparse or dense) and narrow
+  // lengths, from which the host expands h_offsets; the device's dense offsets still come from the kernel.
+  // device_kernel_ms() right after it gives the device time of the decode kernels.
+  // codes_dst / offsets_dst (device; letters bytes / n + 1 entries): decode there instead of into the engine's
+  // buffers, copying what would otherwise be used in place — the caller owns the result's lifetime.
+  DecodedWire decode_wire_device(const WireBatch& b, const WireBatch* host_meta, hipStream_t stream,
+                                 uint8_t* codes_dst = nullptr, int64_t* offsets_dst = nullptr);
+  // Host forms on a host wire batch (pinned or pageable): the decode above, then the profile / top-K / hits / report
+  // path of the byte-letter calls on the decoded buffers — same chunking under profile_scratch_bytes, same
+  // hits_passes() and capacity contract. Synchronous; fill stats() (kernels bit 128 when a decode kernel ran,
+  // h2d_bytes in wire-format bytes). The whole batch is decoded at once.
+  void solve_profile_wire(const WireBatch& b, ProfileEntry* prof_out, int64_t* poffsets_out);
+  void solve_topk_wire(const WireBatch& b, int K, Result* out);
+  void solve_hits_wire(const WireBatch& b, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
+                       std::vector<Result>& rows_out, int64_t max_rows_hint = -1);
+  void report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks);
+  // poffsets[0..n] of a host wire batch (profile_offsets of its decoded lengths; no GPU work)
+  void wire_profile_offsets(const WireBatch& b, int64_t* poffsets) const;
 
   // Context-parallel search: this engine evaluates part `part` of `parts` of the batch's
   // global list of offset tiles and writes one packed 64-bit key per record (moc::encode_key; 0 =
@@ -229,7 +265,25 @@ class HipEngine {
   Ran launch_planned(PlannedBatch& pb, const dev::BatchView& bv, int64_t first_offset, void* d_out, unsigned* counter,
                      void* d_plan, ResultFormat fmt, hipStream_t s);
   std::vector<int64_t> upload_batch(const uint8_t* codes, const int64_t* offsets, int64_t n, size_t out_bytes);
-  void host_call_stats(Stopwatch& wall, double kernel_ms, int64_t letters, int64_t n, size_t d2h_bytes);
+  // A host call's batch once it is on the device (uploaded by upload_batch, or decoded by decode_wire_device),
+  // with what the placement adds to stats(): the second halves of the host forms below take it from there.
+  struct Placed {
+    const uint8_t* d_codes;
+    const int64_t* d_offsets;
+    const int64_t* h_offsets;
+    int64_t n;
+    int64_t h2d_bytes;
+    int32_t kernels;
+  };
+  Placed placed_upload(const std::vector<int64_t>& rebased, int64_t n) const;
+  Placed place_wire(const WireBatch& b, size_t out_bytes);
+  void profile_placed(const Placed& p, ProfileEntry* prof_out, const int64_t* poffsets, Stopwatch& wall);
+  void topk_placed(const Placed& p, int K, Result* out, Stopwatch& wall);
+  void hits_placed(const Placed& p, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
+                   std::vector<Result>& rows_out, int64_t max_rows_hint, Stopwatch& wall);
+  void report_placed(const Placed& p, int K, const Result* rows, int32_t* counts, uint8_t* marks, Stopwatch& wall);
+  static size_t report_out_bytes(int64_t n, int K, int64_t mark_letters);
+  void host_call_stats(Stopwatch& wall, double kernel_ms, const Placed& p, size_t d2h_bytes);
   void ensure_device_events();  // ev_d0_ / ev_d1_, made by the first call that records them
   dev::Plan device_plan(void* d_plan, size_t n_starts, bool has_long_recs, int64_t n_long, const plan::TilePlan& tp,
                         unsigned long long* keys = nullptr) const;
@@ -317,6 +371,15 @@ class HipEngine {
   void* d_hits_rows_ = nullptr;
   size_t d_hits_rows_cap_ = 0;
   int hits_passes_ = 0;
+  // wire decode: the decoded batch (offsets | letters), the packed input of pageable host batches, the host copy
+  // of the dense offsets, and what the last decode moved and launched
+  void* d_wire_ = nullptr;
+  size_t d_wire_cap_ = 0;
+  void* d_wire_in_ = nullptr;
+  size_t d_wire_in_cap_ = 0;
+  std::vector<int64_t> wire_h_offsets_;
+  int64_t wire_h2d_ = 0;
+  int32_t wire_kernels_ = 0;
   std::vector<void*> pinned_;
   struct DirectKey {
     dev::ProblemView pv;

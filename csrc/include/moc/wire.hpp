@@ -142,4 +142,23 @@ struct WireBatch {
   int64_t length_bytes() const { return lengths ? narrow_lengths_bytes(n, len_bits) : 0; }
 };
 
+// ---- host reference decode (the oracle of the device decode, csrc/src/hip/wire_kernels.hip) -------------
+// Sizes of a batch decoded to one byte per letter and dense offsets.
+struct WireDecodedBytes {
+  int64_t codes = 0;    // end_letter() - first_letter()
+  int64_t offsets = 0;  // 8 (n + 1)
+};
+// Throws moc::Error on a batch no decoder takes: sparse offsets without lengths, off_shift outside 0..6,
+// len_bits not 8 / 4 / 3 / kLenBase6, both letter packings, n < 0 or n >= 2^31 - 1, null offsets. Reads no array.
+void validate_wire(const WireBatch& b);
+WireDecodedBytes wire_decoded_bytes(const WireBatch& b);
+// offsets_out[0..n]: absolute dense offsets (offsets_out[0] = first_letter()) from the batch's host-readable
+// offsets and lengths. Validates as validate_wire and throws when an end offset — the batch end, or any sparse
+// entry — disagrees with the summed lengths.
+void wire_dense_offsets(const WireBatch& b, int64_t* offsets_out);
+// The whole batch: codes_out[0 .. end_letter() - first_letter()) byte codes (P33: 1..26, a packed 0 reads back
+// as 1, see p33_field) and offsets_out as wire_dense_offsets. Composes unpack33 / unpack5 / expand_offsets /
+// narrow_length; host pointers only.
+void decode_wire_cpu(const WireBatch& b, uint8_t* codes_out, int64_t* offsets_out);
+
 }  // namespace moc

@@ -592,6 +592,86 @@ int moc_engine_report_device(void* e, const uint8_t* d_codes, const int64_t* d_o
   });
 }
 
+namespace {
+moc::WireBatch wire_batch(const moc_wire_batch* w) {
+  if (!w) throw moc::Error("wire batch: null");
+  if (w->packed != 0 && w->packed != 1 && w->packed != 3) throw moc::Error("letters: 0 bytes, 1 5-bit packed or 3 P33 fields");
+  moc::WireBatch b;
+  b.letters = w->letters;
+  b.packed5 = w->packed == 1;
+  b.packed33 = w->packed == 3;
+  b.offsets = w->offsets;
+  b.off_shift = w->off_shift;
+  b.lengths = w->lengths;
+  b.len_bits = w->len_bits;
+  b.len_base = w->len_base;
+  b.n = w->n;
+  b.device = w->device != 0;
+  return b;
+}
+}  // namespace
+
+int moc_cpu_decode_wire(const moc_wire_batch* w, uint8_t* codes_out, int64_t* offsets_out, int64_t* sizes2) {
+  return guard([&] {
+    const moc::WireBatch b = wire_batch(w);
+    if (b.device) throw moc::Error("decode_wire_cpu: host pointers only");
+    const moc::WireDecodedBytes sz = moc::wire_decoded_bytes(b);
+    if (sizes2) {
+      sizes2[0] = sz.codes;
+      sizes2[1] = sz.offsets;
+    }
+    if (offsets_out) moc::decode_wire_cpu(b, codes_out, offsets_out);
+  });
+}
+
+int moc_engine_decode_wire_device(void* e, const moc_wire_batch* w, const moc_wire_batch* host_meta, void* stream,
+                                  uint64_t* out3, int64_t* h_offsets_out, uint8_t* d_codes_dst, int64_t* d_offsets_dst) {
+  return guard([&] {
+    const moc::WireBatch b = wire_batch(w);
+    moc::WireBatch m;
+    if (host_meta) m = wire_batch(host_meta);
+    const moc::HipEngine::DecodedWire dw = static_cast<moc::HipEngine*>(e)->decode_wire_device(
+        b, host_meta ? &m : nullptr, static_cast<hipStream_t>(stream), d_codes_dst, d_offsets_dst);
+    out3[0] = reinterpret_cast<uint64_t>(dw.d_codes);
+    out3[1] = reinterpret_cast<uint64_t>(dw.d_offsets);
+    out3[2] = static_cast<uint64_t>(dw.h_offsets[dw.n] - dw.h_offsets[0]);
+    if (h_offsets_out) std::memcpy(h_offsets_out, dw.h_offsets, sizeof(int64_t) * static_cast<size_t>(dw.n + 1));
+  });
+}
+
+int moc_engine_solve_profile_wire(void* e, const moc_wire_batch* w, int64_t* poffsets, moc_profile_entry* prof) {
+  return guard([&] {
+    auto* eng = static_cast<moc::HipEngine*>(e);
+    const moc::WireBatch b = wire_batch(w);
+    if (!prof)
+      eng->wire_profile_offsets(b, poffsets);
+    else
+      eng->solve_profile_wire(b, reinterpret_cast<moc::ProfileEntry*>(prof), poffsets);
+  });
+}
+
+int moc_engine_solve_topk_wire(void* e, const moc_wire_batch* w, int K, moc_result* out) {
+  return guard([&] { static_cast<moc::HipEngine*>(e)->solve_topk_wire(wire_batch(w), K, reinterpret_cast<moc::Result*>(out)); });
+}
+
+int moc_engine_solve_hits_wire(void* e, const moc_wire_batch* w, int32_t min_score, const int32_t* thresholds,
+                               int64_t max_rows_hint, int64_t* hoffsets, moc_result* rows, int64_t cap) {
+  return guard([&] {
+    if (cap < 0 || (cap > 0 && !rows)) throw moc::Error("hits: cap rows need a rows buffer");
+    static_cast<moc::HipEngine*>(e)->solve_hits_wire(wire_batch(w), min_score, thresholds, hoffsets, g_hits_rows,
+                                                     max_rows_hint);
+    const size_t m = std::min(g_hits_rows.size(), static_cast<size_t>(cap));
+    if (m) std::memcpy(rows, g_hits_rows.data(), sizeof(moc::Result) * m);
+  });
+}
+
+int moc_engine_report_wire(void* e, const moc_wire_batch* w, int K, const moc_result* rows, int32_t* counts,
+                           uint8_t* marks) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->report_wire(wire_batch(w), K, reinterpret_cast<const moc::Result*>(rows), counts, marks);
+  });
+}
+
 int moc_engine_stats(void* e, double* out14) {
   return guard([&] {
     double* out13 = out14;

@@ -110,7 +110,8 @@ int parse_preload_set(const char* s) {
   } names[] = {{"all", kPreloadAll}, {"none", 0}, {"align", kPreloadAlign}, {"short", kPreloadShort},
                {"swipe", kPreloadSwipeByte | kPreloadSwipeP33}, {"swipe8", kPreloadSwipeByte},
                {"swipe33", kPreloadSwipeP33}, {"tile16", kPreloadTile16}, {"mfma", kPreloadMfma},
-               {"profile", kPreloadProfile}, {"report", kPreloadReport}, {"hits", kPreloadHits}};
+               {"profile", kPreloadProfile}, {"report", kPreloadReport}, {"hits", kPreloadHits},
+               {"wire", kPreloadWire}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -220,6 +221,8 @@ HipEngine::~HipEngine() {
   (void)hipFree(d_prof_scratch_);
   (void)hipFree(d_hits_sums_);
   (void)hipFree(d_hits_rows_);
+  (void)hipFree(d_wire_);
+  (void)hipFree(d_wire_in_);
   for (hipEvent_t e : ev_select_) (void)hipEventDestroy(e);
   (void)hipHostFree(h_plan_);
   (void)hipEventDestroy(ev_plan_);
@@ -938,11 +941,19 @@ std::vector<int64_t> HipEngine::upload_batch(const uint8_t* codes, const int64_t
   return rebased;
 }
 
-// Stats of a synchronous call over a batch uploaded by upload_batch (`letters` letter bytes), once it is complete.
-void HipEngine::host_call_stats(Stopwatch& wall, double kernel_ms, int64_t letters, int64_t n, size_t d2h_bytes) {
+// upload_batch's buffers as a placed batch: rebased[n] letter bytes and n + 1 offsets went up.
+HipEngine::Placed HipEngine::placed_upload(const std::vector<int64_t>& rebased, int64_t n) const {
+  const Slot& s = *slots_[0];
+  return Placed{static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(), n,
+                rebased[n] + static_cast<int64_t>(sizeof(int64_t)) * (n + 1), 0};
+}
+
+// Stats of a synchronous call over a placed batch, once it is complete.
+void HipEngine::host_call_stats(Stopwatch& wall, double kernel_ms, const Placed& p, size_t d2h_bytes) {
   stats_.kernel_ms = kernel_ms;
-  stats_.h2d_bytes = letters + static_cast<int64_t>(sizeof(int64_t)) * (n + 1);
+  stats_.h2d_bytes = p.h2d_bytes;
   stats_.d2h_bytes = static_cast<int64_t>(d2h_bytes);
+  stats_.kernels |= p.kernels;
   wall.stop();
   stats_.total_ms = wall.total_ms();
 }
@@ -964,7 +975,7 @@ void HipEngine::search_keys(const uint8_t* codes, const int64_t* offsets, int64_
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
   float ms = 0;
   MOC_HIP_CHECK(hipEventElapsedTime(&ms, ev_a_, ev_b_));
-  host_call_stats(wall, ms, rebased[n], n, sizeof(uint64_t) * n);
+  host_call_stats(wall, ms, placed_upload(rebased, n), sizeof(uint64_t) * n);
 }
 
 // ---- per-offset score profile and top-K alignments ------------------------------------------------------
@@ -1133,14 +1144,19 @@ void HipEngine::solve_profile(const uint8_t* codes, const int64_t* offsets, int6
   if (n <= 0) return;
   Stopwatch wall;
   wall.start();
-  Slot& s = *slots_[0];
   const size_t pbytes = sizeof(ProfileEntry) * static_cast<size_t>(poffsets_out[n]);
   const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, std::max<size_t>(pbytes, 8));
-  run_profile(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(), n, 0,
-              s.d_out, s_compute_);
+  profile_placed(placed_upload(rebased, n), prof_out, poffsets_out, wall);
+}
+
+// The host forms' second halves: the batch is on the device (p) and slot 0's d_out holds the call's output bytes.
+void HipEngine::profile_placed(const Placed& p, ProfileEntry* prof_out, const int64_t* poffsets, Stopwatch& wall) {
+  Slot& s = *slots_[0];
+  const size_t pbytes = sizeof(ProfileEntry) * static_cast<size_t>(poffsets[p.n]);
+  run_profile(p.d_codes, p.d_offsets, p.h_offsets, p.n, 0, s.d_out, s_compute_);
   if (pbytes) copy_d2h(prof_out, s.d_out, pbytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  host_call_stats(wall, device_kernel_ms(), rebased[n], n, pbytes);
+  host_call_stats(wall, device_kernel_ms(), p, pbytes);
 }
 
 void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, Result* out) {
@@ -1150,14 +1166,18 @@ void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t
   if (n <= 0) return;
   Stopwatch wall;
   wall.start();
+  const std::vector<int64_t> rebased =
+      upload_batch(codes, offsets, n, sizeof(Result) * static_cast<size_t>(n) * static_cast<size_t>(K));
+  topk_placed(placed_upload(rebased, n), K, out, wall);
+}
+
+void HipEngine::topk_placed(const Placed& p, int K, Result* out, Stopwatch& wall) {
   Slot& s = *slots_[0];
-  const size_t obytes = sizeof(Result) * static_cast<size_t>(n) * static_cast<size_t>(K);
-  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, obytes);
-  run_profile(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(), n, K,
-              s.d_out, s_compute_);
+  const size_t obytes = sizeof(Result) * static_cast<size_t>(p.n) * static_cast<size_t>(K);
+  run_profile(p.d_codes, p.d_offsets, p.h_offsets, p.n, K, s.d_out, s_compute_);
   copy_d2h(out, s.d_out, obytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  host_call_stats(wall, device_kernel_ms(), rebased[n], n, obytes);
+  host_call_stats(wall, device_kernel_ms(), p, obytes);
 }
 
 // ---- threshold hits -------------------------------------------------------------------------------------
@@ -1190,17 +1210,24 @@ void HipEngine::solve_hits(const uint8_t* codes, const int64_t* offsets, int64_t
   if (n <= 0) return;
   Stopwatch wall;
   wall.start();
+  const std::vector<int64_t> rebased =
+      upload_batch(codes, offsets, n, sizeof(int64_t) * static_cast<size_t>(n + 1) + sizeof(int32_t) * static_cast<size_t>(n));
+  hits_placed(placed_upload(rebased, n), min_score, thresholds, hoffsets_out, rows_out, max_rows_hint, wall);
+}
+
+void HipEngine::hits_placed(const Placed& p, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
+                            std::vector<Result>& rows_out, int64_t max_rows_hint, Stopwatch& wall) {
   Slot& s = *slots_[0];
+  const int64_t n = p.n;
   // d_out: hoffsets (n + 1) | thresholds (n); the rows have a buffer of their own, which the second pass may grow
   const size_t hbytes = sizeof(int64_t) * static_cast<size_t>(n + 1), tbytes = sizeof(int32_t) * static_cast<size_t>(n);
-  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, hbytes + tbytes);
   char* d = static_cast<char*>(s.d_out);
   if (thresholds) copy_h2d(d + hbytes, thresholds, tbytes, s_compute_);
   int64_t cap = std::max<int64_t>(max_rows_hint < 0 ? 4 * n : max_rows_hint, 1);
   double kernel_ms = 0;
   for (;;) {
     ensure(d_hits_rows_, d_hits_rows_cap_, sizeof(Result) * static_cast<size_t>(cap));
-    solve_hits_device(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(),
+    solve_hits_device(p.d_codes, p.d_offsets, p.h_offsets,
                       n, min_score, thresholds ? reinterpret_cast<const int32_t*>(d + hbytes) : nullptr,
                       reinterpret_cast<int64_t*>(d), static_cast<Result*>(d_hits_rows_), cap, s_compute_);
     copy_d2h(hoffsets_out, d, hbytes, s_compute_);
@@ -1218,7 +1245,7 @@ void HipEngine::solve_hits(const uint8_t* codes, const int64_t* offsets, int64_t
     copy_d2h(rows_out.data(), d_hits_rows_, rbytes, s_compute_);
     MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
   }
-  host_call_stats(wall, kernel_ms, rebased[n], n, hbytes * static_cast<size_t>(hits_passes_) + rbytes);
+  host_call_stats(wall, kernel_ms, p, hbytes * static_cast<size_t>(hits_passes_) + rbytes);
   if (thresholds) stats_.h2d_bytes += static_cast<int64_t>(tbytes);
 }
 
@@ -1279,22 +1306,220 @@ void HipEngine::report(const uint8_t* codes, const int64_t* offsets, int64_t n, 
   if (n <= 0) return;
   Stopwatch wall;
   wall.start();
+  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, report_out_bytes(n, K, marks ? offsets[n] - offsets[0] : 0));
+  report_placed(placed_upload(rebased, n), K, rows, counts, marks, wall);
+}
+
+// d_out of a host report: counts (16-byte aligned at the start) | rows | marker bytes (K * letters, 0 without marks)
+size_t HipEngine::report_out_bytes(int64_t n, int K, int64_t mark_letters) {
+  const size_t n_rows = static_cast<size_t>(n) * static_cast<size_t>(K);
+  return 16 * n_rows + sizeof(Result) * n_rows + std::max<size_t>(static_cast<size_t>(K) * static_cast<size_t>(mark_letters), 16);
+}
+
+void HipEngine::report_placed(const Placed& p, int K, const Result* rows, int32_t* counts, uint8_t* marks, Stopwatch& wall) {
   Slot& s = *slots_[0];
-  // d_out: counts (16-byte aligned at the start) | rows | marker bytes
+  const int64_t n = p.n;
   const size_t n_rows = static_cast<size_t>(n) * static_cast<size_t>(K);
   const size_t cbytes = 16 * n_rows, rbytes = sizeof(Result) * n_rows;
-  const size_t mbytes = marks ? static_cast<size_t>(K) * static_cast<size_t>(offsets[n] - offsets[0]) : 0;
-  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, cbytes + rbytes + std::max<size_t>(mbytes, 16));
+  const size_t mbytes = marks ? static_cast<size_t>(K) * static_cast<size_t>(p.h_offsets[n] - p.h_offsets[0]) : 0;
   char* d = static_cast<char*>(s.d_out);
   copy_h2d(d + cbytes, rows, rbytes, s_compute_);
-  report_device(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(), n, K,
-                reinterpret_cast<const Result*>(d + cbytes), reinterpret_cast<int32_t*>(d),
-                marks ? reinterpret_cast<uint8_t*>(d + cbytes + rbytes) : nullptr, s_compute_);
+  report_device(p.d_codes, p.d_offsets, p.h_offsets, n, K, reinterpret_cast<const Result*>(d + cbytes),
+                reinterpret_cast<int32_t*>(d), marks ? reinterpret_cast<uint8_t*>(d + cbytes + rbytes) : nullptr, s_compute_);
   copy_d2h(counts, d, cbytes, s_compute_);
   if (mbytes) copy_d2h(marks, d + cbytes + rbytes, mbytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  host_call_stats(wall, device_kernel_ms(), rebased[n], n, cbytes + mbytes);
+  host_call_stats(wall, device_kernel_ms(), p, cbytes + mbytes);
   stats_.h2d_bytes += static_cast<int64_t>(rbytes);
+}
+
+// ---- wire-format input ------------------------------------------------------------------------------------
+// Decoded batch: offsets (8 (n + 1), when the kernel or an upload makes them) | letters (from a 16-byte boundary).
+// Packed input of a pageable host batch: sparse offsets | lengths (8-byte aligned: base-6 words) | letters.
+HipEngine::DecodedWire HipEngine::decode_wire_device(const WireBatch& b, const WireBatch* host_meta, hipStream_t stream,
+                                                     uint8_t* codes_dst, int64_t* offsets_dst) {
+  if (b.device && !host_meta) throw Error("decode_wire_device: a device-resident batch needs host copies of its offsets and lengths");
+  const WireBatch& m = b.device ? *host_meta : b;  // the host-readable offsets and lengths
+  validate_wire(b);
+  if (b.device && (m.device || m.n != b.n || m.off_shift != b.off_shift || m.len_bits != b.len_bits ||
+                   m.len_base != b.len_base || !m.lengths != !b.lengths))
+    throw Error("decode_wire_device: the host copies do not describe the device batch");
+  if (b.off_shift && b.len_bits == kLenBase6 && (reinterpret_cast<uintptr_t>(b.lengths) & 7))
+    throw Error("base-6 lengths must be 8-byte aligned (the kernels load whole words)");
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  if (!stream) stream = s_compute_;
+  const int64_t n = b.n;
+  wire_h_offsets_.resize(static_cast<size_t>(n) + 1);
+  wire_dense_offsets(m, wire_h_offsets_.data());  // validates the lengths against the offsets
+  const int64_t c0 = wire_h_offsets_[0], c1 = wire_h_offsets_[n], letters = c1 - c0;
+  if (c0 < 0 || letters < 0) throw Error("wire batch: the end offset lies before the first");
+  wire_h2d_ = 0;
+  wire_kernels_ = 0;
+
+  // ---- where each packed array is read from: in place (device, or page-locked host), or a packed copy
+  const bool direct = opt_.allow_direct;
+  const int64_t lb0 = b.packed33 ? p33_first_byte(c0) : b.packed5 ? (5 * c0) >> 3 : c0;
+  const int64_t lb1 = b.packed33 ? p33_end_byte(c1) : b.packed5 ? (5 * c1 + 7) >> 3 : c1;  // the letters' bytes
+  const bool packed = b.packed33 || b.packed5;
+  const void *src_letters = nullptr, *src_sparse = nullptr, *src_lengths = nullptr;
+  size_t in_sparse = 0, in_lengths = 0, in_letters = 0;  // bytes staged
+  const size_t sparse_bytes = sizeof(int64_t) * static_cast<size_t>(b.offset_entries());
+  const size_t length_bytes = static_cast<size_t>(b.length_bytes());
+  if (b.device) {
+    src_letters = b.letters + lb0;
+    src_sparse = b.offsets;
+    src_lengths = b.lengths;
+  } else {
+    // 5-bit letters: launch_unpack5 loads the byte after each letter's first, one past lb1 for the last
+    if (packed && letters > 0 &&
+        !(direct && pinned_range(b.letters + lb0, static_cast<size_t>(lb1 - lb0) + (b.packed5 ? 1 : 0), &src_letters)))
+      in_letters = static_cast<size_t>(lb1 - lb0);
+    if (b.off_shift) {
+      if (!(direct && pinned_range(b.offsets, sparse_bytes, &src_sparse))) in_sparse = sparse_bytes;
+      if (!(direct && pinned_range(b.lengths, length_bytes, &src_lengths))) in_lengths = length_bytes;
+    }
+  }
+  const size_t in_len_at = (in_sparse + 7) & ~size_t{7}, in_let_at = (in_len_at + in_lengths + 15) & ~size_t{15};
+  const size_t off_bytes = sizeof(int64_t) * static_cast<size_t>(n + 1);
+  const size_t codes_at = (off_bytes + 15) & ~size_t{15};
+  if (!codes_dst || !offsets_dst) ensure(d_wire_, d_wire_cap_, codes_at + static_cast<size_t>(letters) + 32);
+  if (in_sparse + in_lengths + in_letters) {
+    ensure(d_wire_in_, d_wire_in_cap_, in_let_at + in_letters + 32);
+    char* in = static_cast<char*>(d_wire_in_);
+    if (in_sparse) {
+      copy_h2d(in, b.offsets, in_sparse, stream);
+      src_sparse = in;
+    }
+    if (in_lengths) {
+      copy_h2d(in + in_len_at, b.lengths, in_lengths, stream);
+      src_lengths = in + in_len_at;
+    }
+    if (in_letters) {
+      copy_h2d(in + in_let_at, b.letters + lb0, in_letters, stream);
+      src_letters = in + in_let_at;
+    }
+  }
+  int64_t* d_off = offsets_dst ? offsets_dst : static_cast<int64_t*>(d_wire_);
+  uint8_t* d_let = codes_dst ? codes_dst : static_cast<uint8_t*>(d_wire_) + codes_at;
+  DecodedWire dw{d_let - c0, d_off, wire_h_offsets_.data(), n};
+  // device_kernel_ms() after a decode: its kernels (and the upload of byte letters or dense offsets), without the
+  // host work and the packed copies of pageable sources above
+  ensure_device_events();
+  MOC_HIP_CHECK(hipEventRecord(ev_d0_, stream));
+
+  // ---- letters
+  if (!packed) {
+    if (b.device && !codes_dst) {
+      dw.d_codes = b.letters;  // in place
+    } else if (b.device) {
+      if (letters > 0) MOC_HIP_CHECK(hipMemcpyAsync(d_let, b.letters + c0, static_cast<size_t>(letters), hipMemcpyDeviceToDevice, stream));
+    } else if (letters > 0) {
+      copy_h2d(d_let, b.letters + c0, static_cast<size_t>(letters), stream);
+      wire_h2d_ += letters;
+    }
+  } else if (letters > 0) {
+    if (b.packed33) {
+      dev::Unpack33Args ua;
+      ua.src = static_cast<const uint8_t*>(src_letters);
+      ua.c0 = c0;
+      ua.c1 = c1;
+      ua.out = d_let;
+      ua.src_bytes = lb1 - lb0;
+      dev::launch_unpack33(ua, stream);
+    } else {
+      dev::launch_unpack5(static_cast<const uint8_t*>(src_letters), 5 * c0 - 8 * lb0, letters, d_let, stream);
+    }
+    wire_kernels_ = 128;
+    if (!b.device) wire_h2d_ += lb1 - lb0;
+  }
+  // ---- offsets
+  if (b.off_shift) {
+    dev::WireOffsetsArgs oa;
+    oa.sparse = static_cast<const int64_t*>(src_sparse);
+    oa.shift = b.off_shift;
+    oa.bits = b.len_bits;
+    oa.lengths = static_cast<const uint8_t*>(src_lengths);
+    oa.base = b.len_base;
+    oa.n = n;
+    oa.dense = d_off;
+    oa.lengths_bytes = static_cast<int64_t>(length_bytes);
+    oa.sparse_entries = b.offset_entries();
+    dev::launch_wire_offsets(oa, stream);
+    wire_kernels_ = 128;
+    if (!b.device) wire_h2d_ += static_cast<int64_t>(sparse_bytes + length_bytes);
+  } else if (b.device && !offsets_dst) {
+    dw.d_offsets = b.offsets;  // in place
+  } else if (b.device) {
+    MOC_HIP_CHECK(hipMemcpyAsync(d_off, b.offsets, off_bytes, hipMemcpyDeviceToDevice, stream));
+  } else {
+    MOC_HIP_CHECK(hipMemcpyAsync(d_off, wire_h_offsets_.data(), off_bytes, hipMemcpyHostToDevice, stream));
+    wire_h2d_ += static_cast<int64_t>(off_bytes);
+  }
+  MOC_HIP_CHECK(hipGetLastError());
+  MOC_HIP_CHECK(hipEventRecord(ev_d1_, stream));
+  return dw;
+}
+
+// A host wire batch on the device for a host form, slot 0's d_out grown to out_bytes.
+HipEngine::Placed HipEngine::place_wire(const WireBatch& b, size_t out_bytes) {
+  if (b.device) throw Error("the *_wire host forms take host batches; a device-resident one goes through decode_wire_device");
+  const DecodedWire dw = decode_wire_device(b, nullptr, s_compute_);
+  Slot& s = *slots_[0];
+  ensure(s.d_out, s.d_out_cap, out_bytes);
+  return Placed{dw.d_codes, dw.d_offsets, dw.h_offsets, dw.n, wire_h2d_, wire_kernels_};
+}
+
+void HipEngine::wire_profile_offsets(const WireBatch& b, int64_t* poffsets) const {
+  if (b.device) throw Error("wire_profile_offsets: host pointers only");
+  std::vector<int64_t> dense(static_cast<size_t>(std::max<int64_t>(b.n, 0)) + 1);
+  wire_dense_offsets(b, dense.data());
+  profile_offsets(dense.data(), b.n, poffsets);
+}
+
+void HipEngine::solve_profile_wire(const WireBatch& b, ProfileEntry* prof_out, int64_t* poffsets_out) {
+  wire_profile_offsets(b, poffsets_out);
+  if (b.n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  const size_t pbytes = sizeof(ProfileEntry) * static_cast<size_t>(poffsets_out[b.n]);
+  profile_placed(place_wire(b, std::max<size_t>(pbytes, 8)), prof_out, poffsets_out, wall);
+}
+
+void HipEngine::solve_topk_wire(const WireBatch& b, int K, Result* out) {
+  if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  validate_wire(b);
+  if (b.n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  topk_placed(place_wire(b, sizeof(Result) * static_cast<size_t>(b.n) * static_cast<size_t>(K)), K, out, wall);
+}
+
+void HipEngine::solve_hits_wire(const WireBatch& b, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
+                                std::vector<Result>& rows_out, int64_t max_rows_hint) {
+  if (!have_problem_) throw Error("HipEngine: hits before set_problem");
+  validate_wire(b);
+  finish_wire();
+  rows_out.clear();
+  hits_passes_ = 0;
+  hoffsets_out[0] = 0;
+  if (b.n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  const size_t n = static_cast<size_t>(b.n);
+  hits_placed(place_wire(b, sizeof(int64_t) * (n + 1) + sizeof(int32_t) * n), min_score, thresholds, hoffsets_out, rows_out,
+              max_rows_hint, wall);
+}
+
+void HipEngine::report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks) {
+  if (K < 1 || K > kMaxTopK) throw Error("report: K must be in 1.." + std::to_string(kMaxTopK));
+  validate_wire(b);
+  if (b.n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  // the marker bytes need the letter count before the decode: the batch's own first and end offsets
+  const int64_t letters = b.end_letter() - b.first_letter();
+  report_placed(place_wire(b, report_out_bytes(b.n, K, marks ? std::max<int64_t>(letters, 0) : 0)), K, rows, counts, marks, wall);
 }
 
 }  // namespace moc

@@ -161,4 +161,61 @@ int64_t narrow_length(const uint8_t* lengths, int bits, int64_t base, int64_t i)
   return base + ((w >> (bit & 7)) & 7);
 }
 
+// ---- host reference decode ---------------------------------------------------------------------------
+void validate_wire(const WireBatch& b) {
+  if (b.n < 0 || b.n >= (int64_t{1} << 31) - 1) throw Error("wire batch: n must be in 0 .. 2^31 - 2");
+  if (b.packed5 && b.packed33) throw Error("wire batch: letters are 5-bit packed or P33 fields, not both");
+  if (b.off_shift < 0 || b.off_shift > 6) throw Error("wire batch: sparse offsets take one entry per 2^shift records, shift 0..6");
+  if (b.off_shift && !b.lengths) throw Error("wire batch: sparse offsets need narrow lengths");
+  if (b.lengths && b.len_bits != 8 && b.len_bits != 4 && b.len_bits != 3 && b.len_bits != kLenBase6)
+    throw Error("wire batch: lengths must be 8-, 4-, 3-bit or base-6");
+  if (!b.offsets) throw Error("wire batch: no offsets");
+}
+
+WireDecodedBytes wire_decoded_bytes(const WireBatch& b) {
+  validate_wire(b);
+  const int64_t letters = b.end_letter() - b.first_letter();
+  if (letters < 0) throw Error("wire batch: the end offset lies before the first");
+  return WireDecodedBytes{letters, static_cast<int64_t>(sizeof(int64_t)) * (b.n + 1)};
+}
+
+void wire_dense_offsets(const WireBatch& b, int64_t* out) {
+  validate_wire(b);
+  const int64_t n = b.n;
+  if (b.off_shift) {
+    expand_offsets(b.offsets, b.off_shift, b.lengths, b.len_bits, b.len_base, n, out);
+    // every block of 2^shift records must end where the next sparse entry (the last: the batch end) begins
+    const int64_t S = int64_t{1} << b.off_shift, blocks = (n + S - 1) / S;
+    bool ok = true;
+#pragma omp parallel for schedule(static) reduction(&& : ok) if (blocks > 4096)
+    for (int64_t j = 0; j < blocks; ++j) {
+      const int64_t last = std::min(n, (j + 1) * S) - 1;
+      ok = ok && out[last] + narrow_length(b.lengths, b.len_bits, b.len_base, last) == b.offsets[j + 1];
+    }
+    if (!ok) throw Error("wire batch: a sparse offset disagrees with the summed lengths");
+    return;
+  }
+  if (out != b.offsets) std::memcpy(out, b.offsets, sizeof(int64_t) * static_cast<size_t>(n + 1));
+  if (b.lengths) {
+    int64_t sum = 0;
+#pragma omp parallel for schedule(static) reduction(+ : sum) if (n > 65536)
+    for (int64_t i = 0; i < n; ++i) sum += narrow_length(b.lengths, b.len_bits, b.len_base, i);
+    if (b.offsets[0] + sum != b.offsets[n]) throw Error("wire batch: the end offset disagrees with the summed lengths");
+  }
+}
+
+void decode_wire_cpu(const WireBatch& b, uint8_t* codes_out, int64_t* offsets_out) {
+  if (b.device) throw Error("decode_wire_cpu: host pointers only");
+  wire_dense_offsets(b, offsets_out);
+  const int64_t c0 = offsets_out[0], letters = offsets_out[b.n] - c0;
+  if (letters < 0) throw Error("wire batch: the end offset lies before the first");
+  if (!letters) return;
+  if (b.packed33)
+    unpack33(b.letters, c0, letters, codes_out);
+  else if (b.packed5)
+    unpack5(b.letters, c0, letters, codes_out);
+  else
+    std::memcpy(codes_out, b.letters + c0, static_cast<size_t>(letters));
+}
+
 }  // namespace moc

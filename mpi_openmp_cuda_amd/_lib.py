@@ -34,6 +34,14 @@ FORMAT_NAMES = ["r12", "r8", "r4", "r2"]
 _lib = None
 
 
+class WireBatch(ctypes.Structure):
+    """``moc_wire_batch`` (capi.h): one batch in the wire formats, by pointers. ``packed``: 0 byte letters, 1
+    5-bit packed, 3 P33 fields; ``off_shift`` > 0: sparse offsets; ``device``: the pointers are device memory."""
+    _fields_ = [("letters", c_void_p), ("offsets", c_void_p), ("lengths", c_void_p), ("n", c_int64),
+                ("len_base", c_int64), ("packed", c_int32), ("off_shift", c_int32), ("len_bits", c_int32),
+                ("device", c_int32)]
+
+
 class NativeError(RuntimeError):
     """An error reported by the native core (message from moc_last_error)."""
 
@@ -93,6 +101,14 @@ def _decl(lib):
         "moc_engine_solve_hits_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                                  c_void_p, c_void_p, c_int64, c_void_p]),
         "moc_engine_hits_select_ms": (c_int, [c_void_p, c_void_p]),
+        "moc_cpu_decode_wire": (c_int, [P(WireBatch), c_void_p, c_void_p, c_void_p]),
+        "moc_engine_decode_wire_device": (c_int, [c_void_p, P(WireBatch), P(WireBatch), c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p]),
+        "moc_engine_solve_profile_wire": (c_int, [c_void_p, P(WireBatch), c_void_p, c_void_p]),
+        "moc_engine_solve_topk_wire": (c_int, [c_void_p, P(WireBatch), c_int, c_void_p]),
+        "moc_engine_solve_hits_wire": (c_int, [c_void_p, P(WireBatch), c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                               c_int64]),
+        "moc_engine_report_wire": (c_int, [c_void_p, P(WireBatch), c_int, c_void_p, c_void_p, c_void_p]),
         "moc_partition": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_double, c_void_p]),
         "moc_device_count": (c_int, []),
         "moc_host_register": (c_int, [c_void_p, c_size_t]),

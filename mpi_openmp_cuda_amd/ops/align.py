@@ -258,6 +258,54 @@ def report_scores(counts, weights) -> np.ndarray:
     return np.where(c[..., 0] < 0, REPORT_INVALID, s)
 
 
+# ---- wire-format batches (csrc/include/moc/wire.hpp; parallel.wire.WireSlice holds one)
+_LETTER_CODES = {"bytes": 0, "p5": 1, "p33": 3}
+
+
+def _addr(a):
+    return None if a is None else int(a.ctypes.data)
+
+
+def wire_batch_of(ws, shift: int = 0):
+    """A :class:`~..parallel.wire.WireSlice` as the native ``moc_wire_batch`` -> ``(batch, arrays)``; keep
+    ``arrays`` alive while ``batch`` is in use. ``shift`` > 0: the slice's sparse offsets, one per 2^shift records
+    (``WireSlice.wire_offsets``), which need its narrow lengths."""
+    shift = int(shift)
+    if shift and ws.lengths is None:
+        raise ValueError("sparse offsets need narrow lengths (this slice's lengths are too wide for them)")
+    offsets = ws.wire_offsets(shift)
+    arrays = (ws.codes, offsets, ws.lengths)
+    for a in arrays:
+        assert a is None or a.flags["C_CONTIGUOUS"]
+    b = _lib.WireBatch(letters=_addr(ws.codes), offsets=_addr(offsets), lengths=_addr(ws.lengths), n=int(ws.n),
+                       len_base=int(ws.len_base), packed=_LETTER_CODES[ws.letter_format], off_shift=shift,
+                       len_bits=int(ws.len_bits or 8), device=0)
+    return b, arrays
+
+
+def decode_wire_cpu(ws, shift: int = 0):
+    """Host reference decode of a wire batch (``moc::decode_wire_cpu``): ``(codes, offsets)`` — one byte per letter
+    (P33 letters read back as 1..26) and the int64 [n + 1] dense offsets, ``offsets[0]`` the batch's first letter.
+    ``ws``: a WireSlice (``shift`` > 0: through its sparse offsets) or a ``_lib.WireBatch`` of host pointers. A batch
+    whose form or lengths are inconsistent raises :class:`~.._lib.NativeError`."""
+    b, keep = (ws, None) if isinstance(ws, _lib.WireBatch) else wire_batch_of(ws, shift)
+    sizes = np.zeros(2, np.int64)
+    _lib.check(_lib.lib().moc_cpu_decode_wire(ctypes.byref(b), None, None, _lib.ptr(sizes)))
+    codes = np.empty(int(sizes[0]), np.uint8)
+    offsets = np.empty(int(sizes[1]) // 8, np.int64)
+    _lib.check(_lib.lib().moc_cpu_decode_wire(ctypes.byref(b), _lib.ptr(codes), _lib.ptr(offsets), None))
+    del keep
+    return codes, offsets
+
+
+class _DeviceMemory:
+    """Device memory of the native engine as an object torch.as_tensor takes (the CUDA array interface)."""
+
+    def __init__(self, address: int, count: int, typestr: str):
+        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(address), False),
+                                         "version": 2, "strides": None}
+
+
 def brute_force_native(problem: Problem, semantics=Semantics.REFERENCE) -> np.ndarray:
     """Literal O(L1*L2^2) replay of the reference loops, in C++ (test oracle)."""
     out = empty_results(problem.n)
@@ -704,6 +752,157 @@ class HipSearchEngine:
             ctypes.c_void_p(stream.cuda_stream)))
         return counts_t
 
+    # ---- wire-format batches: a device-side decode, then the calls above (csrc/src/hip/wire_kernels.hip)
+    def decode_wire_device(self, letters_t, offsets_t, lengths_t, n: int, h_offsets: np.ndarray,
+                           h_lengths: Optional[np.ndarray], lengths_bits: int = 8, lengths_base: int = 0,
+                           letters: str = "p33", off_shift: int = 0, stream=None):
+        """Device-resident wire batch (torch tensors on this engine's GPU, as the rccl transport holds them) ->
+        ``(codes_t, offsets_t, h_offsets)``: byte letters, int64 [n + 1] dense offsets and their host copy, which
+        feed :meth:`solve_topk_device`, :meth:`solve_hits_device`, :meth:`solve_profile_device` and
+        :meth:`report_device` on the same stream. ``letters_t``: P33 fields (``letters="p33"``), 5-bit packed
+        (``"p5"``, with one readable byte after the last letter's) or ``"bytes"``; ``offsets_t``: dense, or with
+        ``off_shift`` > 0 one entry per 2^off_shift records and the batch end; ``lengths_t``: narrow lengths
+        (``lengths_bits`` 8 / 4 / 3 / 6 = base-6, above ``lengths_base``) or None. ``h_offsets`` / ``h_lengths``
+        are host copies of those two arrays: the host expands them for planning, the device's dense offsets come
+        from the decode kernel. Queued on ``stream`` (default: the current stream) with no sync. Decoded letters
+        and expanded offsets are views of buffers of the engine, valid until its next decode; byte letters and dense
+        offsets are the caller's own tensors. Packed letters must start at letter 0 of ``letters_t``."""
+        import torch
+
+        if letters not in _LETTER_CODES:
+            raise ValueError(f"letters must be one of {tuple(_LETTER_CODES)}")
+        n, off_shift = int(n), int(off_shift)
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        entries = n + 1 if not off_shift else ((n + (1 << off_shift) - 1) >> off_shift) + 1
+        assert letters_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64
+        assert offsets_t.numel() == entries and h_offsets.shape[0] == entries
+        assert (lengths_t is None) == (h_lengths is None)
+        if h_lengths is not None:
+            h_lengths = np.ascontiguousarray(h_lengths, dtype=np.uint8)
+            assert lengths_t.dtype == torch.uint8 and lengths_t.numel() >= h_lengths.shape[0]
+        if letters != "bytes" and n >= 0 and int(h_offsets[0]) != 0:
+            raise ValueError("packed letters must start at letter 0 of letters_t (decoded letters are a view from it)")
+        # the kernels read what the host copies describe: the device arrays must hold that much
+        c1 = int(h_offsets[-1])
+        need = {"p33": (33 * ((c1 + 6) // 7) + 7) >> 3, "p5": ((5 * c1 + 7) >> 3) + 1, "bytes": c1}[letters]
+        if c1 > int(h_offsets[0]) and letters_t.numel() < need:
+            raise ValueError(f"letters_t holds {letters_t.numel()} bytes, the batch's letters end at byte {need}")
+        if h_lengths is not None:
+            bits = int(lengths_bits)
+            need = (n if bits == 8 else (n + 1) // 2 if bits == 4 else 8 * ((n + 23) // 24) if bits == 6
+                    else (3 * n + 7) // 8 + 1)
+            if h_lengths.shape[0] < need or lengths_t.numel() < need:
+                raise ValueError(f"{bits}-bit lengths of {n} records take {need} bytes")
+        if stream is None:
+            stream = torch.cuda.current_stream(letters_t.device)
+        form = dict(n=n, len_base=int(lengths_base), packed=_LETTER_CODES[letters], off_shift=off_shift,
+                    len_bits=int(lengths_bits))
+        b = _lib.WireBatch(letters=letters_t.data_ptr(), offsets=offsets_t.data_ptr(),
+                           lengths=lengths_t.data_ptr() if lengths_t is not None else None, device=1, **form)
+        meta = _lib.WireBatch(letters=None, offsets=_addr(h_offsets), lengths=_addr(h_lengths), device=0, **form)
+        out3 = np.zeros(3, np.uint64)
+        dense = np.zeros(max(n, 0) + 1, np.int64)
+        _lib.check(_lib.lib().moc_engine_decode_wire_device(self._h, ctypes.byref(b), ctypes.byref(meta),
+                                                            ctypes.c_void_p(stream.cuda_stream), _lib.ptr(out3),
+                                                            _lib.ptr(dense), None, None))
+        total = int(out3[2])
+        dev = letters_t.device
+        if letters == "bytes":
+            codes_t = letters_t
+        elif total == 0:
+            codes_t = torch.empty(0, dtype=torch.uint8, device=dev)
+        else:
+            codes_t = torch.as_tensor(_DeviceMemory(int(out3[0]), total, "|u1"), device=dev)
+        dense_t = offsets_t if not off_shift else torch.as_tensor(_DeviceMemory(int(out3[1]), n + 1, "<i8"), device=dev)
+        return codes_t, dense_t, dense
+
+    def decode_wire_into(self, batch, codes_t, offsets_t, host_meta=None, shift: int = 0, stream=None) -> np.ndarray:
+        """The same decode into the caller's tensors: ``codes_t`` (uint8, one element per letter of the batch) and
+        ``offsets_t`` (int64 [n + 1]) on this engine's GPU; nothing outside them is written. ``batch``: a WireSlice
+        (``shift`` > 0: through its sparse offsets) or a ``_lib.WireBatch`` — of host pointers (read in place when
+        page-locked, else copied in packed form), or of device pointers with ``host_meta``, the ``_lib.WireBatch``
+        of the host copies of its offsets and lengths. Queued on ``stream`` (default: the current stream) with no
+        sync; returns the host copy of the dense offsets."""
+        import torch
+
+        b, keep = (batch, None) if isinstance(batch, _lib.WireBatch) else wire_batch_of(batch, shift)
+        n = int(b.n)
+        assert codes_t.dtype == torch.uint8 and codes_t.is_contiguous()
+        assert offsets_t.dtype == torch.int64 and offsets_t.is_contiguous() and offsets_t.numel() == n + 1
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        out3 = np.zeros(3, np.uint64)
+        dense = np.zeros(max(n, 0) + 1, np.int64)
+        # the letter count from the host-readable offsets, before anything is queued: the kernels fill exactly that
+        sizes = np.zeros(2, np.int64)
+        _lib.check(_lib.lib().moc_cpu_decode_wire(ctypes.byref(b if host_meta is None else host_meta), None, None,
+                                                  _lib.ptr(sizes)))
+        if codes_t.numel() != int(sizes[0]):
+            raise ValueError(f"codes_t holds {codes_t.numel()} letters, the batch {int(sizes[0])}")
+        _lib.check(_lib.lib().moc_engine_decode_wire_device(
+            self._h, ctypes.byref(b), ctypes.byref(host_meta) if host_meta is not None else None,
+            ctypes.c_void_p(stream.cuda_stream), _lib.ptr(out3), _lib.ptr(dense),
+            ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr())))
+        del keep
+        return dense
+
+    def solve_profile_wire(self, ws, shift: int = 0):
+        """Host wire batch (a :class:`~..parallel.wire.WireSlice`; ``shift`` > 0: through its sparse offsets) ->
+        ``(prof, poffsets)`` as :meth:`solve_profile` returns them for the decoded records. The packed letters,
+        narrow lengths and sparse offsets are decoded on the GPU — read in place when page-locked (:meth:`pin`),
+        else copied to the device in packed form. Synchronous; ``stats()["kernels"]`` names ``wire``."""
+        b, keep = wire_batch_of(ws, shift)
+        poffsets = np.zeros(ws.n + 1, np.int64)
+        _lib.check(_lib.lib().moc_engine_solve_profile_wire(self._h, ctypes.byref(b), _lib.ptr(poffsets), None))
+        prof = np.zeros(max(int(poffsets[-1]), 1), dtype=PROFILE_DTYPE)  # never a NULL pointer: NULL asks for poffsets
+        _lib.check(_lib.lib().moc_engine_solve_profile_wire(self._h, ctypes.byref(b), _lib.ptr(poffsets),
+                                                            _lib.ptr(prof)))
+        del keep
+        return prof[:int(poffsets[-1])], poffsets
+
+    def solve_topk_wire(self, ws, K: int, shift: int = 0) -> np.ndarray:
+        """Host wire batch -> int32 [n, K, 3] top-K rows, as :meth:`solve_topk` on the decoded records (same chunks
+        under :meth:`set_profile_scratch`). See :meth:`solve_profile_wire`."""
+        K = _check_k(K)
+        b, keep = wire_batch_of(ws, shift)
+        out = np.zeros((ws.n, K, 3), np.int32)
+        _lib.check(_lib.lib().moc_engine_solve_topk_wire(self._h, ctypes.byref(b), K, _lib.ptr(out)))
+        del keep
+        return out
+
+    def solve_hits_wire(self, ws, min_score=None, thresholds=None, within=None, max_rows: Optional[int] = None,
+                        shift: int = 0):
+        """Host wire batch -> ``(rows, hoffsets)``, as :meth:`solve_hits` on the decoded records (exactly one of
+        ``min_score``, ``thresholds``, ``within``; ``max_rows`` and :meth:`hits_passes` as there). ``within`` takes
+        the records' best scores from :meth:`solve_topk_wire`. See :meth:`solve_profile_wire`."""
+        b, keep = wire_batch_of(ws, shift)
+        n = ws.n
+        m, t = _hits_thresholds(n, min_score, thresholds, within, lambda: self.solve_topk_wire(ws, 1, shift)[:, 0, 0])
+        hoffsets = np.zeros(n + 1, np.int64)
+        _lib.check(_lib.lib().moc_engine_solve_hits_wire(self._h, ctypes.byref(b), m, _lib.ptr(t),
+                                                         -1 if max_rows is None else int(max_rows), _lib.ptr(hoffsets),
+                                                         None, 0))
+        total = int(hoffsets[-1])
+        rows = np.zeros((total, 3), np.int32)
+        _lib.check(_lib.lib().moc_engine_hits_rows(_lib.ptr(rows) if total else None, total))
+        del keep
+        return rows, hoffsets
+
+    def report_wire(self, ws, rows, marks: bool = False, shift: int = 0):
+        """Host wire batch + result rows ([n, 3] or [n, K, 3]) -> the counts (and marker bytes) :meth:`report` returns
+        for the decoded records. See :meth:`solve_profile_wire`."""
+        b, keep = wire_batch_of(ws, shift)
+        n = ws.n
+        r, K, flat = _report_rows(rows, n)
+        total = int(ws.total)
+        counts = np.zeros((n, K, 4), np.int32)
+        m = np.zeros(max(K * total, 1), np.uint8) if marks else None
+        _lib.check(_lib.lib().moc_engine_report_wire(self._h, ctypes.byref(b), K, _lib.ptr(r), _lib.ptr(counts),
+                                                     _lib.ptr(m)))
+        del keep
+        counts = counts[:, 0] if flat else counts
+        return (counts, m[:K * total]) if marks else counts
+
     def kernel_times(self) -> tuple:
         """(kernel_ms, total_ms) of the last solve: the two fields a timed loop reads, without stats()'s dict."""
         v = self._stats_buf
@@ -723,7 +922,7 @@ class HipSearchEngine:
         d["r2"] = tuple(int(x) for x in list(v)[10:13])
         d["format"] = _lib.FORMAT_NAMES[int(d["format"])]
         d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16"), (16, "profile"),
-                                             (32, "report"), (64, "hits")) if int(d["kernels"]) & b]
+                                             (32, "report"), (64, "hits"), (128, "wire")) if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
 

@@ -107,6 +107,37 @@ class WireSlice:
         idx = np.minimum(np.arange(((self.n + (1 << shift) - 1) >> shift) + 1, dtype=np.int64) << shift, self.n)
         return np.ascontiguousarray(self.offsets[idx])
 
+    def wire_offsets(self, shift: int = 0) -> np.ndarray:
+        """The offsets array a wire call with ``shift`` reads: ``offsets`` itself (0), or the sparse offsets, made
+        once per shift through ``alloc`` and kept, so they can be page-locked like the slice's other arrays."""
+        if not shift:
+            return self.offsets
+        kept = self.__dict__.setdefault("_sparse", {})
+        if shift not in kept:
+            s = self.sparse_offsets(shift)
+            kept[shift] = self.alloc(f"sparse{shift}", np.int64, s.shape[0])
+            kept[shift][:] = s
+        return kept[shift]
+
+    # ---- profile, top-K, hits and report of the slice on a HipSearchEngine: decoded on the GPU from these arrays
+    def solve_profile_wire(self, engine, shift: int = 0):
+        return engine.solve_profile_wire(self, shift)
+
+    def solve_topk_wire(self, engine, K: int, shift: int = 0):
+        return engine.solve_topk_wire(self, K, shift)
+
+    def solve_hits_wire(self, engine, min_score=None, thresholds=None, within=None, max_rows=None, shift: int = 0):
+        return engine.solve_hits_wire(self, min_score, thresholds, within, max_rows, shift)
+
+    def report_wire(self, engine, rows, marks: bool = False, shift: int = 0):
+        return engine.report_wire(self, rows, marks, shift)
+
+    def decode_cpu(self, shift: int = 0):
+        """``(codes, offsets)`` of the slice from the native host decode (ops.align.decode_wire_cpu)."""
+        from ..ops.align import decode_wire_cpu
+
+        return decode_wire_cpu(self, shift)
+
     # ---- results
     def alloc_results(self, engine, fmt: str = "auto") -> np.ndarray:
         """Results in ``fmt`` (auto: the narrowest the engine can produce for this slice's lengths)."""
