@@ -54,7 +54,7 @@ COMM_OBJS := $(OBJ)/comm/comm.o $(OBJ)/comm/mpi_device_comm.o
 RCCL_OBJS := $(OBJ)/comm/rccl_comm.o
 HEADERS   := $(shell find csrc/include -name '*.h' -o -name '*.hpp')
 
-.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san hits-san wire-san
+.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san hits-san wire-san peaks-san
 
 all: build
 build: lib final $(GPU_PLUGIN)
@@ -245,6 +245,13 @@ wire-san: $(BUILD)/wire_san
 	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/wire_san
 $(BUILD)/wire_san: csrc/tests/wire_san.cpp $(PSAN_OBJS) $(HEADERS)
 	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/wire_san.cpp $(PSAN_OBJS) -ldl
+
+# stand-alone ASan/UBSan check of the CPU engine's distinct placements: peaks_filter against the definition as a
+# double loop, distinct top-K and distinct hits with rows in heap blocks of exactly cap rows (own main, host code only)
+peaks-san: $(BUILD)/peaks_san
+	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/peaks_san
+$(BUILD)/peaks_san: csrc/tests/peaks_san.cpp $(PSAN_OBJS) $(HEADERS)
+	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/peaks_san.cpp $(PSAN_OBJS) -ldl
 
 # parser throughput (count vs fill, SIMD A/B): build/fill_bench [records]
 $(BUILD)/fill_bench: tools/fill_bench.cpp $(CPU_OBJS) $(HEADERS)

@@ -242,6 +242,39 @@ int moc_engine_solve_hits_wire(void* e, const moc_wire_batch* b, int32_t min_sco
                                int64_t max_rows_hint, int64_t* hoffsets, moc_result* rows, int64_t cap);
 int moc_engine_report_wire(void* e, const moc_wire_batch* b, int K, const moc_result* rows, int32_t* counts,
                            uint8_t* marks);
+/* ---- distinct placements (moc/cpu_engine.hpp peaks_filter) ----
+ * Top-K and hits over the peaks of radius `radius` only: entry o of a record's profile is a peak iff no entry o' with
+ * 0 < |o - o'| <= radius inside the profile has a higher score, or an equal score and a smaller offset. Arguments,
+ * shapes and contracts are those of the calls they are named after (top-K pads with (INT32_MIN, 0, 0) past the
+ * record's peaks; the hits index is exact and the capacity contract unchanged); radius = 0 gives their results,
+ * a radius outside 0 .. moc_peaks_max_radius() is an error. */
+int moc_peaks_max_radius(void);
+/* out3: the largest radius, the most profile entries of a record the GPU's wave-per-record peak kernel takes, and the
+ * entries per tile of its tile kernel (moc/kernel_bounds.hpp); no GPU needed */
+int moc_peaks_geometry(int32_t* out3);
+int moc_cpu_topk_distinct(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                          const int64_t* offsets, int64_t n, int semantics, int threads, int K, int64_t radius,
+                          moc_result* out);
+int moc_cpu_hits_distinct(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                          const int64_t* offsets, int64_t n, int semantics, int threads, int32_t min_score,
+                          const int32_t* thresholds, int64_t radius, int64_t* hoffsets, moc_result* rows, int64_t cap);
+int moc_engine_solve_topk_distinct(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int K,
+                                   int64_t radius, moc_result* out);
+int moc_engine_solve_topk_device_distinct(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                          const int64_t* h_offsets, int64_t n, int K, int64_t radius, moc_result* d_out,
+                                          void* stream);
+int moc_engine_solve_topk_wire_distinct(void* e, const moc_wire_batch* b, int K, int64_t radius, moc_result* out);
+/* rows: as moc_engine_solve_hits (kept for this thread's next moc_engine_hits_rows; moc_engine_hits_passes tells) */
+int moc_engine_solve_hits_distinct(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t min_score,
+                                   const int32_t* thresholds, int64_t radius, int64_t max_rows_hint, int64_t* hoffsets,
+                                   moc_result* rows, int64_t cap);
+int moc_engine_solve_hits_device_distinct(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                          const int64_t* h_offsets, int64_t n, int32_t min_score,
+                                          const int32_t* d_thresholds, int64_t radius, int64_t* d_hoffsets,
+                                          moc_result* d_rows, int64_t cap, void* stream);
+int moc_engine_solve_hits_wire_distinct(void* e, const moc_wire_batch* b, int32_t min_score, const int32_t* thresholds,
+                                        int64_t radius, int64_t max_rows_hint, int64_t* hoffsets, moc_result* rows,
+                                        int64_t cap);
 /* stats: kernel_ms, total_ms, h2d_bytes, d2h_bytes, chunks, cells, records, direct, format, kernels,
  * r2 smin, r2 kw, r2 j, forms (moc::bounds::FormBits of the last solve) */
 int moc_engine_stats(void* e, double* out14);

@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "moc/common.hpp"
+#include "moc/kernel_bounds.hpp"
 #include "moc/problem.hpp"
 #include "moc/score_table.hpp"
 
@@ -76,8 +77,10 @@ void profile_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const
 // Top-K, 1 <= K <= kMaxTopK: out[i*K .. i*K+K) = record i's min(K, C_i) best offsets in better() order (higher
 // score, then smaller n), each as (score, n, that offset's profile k), then no_candidate() rows. Row 0 is
 // solve_record's result. One record's profile exists at a time per thread, never the batch's.
+// radius > 0: the distinct form — only the record's peaks of that radius (peaks_filter below) are ranked:
+// min(K, #peaks) rows, then no_candidate() rows; row 0 is still solve_record's result.
 void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
-                    Semantics sem, int num_threads = 0);
+                    Semantics sem, int num_threads = 0, int64_t radius = 0);
 
 // ---- threshold hits: every offset that scores at least a threshold
 // Hits of record i under threshold t_i (thresholds[i], or min_score for every record when thresholds is null): the
@@ -89,7 +92,24 @@ void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const Re
 // Two phases, counts then fill; one record's profile exists at a time per thread, never the batch's.
 void hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int32_t min_score,
                     const int32_t* thresholds, int64_t* hoffsets, Result* rows, int64_t cap, Semantics sem,
-                    int num_threads = 0);
+                    int num_threads = 0, int64_t radius = 0);
+
+// ---- distinct placements: the peak filter of top-K and hits
+// A mutated candidate (o, k) aligns letters < k on diagonal o and letters >= k on diagonal o + 1, so a placement
+// at offset n has a shadow at n - 1 with k = 1 that scores within one letter pair of it. Entry o of a C-entry
+// profile is a PEAK OF RADIUS R (0 <= R <= bounds::kPeaksMaxRadius) iff no entry o' with 0 < |o - o'| <= R and
+// 0 <= o' < C is better() than it: a higher score, or an equal score and a smaller offset. Equivalently the
+// order-free key (score ^ 2^31) << 32 | (2^32 - 1 - o) of entry o is the maximum over its window clipped to [0, C).
+//   R = 0: every entry is a peak (the plain results). R >= C - 1: exactly one, solve_record's result.
+//   A run of equal scores keeps only its first entry: an entry is suppressed by an equal entry to its left within
+//   R even when that entry is suppressed itself. Local-maximum suppression, not greedy: scores 10, 9, 8 at R = 1
+//   have one peak, the 10 (the 8 is suppressed by the 9, which the 10 suppresses). Every entry depends on its
+//   window only.
+//   Whatever suppresses an entry scores at least as much, so a threshold does not interact: distinct hits are the
+//   peaks with score >= t_i; distinct top-K ranks the peaks.
+// peak[o] = 1 or 0 for o in [0, C); O(C) for any R (a monotonic deque). Throws Error for R out of range.
+void peaks_filter(const ProfileEntry* prof, int64_t C, int64_t radius, uint8_t* peak);
+void check_peaks_radius(int64_t radius);  // throws Error unless 0 <= radius <= bounds::kPeaksMaxRadius
 
 // ---- alignment report: the signs under a result row's letter pairs
 // A row is a Result {score, n, k} of record i (L2 letters) against Seq1; rows[i*K .. i*K+K) belong to record i.

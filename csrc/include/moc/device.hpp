@@ -368,6 +368,34 @@ struct HitsArgs {
 };
 // Queues count, scan (one or three launches) and, when cap > 0, the compaction on `stream`.
 void launch_hits(const HitsArgs& ha, hipStream_t stream);
+// The prefix sum alone (one or three launches): hoffsets[rec0 + 1 ..] from per-record counts to running totals.
+void launch_hits_scan(const HitsArgs& ha, hipStream_t stream);
+
+// ---- distinct placements (peaks_kernels.hip; definitions: moc/cpu_engine.hpp peaks_filter)
+// One chunk of consecutive records [rec0, rec0 + n_rec) whose profile lies at prof[poffsets[r] - base + o]:
+// peak[poffsets[r] - base + o] <- 1 when entry o is a peak of radius `radius` of record r, else 0, for every entry
+// of the chunk. The host states what the chunk holds: any_short (a record of 1 .. bounds::kPeaksWaveEntries
+// entries: the wave kernel runs), max_tiles (tiles of bounds::kPeaksTile entries of its longest record when that
+// is longer, else 0: the tile kernel runs) and lds_keys (the most keys a tile of the chunk puts into LDS, halo
+// included: at most kPeaksTile + 2 kPeaksMaxRadius).
+struct PeaksArgs {
+  const ProfileEntry* prof = nullptr;
+  const int64_t* poffsets = nullptr;
+  int64_t base = 0;
+  int64_t prof_entries = 0;  // entries of `prof` and bytes of `peak` (debug builds check indices against it)
+  int64_t rec0 = 0, n_rec = 0;
+  int32_t radius = 0;        // 1 .. bounds::kPeaksMaxRadius
+  int32_t any_short = 0;
+  int32_t max_tiles = 0;
+  int32_t lds_keys = 0;
+  int32_t num_cus = 256;
+  uint8_t* peak = nullptr;
+};
+void launch_peaks(const PeaksArgs& a, hipStream_t stream);
+// launch_topk_select / launch_hits over the peaks only (peak: what launch_peaks stored for the same chunk)
+void launch_topk_select_peaks(const ProfileArgs& pa, const uint8_t* peak, int64_t n_rec, int K, Result* out,
+                              hipStream_t stream);
+void launch_hits_peaks(const HitsArgs& ha, const uint8_t* peak, hipStream_t stream);
 
 // Loads every kernel file's code object onto the current device now (HIP loads them lazily, at the first
 // launch from each file: milliseconds inside the first timed search of a job otherwise).
@@ -381,6 +409,7 @@ void preload_profile_kernels();
 void preload_report_kernels();
 void preload_hits_kernels();
 void preload_wire_kernels();
+void preload_peaks_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -394,6 +423,7 @@ enum PreloadSet : unsigned {
   kPreloadReport = 128,  // report_kernels.hip: likewise
   kPreloadHits = 256,    // hits_kernels.hip: likewise
   kPreloadWire = 512,    // wire_kernels.hip: likewise
+  kPreloadPeaks = 1024,  // peaks_kernels.hip: likewise
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -406,9 +436,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadReport) preload_report_kernels();
   if (set & kPreloadHits) preload_hits_kernels();
   if (set & kPreloadWire) preload_wire_kernels();
+  if (set & kPreloadPeaks) preload_peaks_kernels();
 }
 // "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
-// profile, report, hits, wire;
+// profile, report, hits, wire, peaks;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

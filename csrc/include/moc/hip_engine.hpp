@@ -61,7 +61,8 @@ struct EngineStats {
   int32_t format = 0;    // ResultFormat of the last solve
   int32_t kernels = 0;   // bitmask of kernels used: 1 swipe (lane/record), 2 short (lane/offset), 4 tiles
                          // (LUT tile kernel), 8 tile16, 16 profile (per-offset profile / top-K), 32 report,
-                         // 64 hits (count / scan / compact, next to 16), 128 wire (decode kernels of a *_wire call)
+                         // 64 hits (count / scan / compact, next to 16), 128 wire (decode kernels of a *_wire call),
+                         // 256 peaks (the peak filter and masked select / hits kernels of a distinct call)
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -132,13 +133,18 @@ class HipEngine {
   // EngineOptions::profile_scratch_bytes.
   void solve_profile_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
                             ProfileEntry* d_prof, hipStream_t stream);
+  // radius (here and in every top-K / hits call below): 0 = the plain results, through exactly the launches above;
+  // 1 .. bounds::kPeaksMaxRadius = the distinct forms (moc/cpu_engine.hpp peaks_filter) — per chunk the peak kernels
+  // (csrc/src/hip/peaks_kernels.hip) run between the profile kernel and the select / hits launches, on the same
+  // stream with no sync, over one byte of peak marks per scratch entry (counted under profile_scratch_bytes), and
+  // the select / count / compact kernels take their masked forms. Anything else throws.
   void solve_topk_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n, int K,
-                         Result* d_out, hipStream_t stream);
+                         Result* d_out, hipStream_t stream, int64_t radius = 0);
   // Host forms (upload through the pooled buffers; synchronous). prof_out holds poffsets_out[n] entries;
   // poffsets_out (n + 1) is filled first and may be computed beforehand with profile_offsets().
   void solve_profile(const uint8_t* codes, const int64_t* offsets, int64_t n, ProfileEntry* prof_out,
                      int64_t* poffsets_out);
-  void solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, Result* out);
+  void solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, Result* out, int64_t radius = 0);
   // poffsets[0..n]: record i's profile starts at entry poffsets[i] (this problem's L1 and semantics)
   void profile_offsets(const int64_t* offsets, int64_t n, int64_t* poffsets) const;
   void set_profile_scratch(int64_t bytes);
@@ -157,13 +163,13 @@ class HipEngine {
   // with a null d_rows counts only).
   void solve_hits_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
                          int32_t min_score, const int32_t* d_thresholds, int64_t* d_hoffsets, Result* d_rows,
-                         int64_t cap, hipStream_t stream);
+                         int64_t cap, hipStream_t stream, int64_t radius = 0);
   // Host form (uploads through the pooled buffers; synchronous; fills stats()). thresholds: host int32 [n] or null.
   // Optimistic: one pass with room for max(max_rows_hint, 1) rows (hint < 0: 4 n), and exactly one more with
   // hoffsets[n] rows when that was too few (the counts are exact, so the second pass fits). hits_passes() tells.
   void solve_hits(const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t min_score,
                   const int32_t* thresholds, int64_t* hoffsets_out, std::vector<Result>& rows_out,
-                  int64_t max_rows_hint = -1);
+                  int64_t max_rows_hint = -1, int64_t radius = 0);
   int hits_passes() const { return hits_passes_; }  // passes of the last solve_hits (1 or 2; 0 for n <= 0)
   // Device time (ms) of the count + scan + compact launches of the last hits call; as topk_select_ms().
   double hits_select_ms() { return topk_select_ms(); }
@@ -208,9 +214,9 @@ class HipEngine {
   // hits_passes() and capacity contract. Synchronous; fill stats() (kernels bit 128 when a decode kernel ran,
   // h2d_bytes in wire-format bytes). The whole batch is decoded at once.
   void solve_profile_wire(const WireBatch& b, ProfileEntry* prof_out, int64_t* poffsets_out);
-  void solve_topk_wire(const WireBatch& b, int K, Result* out);
+  void solve_topk_wire(const WireBatch& b, int K, Result* out, int64_t radius = 0);
   void solve_hits_wire(const WireBatch& b, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
-                       std::vector<Result>& rows_out, int64_t max_rows_hint = -1);
+                       std::vector<Result>& rows_out, int64_t max_rows_hint = -1, int64_t radius = 0);
   void report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks);
   // poffsets[0..n] of a host wire batch (profile_offsets of its decoded lengths; no GPU work)
   void wire_profile_offsets(const WireBatch& b, int64_t* poffsets) const;
@@ -278,9 +284,9 @@ class HipEngine {
   Placed placed_upload(const std::vector<int64_t>& rebased, int64_t n) const;
   Placed place_wire(const WireBatch& b, size_t out_bytes);
   void profile_placed(const Placed& p, ProfileEntry* prof_out, const int64_t* poffsets, Stopwatch& wall);
-  void topk_placed(const Placed& p, int K, Result* out, Stopwatch& wall);
+  void topk_placed(const Placed& p, int K, Result* out, Stopwatch& wall, int64_t radius);
   void hits_placed(const Placed& p, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
-                   std::vector<Result>& rows_out, int64_t max_rows_hint, Stopwatch& wall);
+                   std::vector<Result>& rows_out, int64_t max_rows_hint, Stopwatch& wall, int64_t radius);
   void report_placed(const Placed& p, int K, const Result* rows, int32_t* counts, uint8_t* marks, Stopwatch& wall);
   static size_t report_out_bytes(int64_t n, int K, int64_t mark_letters);
   void host_call_stats(Stopwatch& wall, double kernel_ms, const Placed& p, size_t d2h_bytes);
@@ -320,7 +326,7 @@ class HipEngine {
     int64_t cap;
   };
   void run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n, int K,
-                   void* d_dst, hipStream_t stream, const HitsCall* hits = nullptr);
+                   void* d_dst, hipStream_t stream, const HitsCall* hits = nullptr, int64_t radius = 0);
 
   EngineOptions opt_;
   int device_ = 0;

@@ -116,6 +116,19 @@ constexpr int32_t kHitsScanThreads = 256;
 constexpr int32_t kHitsScanBlockRecords = 4 * kHitsScanThreads;  // four consecutive counts per thread
 constexpr int32_t kHitsScanSumsPerPass = 2 * kHitsScanThreads;   // two consecutive sums per thread and pass
 
+// ---- distinct placements (peaks_kernels.hip; definitions: moc/cpu_engine.hpp peaks_filter): the peak filter's
+// radius R ranges over 0 .. kPeaksMaxRadius — at least the longest record of the assignment (2000 letters), so "one
+// placement per record length" is expressible. Records of at most kPeaksWaveEntries profile entries take one wave
+// each; longer ones a workgroup per tile of kPeaksTile entries, which holds the tile and an R-entry halo on each
+// side in LDS as 8-byte keys: (kPeaksTile + 2 kPeaksMaxRadius) * 8 bytes = 48 KiB.
+constexpr int32_t kPeaksMaxRadius = 2048;
+constexpr int32_t kPeaksWaveEntries = 64;
+constexpr int32_t kPeaksTile = 2048;
+constexpr int32_t kPeaksThreads = 256;
+constexpr int32_t kPeaksKeysPerThread = (kPeaksTile + 2 * kPeaksMaxRadius) / kPeaksThreads;  // 24
+static_assert((kPeaksTile + 2 * kPeaksMaxRadius) % kPeaksThreads == 0, "peaks: whole keys per thread");
+static_assert((kPeaksTile + 2 * kPeaksMaxRadius) * 8 <= 64 * 1024, "peaks: tile + halo within one workgroup's LDS");
+
 // Form bits reported per solve (EngineStats::forms; Python: stats()["forms"]).
 enum FormBits : int32_t {
   kFormSwipeKBits = 1,    // swipe, int16 keys with k bits

@@ -672,6 +672,100 @@ int moc_engine_report_wire(void* e, const moc_wire_batch* w, int K, const moc_re
   });
 }
 
+// ---- distinct placements: the calls above over the peaks of a radius
+int moc_peaks_max_radius(void) { return moc::bounds::kPeaksMaxRadius; }
+
+int moc_peaks_geometry(int32_t* out3) {
+  out3[0] = moc::bounds::kPeaksMaxRadius;
+  out3[1] = moc::bounds::kPeaksWaveEntries;
+  out3[2] = moc::bounds::kPeaksTile;
+  return 0;
+}
+
+int moc_cpu_topk_distinct(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                          const int64_t* offsets, int64_t n, int semantics, int threads, int K, int64_t radius,
+                          moc_result* out) {
+  return guard([&] {
+    moc::Weights w = weights_of(weights4);
+    moc::RecordBatch b = view_batch(codes, offsets, n);
+    moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
+    moc::ScoreTable t = moc::ScoreTable::build(w);
+    moc::topk_batch_cpu(t, seq1, L1, b, K, reinterpret_cast<moc::Result*>(out), static_cast<moc::Semantics>(semantics),
+                        threads, radius);
+  });
+}
+
+int moc_cpu_hits_distinct(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                          const int64_t* offsets, int64_t n, int semantics, int threads, int32_t min_score,
+                          const int32_t* thresholds, int64_t radius, int64_t* hoffsets, moc_result* rows, int64_t cap) {
+  return guard([&] {
+    moc::Weights w = weights_of(weights4);
+    moc::RecordBatch b = view_batch(codes, offsets, n);
+    moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
+    moc::ScoreTable t = moc::ScoreTable::build(w);
+    moc::hits_batch_cpu(t, seq1, L1, b, min_score, thresholds, hoffsets, reinterpret_cast<moc::Result*>(rows), cap,
+                        static_cast<moc::Semantics>(semantics), threads, radius);
+  });
+}
+
+int moc_engine_solve_topk_distinct(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int K,
+                                   int64_t radius, moc_result* out) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_topk(codes, offsets, n, K, reinterpret_cast<moc::Result*>(out), radius);
+  });
+}
+
+int moc_engine_solve_topk_device_distinct(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                          const int64_t* h_offsets, int64_t n, int K, int64_t radius, moc_result* d_out,
+                                          void* stream) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_topk_device(d_codes, d_offsets, h_offsets, n, K,
+                                                       reinterpret_cast<moc::Result*>(d_out),
+                                                       static_cast<hipStream_t>(stream), radius);
+  });
+}
+
+int moc_engine_solve_topk_wire_distinct(void* e, const moc_wire_batch* w, int K, int64_t radius, moc_result* out) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_topk_wire(wire_batch(w), K, reinterpret_cast<moc::Result*>(out), radius);
+  });
+}
+
+int moc_engine_solve_hits_distinct(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t min_score,
+                                   const int32_t* thresholds, int64_t radius, int64_t max_rows_hint, int64_t* hoffsets,
+                                   moc_result* rows, int64_t cap) {
+  return guard([&] {
+    if (cap < 0 || (cap > 0 && !rows)) throw moc::Error("hits: cap rows need a rows buffer");
+    static_cast<moc::HipEngine*>(e)->solve_hits(codes, offsets, n, min_score, thresholds, hoffsets, g_hits_rows,
+                                                max_rows_hint, radius);
+    const size_t m = std::min(g_hits_rows.size(), static_cast<size_t>(cap));
+    if (m) std::memcpy(rows, g_hits_rows.data(), sizeof(moc::Result) * m);
+  });
+}
+
+int moc_engine_solve_hits_device_distinct(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                          const int64_t* h_offsets, int64_t n, int32_t min_score,
+                                          const int32_t* d_thresholds, int64_t radius, int64_t* d_hoffsets,
+                                          moc_result* d_rows, int64_t cap, void* stream) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_hits_device(d_codes, d_offsets, h_offsets, n, min_score, d_thresholds,
+                                                       d_hoffsets, reinterpret_cast<moc::Result*>(d_rows), cap,
+                                                       static_cast<hipStream_t>(stream), radius);
+  });
+}
+
+int moc_engine_solve_hits_wire_distinct(void* e, const moc_wire_batch* w, int32_t min_score, const int32_t* thresholds,
+                                        int64_t radius, int64_t max_rows_hint, int64_t* hoffsets, moc_result* rows,
+                                        int64_t cap) {
+  return guard([&] {
+    if (cap < 0 || (cap > 0 && !rows)) throw moc::Error("hits: cap rows need a rows buffer");
+    static_cast<moc::HipEngine*>(e)->solve_hits_wire(wire_batch(w), min_score, thresholds, hoffsets, g_hits_rows,
+                                                     max_rows_hint, radius);
+    const size_t m = std::min(g_hits_rows.size(), static_cast<size_t>(cap));
+    if (m) std::memcpy(rows, g_hits_rows.data(), sizeof(moc::Result) * m);
+  });
+}
+
 int moc_engine_stats(void* e, double* out14) {
   return guard([&] {
     double* out13 = out14;

@@ -296,27 +296,92 @@ void for_each_profile(const ScoreTable& t, const uint8_t* s1, int64_t L1, const 
 }
 }  // namespace
 
+void check_peaks_radius(int64_t radius) {
+  if (radius < 0 || radius > bounds::kPeaksMaxRadius)
+    throw Error("distinct: radius must be in 0.." + std::to_string(bounds::kPeaksMaxRadius) + ", got " +
+                std::to_string(radius));
+}
+
+namespace {
+inline uint64_t profile_key(const ProfileEntry& e, int64_t o) {
+  return (static_cast<uint64_t>(static_cast<uint32_t>(e.score) ^ 0x80000000u) << 32) |
+         (0xffffffffu - static_cast<uint32_t>(o));
+}
+}  // namespace
+
+// Sliding-window maximum of the keys over [o - R, o + R] clipped to [0, C): dq holds the offsets of the window's
+// candidates for the maximum, keys decreasing from front to back. Entry o is a peak iff the front is o itself.
+void peaks_filter(const ProfileEntry* prof, int64_t C, int64_t radius, uint8_t* peak) {
+  check_peaks_radius(radius);
+  if (C <= 0) return;
+  if (radius == 0) {
+    std::fill(peak, peak + C, uint8_t{1});
+    return;
+  }
+  thread_local std::vector<int64_t> dq;  // a ring would do; the offsets only ever move forward
+  dq.resize(static_cast<size_t>(C));
+  int64_t head = 0, tail = 0, next = 0;  // dq[head .. tail); entries [0, next) have entered the window
+  for (int64_t o = 0; o < C; ++o) {
+    const int64_t hi = std::min(C - 1, o + radius);
+    for (; next <= hi; ++next) {
+      const uint64_t k = profile_key(prof[next], next);
+      while (tail > head && profile_key(prof[dq[tail - 1]], dq[tail - 1]) < k) --tail;
+      dq[tail++] = next;
+    }
+    while (dq[head] < o - radius) ++head;  // never empties: o itself entered and nothing after it has left
+    peak[o] = dq[head] == o ? 1 : 0;
+  }
+}
+
 void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
-                    Semantics sem, int num_threads) {
+                    Semantics sem, int num_threads, int64_t radius) {
   if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  check_peaks_radius(radius);
   for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
     thread_local std::vector<uint64_t> keys;
-    select_topk(prof, C, K, out + i * K, keys);
+    if (radius == 0) {
+      select_topk(prof, C, K, out + i * K, keys);
+      return;
+    }
+    thread_local std::vector<uint8_t> peak;
+    peak.resize(static_cast<size_t>(C));
+    peaks_filter(prof, C, radius, peak.data());
+    keys.clear();
+    for (int64_t o = 0; o < C; ++o)
+      if (peak[o]) keys.push_back(profile_key(prof[o], o));
+    const int64_t m = std::min<int64_t>(K, static_cast<int64_t>(keys.size()));
+    std::partial_sort(keys.begin(), keys.begin() + m, keys.end(), std::greater<uint64_t>());
+    Result* row = out + i * K;
+    for (int64_t j = 0; j < m; ++j) {
+      const int64_t o = 0xffffffffu - static_cast<uint32_t>(keys[j]);
+      row[j] = Result{prof[o].score, static_cast<int32_t>(o), prof[o].k};
+    }
+    for (int64_t j = m; j < K; ++j) row[j] = no_candidate();
   });
 }
 
 void hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int32_t min_score,
                     const int32_t* thresholds, int64_t* hoffsets, Result* rows, int64_t cap, Semantics sem,
-                    int num_threads) {
+                    int num_threads, int64_t radius) {
   if (cap < 0 || (cap > 0 && !rows)) throw Error("hits: cap rows need a rows buffer (cap = 0 counts only)");
+  check_peaks_radius(radius);
   const int64_t n = batch.size();
   auto threshold = [&](int64_t i) { return thresholds ? thresholds[i] : min_score; };
+  // the record's peak marks (radius > 0), or null: every entry counts
+  auto peaks_of = [&](const ProfileEntry* prof, int64_t C) -> const uint8_t* {
+    if (radius == 0) return nullptr;
+    thread_local std::vector<uint8_t> peak;
+    peak.resize(static_cast<size_t>(C));
+    peaks_filter(prof, C, radius, peak.data());
+    return peak.data();
+  };
   // phase 1: counts into hoffsets[i + 1], then their running totals
   hoffsets[0] = 0;
   for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
     const int32_t ti = threshold(i);
+    const uint8_t* peak = peaks_of(prof, C);
     int64_t c = 0;
-    for (int64_t o = 0; o < C; ++o) c += prof[o].score >= ti ? 1 : 0;
+    for (int64_t o = 0; o < C; ++o) c += prof[o].score >= ti && (!peak || peak[o]) ? 1 : 0;
     hoffsets[i + 1] = c;
   });
   for (int64_t i = 0; i < n; ++i) hoffsets[i + 1] += hoffsets[i];
@@ -326,8 +391,9 @@ void hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const Re
     int64_t at = hoffsets[i];
     if (at >= cap || at == hoffsets[i + 1]) return;
     const int32_t ti = threshold(i);
+    const uint8_t* peak = peaks_of(prof, C);
     for (int64_t o = 0; o < C && at < cap; ++o)
-      if (prof[o].score >= ti) rows[at++] = Result{prof[o].score, static_cast<int32_t>(o), prof[o].k};
+      if (prof[o].score >= ti && (!peak || peak[o])) rows[at++] = Result{prof[o].score, static_cast<int32_t>(o), prof[o].k};
   });
 }
 

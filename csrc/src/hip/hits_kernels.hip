@@ -170,17 +170,22 @@ void preload_hits_kernels() {
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&hits_count_kernel));
 }
 
-void launch_hits(const HitsArgs& ha, hipStream_t stream) {
+void launch_hits_scan(const HitsArgs& ha, hipStream_t stream) {
   if (ha.n_rec <= 0) return;
-  const unsigned wave_blocks = static_cast<unsigned>((ha.n_rec + kWavesPerBlock - 1) / kWavesPerBlock);
   const int64_t n_sums = (ha.n_rec + bounds::kHitsScanBlockRecords - 1) / bounds::kHitsScanBlockRecords;
-  hipLaunchKernelGGL(hits_count_kernel, dim3(wave_blocks), dim3(kBlock), 0, stream, ha);
   if (n_sums > 1) {
     hipLaunchKernelGGL(hits_block_sums_kernel, dim3(static_cast<unsigned>(n_sums)), dim3(kBlock), 0, stream, ha);
     hipLaunchKernelGGL(hits_scan_sums_kernel, dim3(1), dim3(kBlock), 0, stream, ha, n_sums);
   }
   hipLaunchKernelGGL(hits_rescan_kernel, dim3(static_cast<unsigned>(n_sums)), dim3(kBlock), 0, stream, ha,
                      n_sums > 1 ? 1 : 0);
+}
+
+void launch_hits(const HitsArgs& ha, hipStream_t stream) {
+  if (ha.n_rec <= 0) return;
+  const unsigned wave_blocks = static_cast<unsigned>((ha.n_rec + kWavesPerBlock - 1) / kWavesPerBlock);
+  hipLaunchKernelGGL(hits_count_kernel, dim3(wave_blocks), dim3(kBlock), 0, stream, ha);
+  launch_hits_scan(ha, stream);
   if (ha.cap > 0 && ha.rows)
     hipLaunchKernelGGL(hits_compact_kernel, dim3(wave_blocks), dim3(kBlock), 0, stream, ha);
 }

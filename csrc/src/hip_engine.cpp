@@ -111,7 +111,7 @@ int parse_preload_set(const char* s) {
                {"swipe", kPreloadSwipeByte | kPreloadSwipeP33}, {"swipe8", kPreloadSwipeByte},
                {"swipe33", kPreloadSwipeP33}, {"tile16", kPreloadTile16}, {"mfma", kPreloadMfma},
                {"profile", kPreloadProfile}, {"report", kPreloadReport}, {"hits", kPreloadHits},
-               {"wire", kPreloadWire}};
+               {"wire", kPreloadWire}, {"peaks", kPreloadPeaks}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -1006,9 +1006,10 @@ double HipEngine::topk_select_ms() {
 // followed by count, prefix sum and compaction into the call's buffers. Plan buffer: poffsets (n + 1) | every
 // chunk's wave starts.
 void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
-                            int K, void* d_dst, hipStream_t stream, const HitsCall* hits) {
+                            int K, void* d_dst, hipStream_t stream, const HitsCall* hits, int64_t radius) {
   if (!have_problem_) throw Error("HipEngine: profile / top-K before set_problem");
   if (K < 0 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  check_peaks_radius(radius);
   finish_wire();
   MOC_HIP_CHECK(hipSetDevice(device_));
   ev_select_used_ = 0;
@@ -1017,6 +1018,8 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   if (!stream) stream = s_compute_;
   TraceRange tr(hits ? "moc.solve_hits_device" : K ? "moc.solve_topk_device" : "moc.solve_profile_device");
   const bool chunked = K || hits;  // through the bounded scratch
+  const bool peaks = chunked && radius > 0;  // the distinct forms: a byte of peak marks beside every scratch entry
+  const int64_t entry_bytes = static_cast<int64_t>(sizeof(ProfileEntry)) + (peaks ? 1 : 0);
   std::vector<int64_t> poff(static_cast<size_t>(n) + 1);
   profile_offsets(h_offsets, n, poff.data());
   int64_t sum_l2 = 0, max_l2 = 0, cells = 0, max_need = 1;
@@ -1037,7 +1040,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
     size_t starts_at, n_starts;
   };
   std::vector<Chunk> chunks;
-  const int64_t cap_entries = std::max<int64_t>(1, opt_.profile_scratch_bytes / static_cast<int64_t>(sizeof(ProfileEntry)));
+  const int64_t cap_entries = std::max<int64_t>(1, opt_.profile_scratch_bytes / entry_bytes);
   for (int64_t r0 = 0; r0 < n;) {
     int64_t r1 = r0 + 1;
     if (!chunked)
@@ -1062,7 +1065,10 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   MOC_HIP_CHECK(hipEventSynchronize(ev_plan_));  // previous call's plan buffers are free again
   ensure(d_plan_, d_plan_cap_, plan_bytes);
   ensure_host(h_plan_, h_plan_cap_, plan_bytes);
-  if (chunked) ensure(d_prof_scratch_, d_prof_scratch_cap_, sizeof(ProfileEntry) * static_cast<size_t>(std::max<int64_t>(max_entries, 1)));
+  // scratch: the largest chunk's profile entries | its peak marks (distinct forms)
+  const size_t scratch_entries = static_cast<size_t>(std::max<int64_t>(max_entries, 1));
+  if (chunked) ensure(d_prof_scratch_, d_prof_scratch_cap_, static_cast<size_t>(entry_bytes) * scratch_entries);
+  uint8_t* d_peak = peaks ? static_cast<uint8_t*>(d_prof_scratch_) + sizeof(ProfileEntry) * scratch_entries : nullptr;
   if (hits)
     ensure(d_hits_sums_, d_hits_sums_cap_,
            sizeof(int64_t) * static_cast<size_t>((max_records + bounds::kHitsScanBlockRecords - 1) / bounds::kHitsScanBlockRecords));
@@ -1094,6 +1100,29 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
     dev::launch_offset_profile(pv, bv, pa, stream);
     if (chunked) {
       if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
+      if (peaks) {
+        dev::PeaksArgs ka;
+        ka.prof = pa.prof;
+        ka.poffsets = pa.poffsets;
+        ka.base = pa.base;
+        ka.prof_entries = pa.prof_entries;
+        ka.rec0 = c.r0;
+        ka.n_rec = c.r1 - c.r0;
+        ka.radius = static_cast<int32_t>(radius);
+        ka.num_cus = cfg_.num_cus;
+        ka.peak = d_peak;
+        int64_t max_c = 0;
+        for (int64_t r = c.r0; r < c.r1; ++r) {
+          const int64_t C = poff[r + 1] - poff[r];
+          if (C >= 1 && C <= bounds::kPeaksWaveEntries) ka.any_short = 1;
+          max_c = std::max(max_c, C);
+        }
+        if (max_c > bounds::kPeaksWaveEntries) {
+          ka.max_tiles = static_cast<int32_t>((max_c + bounds::kPeaksTile - 1) / bounds::kPeaksTile);
+          ka.lds_keys = static_cast<int32_t>(std::min<int64_t>(bounds::kPeaksTile, max_c) + 2 * std::min<int64_t>(radius, max_c - 1));
+        }
+        dev::launch_peaks(ka, stream);
+      }
       if (hits) {
         dev::HitsArgs ha;
         ha.prof = pa.prof;
@@ -1108,7 +1137,12 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
         ha.sums = static_cast<int64_t*>(d_hits_sums_);
         ha.rows = hits->d_rows;
         ha.cap = hits->cap;
-        dev::launch_hits(ha, stream);
+        if (peaks)
+          dev::launch_hits_peaks(ha, d_peak, stream);
+        else
+          dev::launch_hits(ha, stream);
+      } else if (peaks) {
+        dev::launch_topk_select_peaks(pa, d_peak, c.r1 - c.r0, K, static_cast<Result*>(d_dst), stream);
       } else {
         dev::launch_topk_select(pa, c.r1 - c.r0, K, static_cast<Result*>(d_dst), stream);
       }
@@ -1122,7 +1156,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   stats_.cells = cells;
   stats_.records = n;
   stats_.chunks = static_cast<int64_t>(chunks.size());
-  stats_.kernels = hits ? 16 | 64 : 16;
+  stats_.kernels = (hits ? 16 | 64 : 16) | (peaks ? 256 : 0);
 }
 
 void HipEngine::solve_profile_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
@@ -1131,9 +1165,9 @@ void HipEngine::solve_profile_device(const uint8_t* d_codes, const int64_t* d_of
 }
 
 void HipEngine::solve_topk_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
-                                  int64_t n, int K, Result* d_out, hipStream_t stream) {
+                                  int64_t n, int K, Result* d_out, hipStream_t stream, int64_t radius) {
   if (K < 1) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
-  run_profile(d_codes, d_offsets, h_offsets, n, K, d_out, stream);
+  run_profile(d_codes, d_offsets, h_offsets, n, K, d_out, stream, nullptr, radius);
 }
 
 void HipEngine::solve_profile(const uint8_t* codes, const int64_t* offsets, int64_t n, ProfileEntry* prof_out,
@@ -1159,8 +1193,10 @@ void HipEngine::profile_placed(const Placed& p, ProfileEntry* prof_out, const in
   host_call_stats(wall, device_kernel_ms(), p, pbytes);
 }
 
-void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, Result* out) {
+void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, Result* out,
+                           int64_t radius) {
   if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  check_peaks_radius(radius);
   finish_wire();
   MOC_HIP_CHECK(hipSetDevice(device_));
   if (n <= 0) return;
@@ -1168,13 +1204,13 @@ void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t
   wall.start();
   const std::vector<int64_t> rebased =
       upload_batch(codes, offsets, n, sizeof(Result) * static_cast<size_t>(n) * static_cast<size_t>(K));
-  topk_placed(placed_upload(rebased, n), K, out, wall);
+  topk_placed(placed_upload(rebased, n), K, out, wall, radius);
 }
 
-void HipEngine::topk_placed(const Placed& p, int K, Result* out, Stopwatch& wall) {
+void HipEngine::topk_placed(const Placed& p, int K, Result* out, Stopwatch& wall, int64_t radius) {
   Slot& s = *slots_[0];
   const size_t obytes = sizeof(Result) * static_cast<size_t>(p.n) * static_cast<size_t>(K);
-  run_profile(p.d_codes, p.d_offsets, p.h_offsets, p.n, K, s.d_out, s_compute_);
+  run_profile(p.d_codes, p.d_offsets, p.h_offsets, p.n, K, s.d_out, s_compute_, nullptr, radius);
   copy_d2h(out, s.d_out, obytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
   host_call_stats(wall, device_kernel_ms(), p, obytes);
@@ -1183,8 +1219,9 @@ void HipEngine::topk_placed(const Placed& p, int K, Result* out, Stopwatch& wall
 // ---- threshold hits -------------------------------------------------------------------------------------
 void HipEngine::solve_hits_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
                                   int32_t min_score, const int32_t* d_thresholds, int64_t* d_hoffsets, Result* d_rows,
-                                  int64_t cap, hipStream_t stream) {
+                                  int64_t cap, hipStream_t stream, int64_t radius) {
   if (!have_problem_) throw Error("HipEngine: hits before set_problem");
+  check_peaks_radius(radius);
   if (cap < 0 || (cap > 0 && !d_rows)) throw Error("hits: cap rows need a rows buffer (cap = 0 counts only)");
   if (!d_hoffsets) throw Error("hits: no hoffsets buffer");
   if (n <= 0) {  // no launch: the index of an empty batch is its single 0
@@ -1195,13 +1232,14 @@ void HipEngine::solve_hits_device(const uint8_t* d_codes, const int64_t* d_offse
     return;
   }
   const HitsCall hc{min_score, d_thresholds, d_hoffsets, d_rows, d_rows ? cap : 0};
-  run_profile(d_codes, d_offsets, h_offsets, n, 0, nullptr, stream, &hc);
+  run_profile(d_codes, d_offsets, h_offsets, n, 0, nullptr, stream, &hc, radius);
 }
 
 void HipEngine::solve_hits(const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t min_score,
                            const int32_t* thresholds, int64_t* hoffsets_out, std::vector<Result>& rows_out,
-                           int64_t max_rows_hint) {
+                           int64_t max_rows_hint, int64_t radius) {
   if (!have_problem_) throw Error("HipEngine: hits before set_problem");
+  check_peaks_radius(radius);
   finish_wire();
   MOC_HIP_CHECK(hipSetDevice(device_));
   rows_out.clear();
@@ -1212,11 +1250,11 @@ void HipEngine::solve_hits(const uint8_t* codes, const int64_t* offsets, int64_t
   wall.start();
   const std::vector<int64_t> rebased =
       upload_batch(codes, offsets, n, sizeof(int64_t) * static_cast<size_t>(n + 1) + sizeof(int32_t) * static_cast<size_t>(n));
-  hits_placed(placed_upload(rebased, n), min_score, thresholds, hoffsets_out, rows_out, max_rows_hint, wall);
+  hits_placed(placed_upload(rebased, n), min_score, thresholds, hoffsets_out, rows_out, max_rows_hint, wall, radius);
 }
 
 void HipEngine::hits_placed(const Placed& p, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
-                            std::vector<Result>& rows_out, int64_t max_rows_hint, Stopwatch& wall) {
+                            std::vector<Result>& rows_out, int64_t max_rows_hint, Stopwatch& wall, int64_t radius) {
   Slot& s = *slots_[0];
   const int64_t n = p.n;
   // d_out: hoffsets (n + 1) | thresholds (n); the rows have a buffer of their own, which the second pass may grow
@@ -1229,7 +1267,7 @@ void HipEngine::hits_placed(const Placed& p, int32_t min_score, const int32_t* t
     ensure(d_hits_rows_, d_hits_rows_cap_, sizeof(Result) * static_cast<size_t>(cap));
     solve_hits_device(p.d_codes, p.d_offsets, p.h_offsets,
                       n, min_score, thresholds ? reinterpret_cast<const int32_t*>(d + hbytes) : nullptr,
-                      reinterpret_cast<int64_t*>(d), static_cast<Result*>(d_hits_rows_), cap, s_compute_);
+                      reinterpret_cast<int64_t*>(d), static_cast<Result*>(d_hits_rows_), cap, s_compute_, radius);
     copy_d2h(hoffsets_out, d, hbytes, s_compute_);
     MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
     kernel_ms += device_kernel_ms();
@@ -1486,18 +1524,20 @@ void HipEngine::solve_profile_wire(const WireBatch& b, ProfileEntry* prof_out, i
   profile_placed(place_wire(b, std::max<size_t>(pbytes, 8)), prof_out, poffsets_out, wall);
 }
 
-void HipEngine::solve_topk_wire(const WireBatch& b, int K, Result* out) {
+void HipEngine::solve_topk_wire(const WireBatch& b, int K, Result* out, int64_t radius) {
   if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  check_peaks_radius(radius);
   validate_wire(b);
   if (b.n <= 0) return;
   Stopwatch wall;
   wall.start();
-  topk_placed(place_wire(b, sizeof(Result) * static_cast<size_t>(b.n) * static_cast<size_t>(K)), K, out, wall);
+  topk_placed(place_wire(b, sizeof(Result) * static_cast<size_t>(b.n) * static_cast<size_t>(K)), K, out, wall, radius);
 }
 
 void HipEngine::solve_hits_wire(const WireBatch& b, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
-                                std::vector<Result>& rows_out, int64_t max_rows_hint) {
+                                std::vector<Result>& rows_out, int64_t max_rows_hint, int64_t radius) {
   if (!have_problem_) throw Error("HipEngine: hits before set_problem");
+  check_peaks_radius(radius);
   validate_wire(b);
   finish_wire();
   rows_out.clear();
@@ -1508,7 +1548,7 @@ void HipEngine::solve_hits_wire(const WireBatch& b, int32_t min_score, const int
   wall.start();
   const size_t n = static_cast<size_t>(b.n);
   hits_placed(place_wire(b, sizeof(int64_t) * (n + 1) + sizeof(int32_t) * n), min_score, thresholds, hoffsets_out, rows_out,
-              max_rows_hint, wall);
+              max_rows_hint, wall, radius);
 }
 
 void HipEngine::report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks) {

@@ -109,6 +109,22 @@ def _decl(lib):
         "moc_engine_solve_hits_wire": (c_int, [c_void_p, P(WireBatch), c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                                c_int64]),
         "moc_engine_report_wire": (c_int, [c_void_p, P(WireBatch), c_int, c_void_p, c_void_p, c_void_p]),
+        "moc_peaks_max_radius": (c_int, []),
+        "moc_peaks_geometry": (c_int, [c_void_p]),
+        "moc_cpu_topk_distinct": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                          c_int, c_int64, c_void_p]),
+        "moc_cpu_hits_distinct": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                          c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64]),
+        "moc_engine_solve_topk_distinct": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p]),
+        "moc_engine_solve_topk_device_distinct": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                                          c_int64, c_void_p, c_void_p]),
+        "moc_engine_solve_topk_wire_distinct": (c_int, [c_void_p, P(WireBatch), c_int, c_int64, c_void_p]),
+        "moc_engine_solve_hits_distinct": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64,
+                                                   c_int64, c_void_p, c_void_p, c_int64]),
+        "moc_engine_solve_hits_device_distinct": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                                          c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+        "moc_engine_solve_hits_wire_distinct": (c_int, [c_void_p, P(WireBatch), c_int32, c_void_p, c_int64, c_int64,
+                                                        c_void_p, c_void_p, c_int64]),
         "moc_partition": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_double, c_void_p]),
         "moc_device_count": (c_int, []),
         "moc_host_register": (c_int, [c_void_p, c_size_t]),

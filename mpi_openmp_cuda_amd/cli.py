@@ -50,6 +50,11 @@ def main(argv=None) -> int:
                            "--top K > 1 or --show-alignment; record slices on one node only (--partition records)")
     hits.add_argument("--within", type=int, default=None, metavar="D",
                       help="the same for every offset within D >= 0 of the record's own best score")
+    ap.add_argument("--distinct", type=int, default=None, metavar="R",
+                    help="with --top K or --min-score / --within: distinct placements only — an offset is printed "
+                         "only when no offset within R of it (0..2048) scores higher, or the same at a smaller n, so "
+                         "the one-column shadow of a placement and the rest of its slope drop out. Same line "
+                         "formats, fewer lines; R = 0 prints what no flag prints")
     a = ap.parse_args(argv)
     if not 1 <= a.top <= 64:
         ap.error("--top K: K must be in 1..64")
@@ -58,6 +63,12 @@ def main(argv=None) -> int:
         ap.error("--min-score / --within do not combine with --top K > 1 or --show-alignment")
     if a.within is not None and a.within < 0:
         ap.error("--within D: D must be >= 0")
+    if a.distinct is not None:
+        if not 0 <= a.distinct <= 2048:
+            ap.error("--distinct R: R must be in 0..2048")
+        if not want_hits and a.top <= 1:
+            ap.error("--distinct R filters the lines of --top K (K > 1) or --min-score / --within: give one of them")
+    radius = a.distinct or 0
     if a.min_score is not None and not -2 ** 31 <= a.min_score < 2 ** 31:
         ap.error("--min-score T: T must be an int32")
 
@@ -104,10 +115,10 @@ def main(argv=None) -> int:
         return 2
     hit_rows = None
     if want_hits:
-        got = search.run_hits(problem, a.min_score, a.within, Semantics.parse(a.semantics))
+        got = search.run_hits(problem, a.min_score, a.within, Semantics.parse(a.semantics), radius)
         results, hit_rows = (got[0], got[1:]) if ctx.is_root else (None, None)
     elif a.top > 1:
-        results = search.run_topk(problem, a.top, Semantics.parse(a.semantics))
+        results = search.run_topk(problem, a.top, Semantics.parse(a.semantics), radius)
     else:
         results = search.run(problem, Semantics.parse(a.semantics))
     if ctx.is_root:

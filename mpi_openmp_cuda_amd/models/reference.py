@@ -66,6 +66,28 @@ def brute_force_profile(table: np.ndarray, s1: np.ndarray, s2: np.ndarray, seman
     return prof
 
 
+def brute_force_peaks(table: np.ndarray, s1: np.ndarray, s2: np.ndarray, radius: int, semantics=Semantics.REFERENCE,
+                      profile=None):
+    """The peaks of radius ``radius`` of :func:`brute_force_profile` (or of ``profile``, a list of (score, k), when
+    given): a list of rows (score, n, k) in ascending n. Entry o is a peak iff no entry o' with 0 < |o - o'| <=
+    radius and 0 <= o' < C is better than it — a higher score, or an equal score and a smaller offset. Written from
+    that sentence with a plain double loop, O(C * radius): the anchor oracle of the native peak filters."""
+    prof = brute_force_profile(table, s1, s2, semantics) if profile is None else list(profile)
+    C = len(prof)
+    rows = []
+    for o in range(C):
+        peak = True
+        for o2 in range(max(0, o - radius), min(C - 1, o + radius) + 1):
+            if o2 == o:
+                continue
+            if prof[o2][0] > prof[o][0] or (prof[o2][0] == prof[o][0] and o2 < o):
+                peak = False
+                break
+        if peak:
+            rows.append((int(prof[o][0]), o, int(prof[o][1])))
+    return rows
+
+
 def prefix_oracle(table: np.ndarray, s1: np.ndarray, s2: np.ndarray, semantics=Semantics.REFERENCE):
     L1, L2 = len(s1), len(s2)
     if L2 > L1:

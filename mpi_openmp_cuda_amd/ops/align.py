@@ -103,6 +103,28 @@ def _check_k(K) -> int:
     return K
 
 
+MAX_PEAK_RADIUS = 2048  # csrc/include/moc/kernel_bounds.hpp kPeaksMaxRadius (tests compare it with the native value)
+
+
+def _check_radius(radius) -> int:
+    """The radius of the distinct forms of top-K and hits: 0 (the plain results) .. MAX_PEAK_RADIUS. Entry o of a
+    record's profile is a peak of radius R iff no entry o' with 0 < |o - o'| <= R inside the profile has a higher
+    score, or an equal score and a smaller offset; the distinct forms keep the peaks only."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)):
+        raise ValueError(f"distinct: radius must be an integer in 0..{MAX_PEAK_RADIUS}, got {radius!r}")
+    if not 0 <= int(radius) <= MAX_PEAK_RADIUS:
+        raise ValueError(f"distinct: radius must be in 0..{MAX_PEAK_RADIUS}, got {int(radius)}")
+    return int(radius)
+
+
+def peaks_geometry() -> tuple:
+    """(largest radius, most profile entries of a record that the GPU's wave-per-record peak kernel takes, entries
+    per tile of its tile kernel) — csrc/include/moc/kernel_bounds.hpp; no GPU needed."""
+    g = np.zeros(3, np.int32)
+    _lib.check(_lib.lib().moc_peaks_geometry(_lib.ptr(g)))
+    return int(g[0]), int(g[1]), int(g[2])
+
+
 def profile_offsets(L1: int, lengths, semantics=Semantics.REFERENCE) -> np.ndarray:
     """int64 [n + 1] index of a batch's flat per-offset profile: record i owns entries
     [poffsets[i], poffsets[i + 1]), one per candidate offset — 0 if L2 > L1 or L2 <= 0, 1 if L2 == L1,
@@ -128,15 +150,22 @@ def search_profile_cpu(problem: Problem, semantics=Semantics.REFERENCE, threads:
     return prof, poffsets
 
 
-def search_topk_cpu(problem: Problem, K: int, semantics=Semantics.REFERENCE, threads: int = 0) -> np.ndarray:
+def search_topk_cpu(problem: Problem, K: int, semantics=Semantics.REFERENCE, threads: int = 0,
+                    radius: int = 0) -> np.ndarray:
     """The K best offsets of every record on the CPU engine: int32 [n, K, 3] rows (score, n, k) in the order
     higher score, then smaller n, each with that offset's profile k; records with fewer than K candidate
-    offsets are padded with (INT32_MIN, 0, 0). Row 0 is search_cpu's result."""
+    offsets are padded with (INT32_MIN, 0, 0). Row 0 is search_cpu's result. ``radius`` > 0: distinct placements —
+    only the peaks of that radius (:func:`_check_radius`) are ranked, min(K, #peaks) rows and then padding; row 0
+    is unchanged, the best offset always being a peak."""
     K = _check_k(K)
+    radius = _check_radius(radius)
     out = np.zeros((problem.n, K, 3), np.int32)
-    _lib.check(_lib.lib().moc_cpu_topk(
-        _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
-        _lib.ptr(problem.offsets), problem.n, int(Semantics.parse(semantics)), int(threads), K, _lib.ptr(out)))
+    head = (_lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+            _lib.ptr(problem.offsets), problem.n, int(Semantics.parse(semantics)), int(threads), K)
+    if radius:
+        _lib.check(_lib.lib().moc_cpu_topk_distinct(*head, radius, _lib.ptr(out)))
+    else:
+        _lib.check(_lib.lib().moc_cpu_topk(*head, _lib.ptr(out)))
     return out
 
 
@@ -185,23 +214,28 @@ def _hits_thresholds(n: int, min_score, thresholds, within, best_scores):
 
 
 def search_hits_cpu(problem: Problem, min_score=None, thresholds=None, within=None, semantics=Semantics.REFERENCE,
-                    threads: int = 0):
+                    threads: int = 0, radius: int = 0):
     """Threshold hits on the CPU engine: ``(rows, hoffsets)``. Record i's hits are the offsets o whose profile score
     (:func:`search_profile_cpu`) is >= its threshold (inclusive), ascending in o, as int32 rows (score, n = o, k of
     that profile entry) at ``rows[hoffsets[i]:hoffsets[i + 1]]``; ``hoffsets`` is int64 [n + 1] and
     ``hoffsets[-1]`` the total H. Exactly one of ``min_score`` (one int32 for the batch; INT32_MIN selects the whole
     profile), ``thresholds`` (int32 [n]) and ``within`` (D >= 0: every offset within D of the record's best score,
-    from a search on the same engine) must be given."""
+    from a search on the same engine) must be given. ``radius`` > 0: distinct placements — only the hits that are
+    peaks of that radius (:func:`_check_radius`); a threshold does not interact with the suppression, whatever
+    suppresses an entry scores at least as much."""
     sem = Semantics.parse(semantics)
+    radius = _check_radius(radius)
     m, t = _hits_thresholds(problem.n, min_score, thresholds, within,
                             lambda: search_cpu(problem, sem, threads)["score"])
     hoffsets = np.zeros(problem.n + 1, np.int64)
 
     def call(rows, cap):
-        _lib.check(_lib.lib().moc_cpu_hits(
-            _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
-            _lib.ptr(problem.offsets), problem.n, int(sem), int(threads), m, _lib.ptr(t), _lib.ptr(hoffsets),
-            _lib.ptr(rows), cap))
+        head = (_lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1,
+                _lib.ptr(problem.codes), _lib.ptr(problem.offsets), problem.n, int(sem), int(threads), m, _lib.ptr(t))
+        if radius:
+            _lib.check(_lib.lib().moc_cpu_hits_distinct(*head, radius, _lib.ptr(hoffsets), _lib.ptr(rows), cap))
+        else:
+            _lib.check(_lib.lib().moc_cpu_hits(*head, _lib.ptr(hoffsets), _lib.ptr(rows), cap))
 
     call(None, 0)  # counts
     total = int(hoffsets[-1])
@@ -558,16 +592,25 @@ class HipSearchEngine:
                                                        _lib.ptr(poffsets), _lib.ptr(prof)))
         return prof[:int(poffsets[-1])], poffsets
 
-    def solve_topk(self, codes: np.ndarray, offsets: np.ndarray, K: int) -> np.ndarray:
+    def solve_topk(self, codes: np.ndarray, offsets: np.ndarray, K: int, radius: int = 0) -> np.ndarray:
         """Host CSR -> int32 [n, K, 3] top-K rows as :func:`search_topk_cpu` returns them. The batch's profile
         is never materialised: records run in chunks whose profile scratch stays under the bound of
-        :meth:`set_profile_scratch` (default 256 MiB). Synchronous."""
+        :meth:`set_profile_scratch` (default 256 MiB). Synchronous. ``radius`` > 0 (here and in every top-K and
+        hits call of the engine): distinct placements, as :func:`search_topk_cpu` — the peak kernels
+        (csrc/src/hip/peaks_kernels.hip) run between each chunk's profile and its select, ``stats()["kernels"]``
+        names ``peaks``; ``radius=0`` is the plain call, launch for launch."""
         K = _check_k(K)
+        radius = _check_radius(radius)
         codes = np.ascontiguousarray(codes, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = offsets.shape[0] - 1
         out = np.zeros((n, K, 3), np.int32)
-        _lib.check(_lib.lib().moc_engine_solve_topk(self._h, _lib.ptr(codes), _lib.ptr(offsets), n, K, _lib.ptr(out)))
+        if radius:
+            _lib.check(_lib.lib().moc_engine_solve_topk_distinct(self._h, _lib.ptr(codes), _lib.ptr(offsets), n, K,
+                                                                 radius, _lib.ptr(out)))
+        else:
+            _lib.check(_lib.lib().moc_engine_solve_topk(self._h, _lib.ptr(codes), _lib.ptr(offsets), n, K,
+                                                        _lib.ptr(out)))
         return out
 
     def solve_profile_device(self, codes_t, offsets_t, h_offsets: np.ndarray, prof_t=None, stream=None):
@@ -591,21 +634,27 @@ class HipSearchEngine:
             n, ctypes.c_void_p(prof_t.data_ptr()), ctypes.c_void_p(stream.cuda_stream)))
         return prof_t, poffsets
 
-    def solve_topk_device(self, codes_t, offsets_t, h_offsets: np.ndarray, K: int, out_t, stream=None):
+    def solve_topk_device(self, codes_t, offsets_t, h_offsets: np.ndarray, K: int, out_t, stream=None,
+                          radius: int = 0):
         """Device-resident batch -> ``out_t``, an int32 [n, K, 3] tensor of top-K rows. Queued on ``stream``
-        (default: the current stream); returns immediately."""
+        (default: the current stream); returns immediately. ``radius``: as :meth:`solve_topk`."""
         import torch
 
         K = _check_k(K)
+        radius = _check_radius(radius)
         h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
         n = h_offsets.shape[0] - 1
         assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
         assert out_t.dtype == torch.int32 and out_t.shape == (n, K, 3) and out_t.is_contiguous()
         if stream is None:
             stream = torch.cuda.current_stream(codes_t.device)
-        _lib.check(_lib.lib().moc_engine_solve_topk_device(
-            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
-            n, K, ctypes.c_void_p(out_t.data_ptr()), ctypes.c_void_p(stream.cuda_stream)))
+        head = (self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()),
+                _lib.ptr(h_offsets), n, K)
+        tail = (ctypes.c_void_p(out_t.data_ptr()), ctypes.c_void_p(stream.cuda_stream))
+        if radius:
+            _lib.check(_lib.lib().moc_engine_solve_topk_device_distinct(*head, radius, *tail))
+        else:
+            _lib.check(_lib.lib().moc_engine_solve_topk_device(*head, *tail))
         return out_t
 
     def set_profile_scratch(self, nbytes: int):
@@ -622,19 +671,24 @@ class HipSearchEngine:
 
     # ---- threshold hits (byte letters, dense offsets; csrc/src/hip/hits_kernels.hip)
     def solve_hits(self, codes: np.ndarray, offsets: np.ndarray, min_score=None, thresholds=None, within=None,
-                   max_rows: Optional[int] = None):
+                   max_rows: Optional[int] = None, radius: int = 0):
         """Host CSR -> ``(rows, hoffsets)`` as :func:`search_hits_cpu` returns them (exactly one of ``min_score``,
         ``thresholds``, ``within``), through the chunks of :meth:`solve_topk` with count, prefix sum and compaction
         kernels behind each chunk's profile. Optimistic: one pass with room for ``max_rows`` rows (default 4 n) and
-        exactly one more when more offsets qualify (:meth:`hits_passes`). Synchronous."""
+        exactly one more when more offsets qualify (:meth:`hits_passes`). Synchronous. ``radius`` > 0: only the hits
+        that are peaks of that radius, as :func:`search_hits_cpu` (see :meth:`solve_topk`)."""
+        radius = _check_radius(radius)
         codes = np.ascontiguousarray(codes, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = offsets.shape[0] - 1
         m, t = _hits_thresholds(n, min_score, thresholds, within, lambda: self.solve(codes, offsets)["score"])
         hoffsets = np.zeros(n + 1, np.int64)
-        _lib.check(_lib.lib().moc_engine_solve_hits(self._h, _lib.ptr(codes), _lib.ptr(offsets), n, m, _lib.ptr(t),
-                                                    -1 if max_rows is None else int(max_rows), _lib.ptr(hoffsets),
-                                                    None, 0))
+        head = (self._h, _lib.ptr(codes), _lib.ptr(offsets), n, m, _lib.ptr(t))
+        tail = (-1 if max_rows is None else int(max_rows), _lib.ptr(hoffsets), None, 0)
+        if radius:
+            _lib.check(_lib.lib().moc_engine_solve_hits_distinct(*head, radius, *tail))
+        else:
+            _lib.check(_lib.lib().moc_engine_solve_hits(*head, *tail))
         total = int(hoffsets[-1])
         rows = np.zeros((total, 3), np.int32)
         _lib.check(_lib.lib().moc_engine_hits_rows(_lib.ptr(rows) if total else None, total))
@@ -652,16 +706,18 @@ class HipSearchEngine:
         return float(ms.value)
 
     def solve_hits_device(self, codes_t, offsets_t, h_offsets: np.ndarray, min_score=None, thresholds_t=None,
-                          within=None, cap: Optional[int] = None, rows_t=None, hoffsets_t=None, stream=None):
+                          within=None, cap: Optional[int] = None, rows_t=None, hoffsets_t=None, stream=None,
+                          radius: int = 0):
         """Device-resident batch (as :meth:`solve_device`) -> ``(rows_t, hoffsets_t)``: ``hoffsets_t`` an int64
         [n + 1] tensor, always complete and exact; ``rows_t`` an int32 [cap, 3] tensor (``cap`` default 4 n) of
         which the rows with a flat index < cap are written and nothing else is touched — compare
         ``hoffsets_t[-1]`` with ``cap`` after a sync. ``cap = 0`` counts only. Exactly one of ``min_score``,
         ``thresholds_t`` (an int32 [n] tensor on the same device, e.g. built from a search's scores) and ``within``
         (a search queued on the same stream first). Both tensors are allocated when None. Queued on ``stream``
-        (default: the current stream); returns immediately."""
+        (default: the current stream); returns immediately. ``radius``: as :meth:`solve_hits`."""
         import torch
 
+        radius = _check_radius(radius)
         h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
         n = h_offsets.shape[0] - 1
         if sum(x is not None for x in (min_score, thresholds_t, within)) != 1:
@@ -698,11 +754,15 @@ class HipSearchEngine:
         assert rows_t.dtype == torch.int32 and rows_t.is_contiguous() and rows_t.dim() == 2 and rows_t.shape[1] == 3
         assert rows_t.shape[0] >= cap
         assert hoffsets_t.dtype == torch.int64 and hoffsets_t.is_contiguous() and hoffsets_t.numel() == n + 1
-        _lib.check(_lib.lib().moc_engine_solve_hits_device(
-            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
-            n, m, ctypes.c_void_p(thresholds_t.data_ptr()) if thresholds_t is not None else None,
-            ctypes.c_void_p(hoffsets_t.data_ptr()), ctypes.c_void_p(rows_t.data_ptr()) if cap else None, cap,
-            ctypes.c_void_p(stream.cuda_stream)))
+        head = (self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()),
+                _lib.ptr(h_offsets), n, m,
+                ctypes.c_void_p(thresholds_t.data_ptr()) if thresholds_t is not None else None)
+        tail = (ctypes.c_void_p(hoffsets_t.data_ptr()), ctypes.c_void_p(rows_t.data_ptr()) if cap else None, cap,
+                ctypes.c_void_p(stream.cuda_stream))
+        if radius:
+            _lib.check(_lib.lib().moc_engine_solve_hits_device_distinct(*head, radius, *tail))
+        else:
+            _lib.check(_lib.lib().moc_engine_solve_hits_device(*head, *tail))
         return rows_t, hoffsets_t
 
     # ---- alignment report (byte letters, dense offsets; csrc/src/hip/report_kernels.hip)
@@ -860,28 +920,38 @@ class HipSearchEngine:
         del keep
         return prof[:int(poffsets[-1])], poffsets
 
-    def solve_topk_wire(self, ws, K: int, shift: int = 0) -> np.ndarray:
+    def solve_topk_wire(self, ws, K: int, shift: int = 0, radius: int = 0) -> np.ndarray:
         """Host wire batch -> int32 [n, K, 3] top-K rows, as :meth:`solve_topk` on the decoded records (same chunks
-        under :meth:`set_profile_scratch`). See :meth:`solve_profile_wire`."""
+        under :meth:`set_profile_scratch`, same ``radius``). See :meth:`solve_profile_wire`."""
         K = _check_k(K)
+        radius = _check_radius(radius)
         b, keep = wire_batch_of(ws, shift)
         out = np.zeros((ws.n, K, 3), np.int32)
-        _lib.check(_lib.lib().moc_engine_solve_topk_wire(self._h, ctypes.byref(b), K, _lib.ptr(out)))
+        if radius:
+            _lib.check(_lib.lib().moc_engine_solve_topk_wire_distinct(self._h, ctypes.byref(b), K, radius,
+                                                                      _lib.ptr(out)))
+        else:
+            _lib.check(_lib.lib().moc_engine_solve_topk_wire(self._h, ctypes.byref(b), K, _lib.ptr(out)))
         del keep
         return out
 
     def solve_hits_wire(self, ws, min_score=None, thresholds=None, within=None, max_rows: Optional[int] = None,
-                        shift: int = 0):
+                        shift: int = 0, radius: int = 0):
         """Host wire batch -> ``(rows, hoffsets)``, as :meth:`solve_hits` on the decoded records (exactly one of
         ``min_score``, ``thresholds``, ``within``; ``max_rows`` and :meth:`hits_passes` as there). ``within`` takes
-        the records' best scores from :meth:`solve_topk_wire`. See :meth:`solve_profile_wire`."""
+        the records' best scores from :meth:`solve_topk_wire`; ``radius`` as :meth:`solve_hits`. See
+        :meth:`solve_profile_wire`."""
+        radius = _check_radius(radius)
         b, keep = wire_batch_of(ws, shift)
         n = ws.n
         m, t = _hits_thresholds(n, min_score, thresholds, within, lambda: self.solve_topk_wire(ws, 1, shift)[:, 0, 0])
         hoffsets = np.zeros(n + 1, np.int64)
-        _lib.check(_lib.lib().moc_engine_solve_hits_wire(self._h, ctypes.byref(b), m, _lib.ptr(t),
-                                                         -1 if max_rows is None else int(max_rows), _lib.ptr(hoffsets),
-                                                         None, 0))
+        head = (self._h, ctypes.byref(b), m, _lib.ptr(t))
+        tail = (-1 if max_rows is None else int(max_rows), _lib.ptr(hoffsets), None, 0)
+        if radius:
+            _lib.check(_lib.lib().moc_engine_solve_hits_wire_distinct(*head, radius, *tail))
+        else:
+            _lib.check(_lib.lib().moc_engine_solve_hits_wire(*head, *tail))
         total = int(hoffsets[-1])
         rows = np.zeros((total, 3), np.int32)
         _lib.check(_lib.lib().moc_engine_hits_rows(_lib.ptr(rows) if total else None, total))
@@ -922,7 +992,8 @@ class HipSearchEngine:
         d["r2"] = tuple(int(x) for x in list(v)[10:13])
         d["format"] = _lib.FORMAT_NAMES[int(d["format"])]
         d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16"), (16, "profile"),
-                                             (32, "report"), (64, "hits"), (128, "wire")) if int(d["kernels"]) & b]
+                                             (32, "report"), (64, "hits"), (128, "wire"), (256, "peaks"))
+                        if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
 
@@ -981,23 +1052,25 @@ def align_profile_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets,
     return engine.solve_profile_device(codes_t, offsets_t, h_offsets, None, stream)
 
 
-def align_topk_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, K: int, stream=None):
+def align_topk_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, K: int, stream=None, radius: int = 0):
     """torch-facing op: an int32 [n, K, 3] tensor of the K best (score, n, k) rows per record on the codes'
-    device; ``[:, 0]`` equals :func:`align_search_device`."""
+    device; ``[:, 0]`` equals :func:`align_search_device`. ``radius`` > 0: the K best distinct placements
+    (:meth:`HipSearchEngine.solve_topk`)."""
     import torch
 
     n = int(len(h_offsets) - 1)
     out = torch.empty((n, _check_k(K), 3), dtype=torch.int32, device=codes_t.device)
-    engine.solve_topk_device(codes_t, offsets_t, h_offsets, K, out, stream)
+    engine.solve_topk_device(codes_t, offsets_t, h_offsets, K, out, stream, radius)
     return out
 
 
 def align_hits_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, min_score=None, thresholds_t=None,
-                      within=None, cap: Optional[int] = None, stream=None):
+                      within=None, cap: Optional[int] = None, stream=None, radius: int = 0):
     """torch-facing op: threshold hits as ``(rows_t, hoffsets_t)`` on the codes' device — int32 [cap, 3] rows
-    (score, n, k) and the int64 [n + 1] index; see :meth:`HipSearchEngine.solve_hits_device`."""
+    (score, n, k) and the int64 [n + 1] index; see :meth:`HipSearchEngine.solve_hits_device` (``radius`` > 0: the
+    distinct placements among them)."""
     return engine.solve_hits_device(codes_t, offsets_t, h_offsets, min_score, thresholds_t, within, cap, None, None,
-                                    stream)
+                                    stream, radius)
 
 
 def align_report_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, rows_t, marks: bool = False,

@@ -153,11 +153,13 @@ class DistributedSearch:
             win = NodeWindow(name, n, total, create=False)
         return win
 
-    def run_topk(self, problem: Optional[Problem], K: int, semantics=Semantics.REFERENCE) -> Optional[np.ndarray]:
+    def run_topk(self, problem: Optional[Problem], K: int, semantics=Semantics.REFERENCE,
+                 radius: int = 0) -> Optional[np.ndarray]:
         """The K best offsets of every record (ops.align.search_topk_cpu's int32 [n, K, 3] rows) for the
         ``records`` partition: every rank searches its cost-balanced slice of the node-shared input window, and
         the root collects the rows with one MAX all-reduce of an array each rank fills only in its own slice
-        (no new transport). One node; byte letters through the engines' top-K calls."""
+        (no new transport). One node; byte letters through the engines' top-K calls. ``radius`` > 0 (the same on
+        every rank): the K best distinct placements (ops.align.search_topk_cpu)."""
         if self.partition != "records":
             raise ValueError("top-K runs on record slices (--partition records, one node): the offsets partition "
                              "combines one packed key per record and cannot carry K rows")
@@ -172,24 +174,26 @@ class DistributedSearch:
             if e > b:
                 offsets = np.asarray(win.offsets[b:e + 1])
                 if self.engine is not None:
-                    rows[b:e] = self.engine.solve_topk(np.asarray(win.codes), offsets, K)
+                    rows[b:e] = self.engine.solve_topk(np.asarray(win.codes), offsets, K, radius)
                 else:
                     sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
                                   offsets - offsets[0])
-                    rows[b:e] = search_topk_cpu(sub, K, sem, self.threads)
+                    rows[b:e] = search_topk_cpu(sub, K, sem, self.threads, radius)
         with T.phase("gather"):
             rows = D.allreduce_max_int64(ctx, rows.reshape(-1)).reshape(n, K, 3)
             D.barrier(ctx)
             win.close(unlink=ctx.is_root)
         return rows.astype(np.int32) if ctx.is_root else None
 
-    def run_hits(self, problem: Optional[Problem], min_score=None, within=None, semantics=Semantics.REFERENCE):
+    def run_hits(self, problem: Optional[Problem], min_score=None, within=None, semantics=Semantics.REFERENCE,
+                 radius: int = 0):
         """Threshold hits (ops.align.search_hits_cpu's ``(rows, hoffsets)``; exactly one of ``min_score`` and
         ``within``, the same on every rank) together with the search's own rows, for the ``records`` partition:
         every rank computes its cost-balanced slice of the node-shared input window; the root collects the counts and then the rows, each
         with one MAX all-reduce of an int64 array that a rank fills only in its own slice, INT64_MIN elsewhere (no
         new transport). Returns ``(results, rows, hoffsets)`` on the root, else None. One node; byte letters
-        through the engines' hits calls."""
+        through the engines' hits calls. ``radius`` > 0 (the same on every rank): the distinct placements among the
+        hits (ops.align.search_hits_cpu)."""
         if self.partition != "records":
             raise ValueError("hits run on record slices (--partition records, one node): the offsets partition "
                              "combines one packed key per record and cannot carry a list of rows")
@@ -218,12 +222,12 @@ class DistributedSearch:
                 if self.engine is not None:
                     codes = np.asarray(win.codes)
                     best[b:e] = self.engine.solve(codes, offsets).view(np.int32).reshape(-1, 3)
-                    mine, h = self.engine.solve_hits(codes, offsets, **kw(best[b:e, 0]))
+                    mine, h = self.engine.solve_hits(codes, offsets, radius=radius, **kw(best[b:e, 0]))
                 else:
                     sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
                                   offsets - offsets[0])
                     best[b:e] = search_cpu(sub, sem, self.threads).view(np.int32).reshape(-1, 3)
-                    mine, h = search_hits_cpu(sub, semantics=sem, threads=self.threads, **kw(best[b:e, 0]))
+                    mine, h = search_hits_cpu(sub, semantics=sem, threads=self.threads, radius=radius, **kw(best[b:e, 0]))
                 counts[b:e] = np.diff(h)
         with T.phase("gather"):
             counts = D.allreduce_max_int64(ctx, counts)

@@ -123,11 +123,12 @@ class WireSlice:
     def solve_profile_wire(self, engine, shift: int = 0):
         return engine.solve_profile_wire(self, shift)
 
-    def solve_topk_wire(self, engine, K: int, shift: int = 0):
-        return engine.solve_topk_wire(self, K, shift)
+    def solve_topk_wire(self, engine, K: int, shift: int = 0, radius: int = 0):
+        return engine.solve_topk_wire(self, K, shift, radius)
 
-    def solve_hits_wire(self, engine, min_score=None, thresholds=None, within=None, max_rows=None, shift: int = 0):
-        return engine.solve_hits_wire(self, min_score, thresholds, within, max_rows, shift)
+    def solve_hits_wire(self, engine, min_score=None, thresholds=None, within=None, max_rows=None, shift: int = 0,
+                        radius: int = 0):
+        return engine.solve_hits_wire(self, min_score, thresholds, within, max_rows, shift, radius)
 
     def report_wire(self, engine, rows, marks: bool = False, shift: int = 0):
         return engine.report_wire(self, rows, marks, shift)
