@@ -275,6 +275,33 @@ int moc_engine_solve_hits_device_distinct(void* e, const uint8_t* d_codes, const
 int moc_engine_solve_hits_wire_distinct(void* e, const moc_wire_batch* b, int32_t min_score, const int32_t* thresholds,
                                         int64_t radius, int64_t max_rows_hint, int64_t* hoffsets, moc_result* rows,
                                         int64_t cap);
+/* ---- profile summary (moc/cpu_engine.hpp summary_batch_cpu) ----
+ * Per record the moments and extremes of its whole per-offset profile and, optionally, a histogram of its scores.
+ * summary: int64 [n, 7], columns (count, sum, sumsq, min, max, n, k): count = the record's candidate offsets C, sum and
+ * sumsq of the scores (exact), min and max over them, (max, n, k) the search's result; C = 0 gives
+ * (0, 0, 0, INT32_MAX, INT32_MIN, 0, 0). hist: int32 [n, bins], bins in 0 .. 256 (0: none, hist may be NULL and is
+ * not touched): a score s counts in bin clamp(floor((s - lo) / width), 0, bins - 1), computed in 64 bits; width >= 1;
+ * every row sums to count. Errors, all reported before any work and with a message that starts with "summary:": bins
+ * or width out of range, and the exactness bound — with M = min(2^31, max |W| * the call's longest record), a record
+ * of more than moc_summary_bound(max |W|, longest record) = floor((2^63 - 1) / M^2) candidate offsets could overflow
+ * sumsq. The engine forms are as moc_engine_solve_hits*: the host and wire forms synchronous, the device form queued
+ * on `stream` without a sync (d_summary: device int64 [n, 7]; d_hist: device int32 [n, bins] or NULL). */
+int moc_cpu_summary(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                    const int64_t* offsets, int64_t n, int semantics, int threads, int32_t bins, int32_t lo,
+                    int32_t width, int64_t* summary, int32_t* hist);
+/* out3: records per workgroup of the GPU's summary kernels (one wave each), threads per workgroup, and the largest
+ * bins (moc/kernel_bounds.hpp); no GPU needed */
+int moc_summary_geometry(int32_t* out3);
+int64_t moc_summary_bound(int32_t max_abs_weight, int64_t max_l2);
+int moc_engine_solve_summary(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t bins, int32_t lo,
+                             int32_t width, int64_t* summary, int32_t* hist);
+int moc_engine_solve_summary_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                    int64_t n, int32_t bins, int32_t lo, int32_t width, int64_t* d_summary,
+                                    int32_t* d_hist, void* stream);
+int moc_engine_solve_summary_wire(void* e, const moc_wire_batch* b, int32_t bins, int32_t lo, int32_t width,
+                                  int64_t* summary, int32_t* hist);
+/* device time (ms) of the last summary call's summary + histogram launches (MOC_PROFILE_TIMING=1; else 0) */
+int moc_engine_summary_ms(void* e, double* ms);
 /* stats: kernel_ms, total_ms, h2d_bytes, d2h_bytes, chunks, cells, records, direct, format, kernels,
  * r2 smin, r2 kw, r2 j, forms (moc::bounds::FormBits of the last solve) */
 int moc_engine_stats(void* e, double* out14);

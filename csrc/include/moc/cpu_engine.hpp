@@ -111,6 +111,28 @@ void hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const Re
 void peaks_filter(const ProfileEntry* prof, int64_t C, int64_t radius, uint8_t* peak);
 void check_peaks_radius(int64_t radius);  // throws Error unless 0 <= radius <= bounds::kPeaksMaxRadius
 
+// ---- profile summary: the moments, extremes and a fixed-bin histogram of every record's profile
+// Record i with the C_i profile entries {score, k} gives the row summary[i*7 .. i*7+7) =
+// (count, sum, sumsq, min, max, n, k), kSummaryCols int64 values: count = C_i; sum and sumsq of the scores, exact;
+// min and max over the scores; (max, n, k) the better()-maximum of the profile (highest score, then smallest offset,
+// with that entry's k) — solve_record's result and row 0 of top-K. C_i = 0: (0, 0, 0, INT32_MAX, INT32_MIN, 0, 0).
+// Histogram (bins = B in 0 .. bounds::kSummaryMaxBins; 0: none, hist may be null): entry o counts in bin
+// summary_bin(score, lo, width, B) = clamp(floor((score - lo) / width), 0, B - 1), the subtraction and the floor
+// division in int64 (lo = INT32_MIN with a positive score does not wrap; a negative numerator rounds down). Scores
+// below lo land in bin 0, scores at or past lo + B * width in bin B - 1. hist: int32 [n * B]; every row sums to
+// C_i. width >= 1. No radius and no threshold: the summary is of the whole profile.
+// Exactness: check_summary_args throws Error ("summary: ...") unless 0 <= bins <= kSummaryMaxBins, width >= 1 and
+// bounds::summary_exact(max |W|, the call's longest record, its longest profile) — then sumsq fits int64.
+constexpr int kSummaryCols = 7;
+inline int64_t summary_bin(int32_t score, int32_t lo, int32_t width, int32_t bins) {
+  const int64_t d = static_cast<int64_t>(score) - lo;
+  const int64_t q = d >= 0 ? d / width : -((-d + width - 1) / width);
+  return std::min<int64_t>(std::max<int64_t>(q, 0), bins - 1);
+}
+void check_summary_args(int32_t max_abs_weight, int64_t max_l2, int64_t max_count, int32_t bins, int32_t width);
+void summary_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int64_t* summary,
+                       int32_t* hist, int32_t bins, int32_t lo, int32_t width, Semantics sem, int num_threads = 0);
+
 // ---- alignment report: the signs under a result row's letter pairs
 // A row is a Result {score, n, k} of record i (L2 letters) against Seq1; rows[i*K .. i*K+K) belong to record i.
 //   empty row   (score == kNoCandidateScore, e.g. top-K padding): counts {0,0,0,0}, marker bytes 0, nothing read

@@ -397,6 +397,24 @@ void launch_topk_select_peaks(const ProfileArgs& pa, const uint8_t* peak, int64_
                               hipStream_t stream);
 void launch_hits_peaks(const HitsArgs& ha, const uint8_t* peak, hipStream_t stream);
 
+// ---- profile summary (summary_kernels.hip; definitions: moc/cpu_engine.hpp summary_batch_cpu)
+// One chunk of consecutive records [rec0, rec0 + n_rec) whose profile lies where hits_count_kernel reads it:
+// prof[poffsets[r] - base + o]. Record r's row goes to summary[r * 7 ..) and, with bins > 0, its histogram to
+// hist[r * bins ..) (batch-wide record index; every value of both is stored, nothing is accumulated into).
+struct SummaryArgs {
+  const ProfileEntry* prof = nullptr;
+  const int64_t* poffsets = nullptr;
+  int64_t base = 0;
+  int64_t prof_entries = 0;  // entries of `prof` (debug builds check the load index against it)
+  int64_t rec0 = 0, n_rec = 0;
+  int64_t n_total = 0;       // records of the batch (debug builds check the store indices against it)
+  int64_t* summary = nullptr;  // device int64 [n * 7]
+  int32_t* hist = nullptr;     // device int32 [n * bins], or null with bins == 0
+  int32_t bins = 0, lo = 0, width = 1;
+};
+// Queues the summary kernel and, when bins > 0, the histogram kernel on `stream`.
+void launch_summary(const SummaryArgs& sa, hipStream_t stream);
+
 // Loads every kernel file's code object onto the current device now (HIP loads them lazily, at the first
 // launch from each file: milliseconds inside the first timed search of a job otherwise).
 void preload_align_kernels();
@@ -410,6 +428,7 @@ void preload_report_kernels();
 void preload_hits_kernels();
 void preload_wire_kernels();
 void preload_peaks_kernels();
+void preload_summary_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -424,6 +443,7 @@ enum PreloadSet : unsigned {
   kPreloadHits = 256,    // hits_kernels.hip: likewise
   kPreloadWire = 512,    // wire_kernels.hip: likewise
   kPreloadPeaks = 1024,  // peaks_kernels.hip: likewise
+  kPreloadSummary = 2048,  // summary_kernels.hip: likewise
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -437,9 +457,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadHits) preload_hits_kernels();
   if (set & kPreloadWire) preload_wire_kernels();
   if (set & kPreloadPeaks) preload_peaks_kernels();
+  if (set & kPreloadSummary) preload_summary_kernels();
 }
 // "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
-// profile, report, hits, wire, peaks;
+// profile, report, hits, wire, peaks, summary;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

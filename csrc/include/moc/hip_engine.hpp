@@ -62,7 +62,8 @@ struct EngineStats {
   int32_t kernels = 0;   // bitmask of kernels used: 1 swipe (lane/record), 2 short (lane/offset), 4 tiles
                          // (LUT tile kernel), 8 tile16, 16 profile (per-offset profile / top-K), 32 report,
                          // 64 hits (count / scan / compact, next to 16), 128 wire (decode kernels of a *_wire call),
-                         // 256 peaks (the peak filter and masked select / hits kernels of a distinct call)
+                         // 256 peaks (the peak filter and masked select / hits kernels of a distinct call),
+                         // 512 summary (the summary / histogram kernels, next to 16)
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -174,6 +175,26 @@ class HipEngine {
   // Device time (ms) of the count + scan + compact launches of the last hits call; as topk_select_ms().
   double hits_select_ms() { return topk_select_ms(); }
 
+  // ---- profile summary (definitions: moc/cpu_engine.hpp summary_batch_cpu; kernels:
+  // csrc/src/hip/summary_kernels.hip): per record the row (count, sum, sumsq, min, max, n, k) of its whole profile as
+  // seven int64 and, with bins > 0, an int32 [bins] histogram of its scores (bin = clamp(floor((s - lo) / width), 0,
+  // bins - 1)). Limits as hits: byte letters and dense int64 offsets (wire batches: solve_summary_wire), n < 2^31 - 1;
+  // no radius and no threshold. Before anything is launched or any state changes, bins (0 .. kSummaryMaxBins), width
+  // (>= 1) and the exactness bound of the batch (bounds::summary_exact over max |W|, the longest record and the
+  // longest profile) are checked, and a call outside them throws an Error that starts with "summary:".
+  // Device form: queued on `stream` (0 = engine compute stream) with no sync, in the chunks of hits under
+  // profile_scratch_bytes — per chunk the profile kernel, then the summary kernel and, with bins > 0, the histogram
+  // kernel. d_summary: device int64 [n * 7]; d_hist: device int32 [n * bins], never touched with bins == 0. An empty
+  // batch launches nothing.
+  void solve_summary_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                            int64_t* d_summary, int32_t* d_hist, int32_t bins, int32_t lo, int32_t width,
+                            hipStream_t stream);
+  // Host form (uploads through the pooled buffers; synchronous; fills stats()). hist_out may be null with bins == 0.
+  void solve_summary(const uint8_t* codes, const int64_t* offsets, int64_t n, int64_t* summary_out, int32_t* hist_out,
+                     int32_t bins, int32_t lo, int32_t width);
+  // Device time (ms) of the summary (and histogram) launches of the last summary call; as topk_select_ms().
+  double summary_ms() { return topk_select_ms(); }
+
   // ---- alignment report (definitions: moc/cpu_engine.hpp report_batch_cpu; kernels:
   // csrc/src/hip/report_kernels.hip): the sign counts and, optionally, the marker bytes of caller-supplied rows.
   // Byte letters and dense int64 offsets (wire batches: report_wire); no Semantics (row validity does not depend on
@@ -218,6 +239,8 @@ class HipEngine {
   void solve_hits_wire(const WireBatch& b, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
                        std::vector<Result>& rows_out, int64_t max_rows_hint = -1, int64_t radius = 0);
   void report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks);
+  void solve_summary_wire(const WireBatch& b, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo,
+                          int32_t width);
   // poffsets[0..n] of a host wire batch (profile_offsets of its decoded lengths; no GPU work)
   void wire_profile_offsets(const WireBatch& b, int64_t* poffsets) const;
 
@@ -325,8 +348,18 @@ class HipEngine {
     Result* d_rows;
     int64_t cap;
   };
+  struct SummaryCall {  // ... or when it is for a summary
+    int64_t* d_summary;
+    int32_t* d_hist;
+    int32_t bins, lo, width;
+  };
   void run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n, int K,
-                   void* d_dst, hipStream_t stream, const HitsCall* hits = nullptr, int64_t radius = 0);
+                   void* d_dst, hipStream_t stream, const HitsCall* hits = nullptr, int64_t radius = 0,
+                   const SummaryCall* summary = nullptr);
+  // throws unless bins, width and the batch's exactness bound (bounds::summary_exact) allow the call; touches nothing
+  void check_summary(const int64_t* h_offsets, int64_t n, int32_t bins, int32_t width) const;
+  void summary_placed(const Placed& p, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo, int32_t width,
+                      Stopwatch& wall);
 
   EngineOptions opt_;
   int device_ = 0;

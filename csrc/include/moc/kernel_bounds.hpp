@@ -129,6 +129,25 @@ constexpr int32_t kPeaksKeysPerThread = (kPeaksTile + 2 * kPeaksMaxRadius) / kPe
 static_assert((kPeaksTile + 2 * kPeaksMaxRadius) % kPeaksThreads == 0, "peaks: whole keys per thread");
 static_assert((kPeaksTile + 2 * kPeaksMaxRadius) * 8 <= 64 * 1024, "peaks: tile + halo within one workgroup's LDS");
 
+// ---- profile summary (summary_kernels.hip; definitions: moc/cpu_engine.hpp summary_batch_cpu): one wave per record,
+// kSummaryRecordsPerBlock waves (records) per workgroup; the optional histogram has 0 .. kSummaryMaxBins bins, one
+// int32 LDS counter per bin and wave. sum and sumsq are exact int64: every |score| <= M = min(2^31, W * L2) (a score
+// is an int32 sum of L2 table entries), so |sum| <= C * M and sumsq <= C * M^2 for a record of C entries.
+// summary_max_count is the largest C for which C * M^2 <= 2^63 - 1 (M^2 <= 2^62, so it is at least 2); a call whose
+// longest profile has more entries is refused on the host before anything is launched.
+constexpr int32_t kSummaryThreads = 256;
+constexpr int32_t kSummaryRecordsPerBlock = kSummaryThreads / 64;
+constexpr int32_t kSummaryMaxBins = 256;
+inline int64_t summary_max_count(int32_t max_abs_weight, int64_t max_l2) {
+  const int64_t w = std::max(max_abs_weight, 1), l2 = std::max<int64_t>(max_l2, 1);
+  const int64_t cap = int64_t{1} << 31;
+  const int64_t m = l2 >= cap || w > cap / l2 ? cap : std::min(cap, w * l2);
+  return INT64_MAX / (m * m);
+}
+inline bool summary_exact(int32_t max_abs_weight, int64_t max_l2, int64_t max_count) {
+  return max_count <= summary_max_count(max_abs_weight, max_l2);
+}
+
 // Form bits reported per solve (EngineStats::forms; Python: stats()["forms"]).
 enum FormBits : int32_t {
   kFormSwipeKBits = 1,    // swipe, int16 keys with k bits

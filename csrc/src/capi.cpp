@@ -766,6 +766,56 @@ int moc_engine_solve_hits_wire_distinct(void* e, const moc_wire_batch* w, int32_
   });
 }
 
+// ---- profile summary
+int moc_summary_geometry(int32_t* out3) {
+  out3[0] = moc::bounds::kSummaryRecordsPerBlock;
+  out3[1] = moc::bounds::kSummaryThreads;
+  out3[2] = moc::bounds::kSummaryMaxBins;
+  return 0;
+}
+
+int64_t moc_summary_bound(int32_t max_abs_weight, int64_t max_l2) {
+  return moc::bounds::summary_max_count(max_abs_weight, max_l2);
+}
+
+int moc_cpu_summary(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                    const int64_t* offsets, int64_t n, int semantics, int threads, int32_t bins, int32_t lo,
+                    int32_t width, int64_t* summary, int32_t* hist) {
+  return guard([&] {
+    moc::Weights w = weights_of(weights4);
+    moc::RecordBatch b = view_batch(codes, offsets, n);
+    moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
+    moc::ScoreTable t = moc::ScoreTable::build(w);
+    moc::summary_batch_cpu(t, seq1, L1, b, summary, hist, bins, lo, width, static_cast<moc::Semantics>(semantics),
+                           threads);
+  });
+}
+
+int moc_engine_solve_summary(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t bins, int32_t lo,
+                             int32_t width, int64_t* summary, int32_t* hist) {
+  return guard([&] { static_cast<moc::HipEngine*>(e)->solve_summary(codes, offsets, n, summary, hist, bins, lo, width); });
+}
+
+int moc_engine_solve_summary_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                    int64_t n, int32_t bins, int32_t lo, int32_t width, int64_t* d_summary,
+                                    int32_t* d_hist, void* stream) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_summary_device(d_codes, d_offsets, h_offsets, n, d_summary, d_hist, bins, lo,
+                                                          width, static_cast<hipStream_t>(stream));
+  });
+}
+
+int moc_engine_solve_summary_wire(void* e, const moc_wire_batch* w, int32_t bins, int32_t lo, int32_t width,
+                                  int64_t* summary, int32_t* hist) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_summary_wire(wire_batch(w), summary, hist, bins, lo, width);
+  });
+}
+
+int moc_engine_summary_ms(void* e, double* ms) {
+  return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->summary_ms(); });
+}
+
 int moc_engine_stats(void* e, double* out14) {
   return guard([&] {
     double* out13 = out14;

@@ -333,6 +333,50 @@ void peaks_filter(const ProfileEntry* prof, int64_t C, int64_t radius, uint8_t* 
   }
 }
 
+void check_summary_args(int32_t max_abs_weight, int64_t max_l2, int64_t max_count, int32_t bins, int32_t width) {
+  if (bins < 0 || bins > bounds::kSummaryMaxBins)
+    throw Error("summary: bins must be in 0.." + std::to_string(bounds::kSummaryMaxBins) + ", got " + std::to_string(bins));
+  if (width < 1) throw Error("summary: width must be at least 1, got " + std::to_string(width));
+  if (!bounds::summary_exact(max_abs_weight, max_l2, max_count))
+    throw Error("summary: exactness bound: a profile of " + std::to_string(max_count) + " entries with |score| <= min(2^31, " +
+                std::to_string(max_abs_weight) + " * " + std::to_string(max_l2) + ") may overflow the int64 sum of squares (at most " +
+                std::to_string(bounds::summary_max_count(max_abs_weight, max_l2)) + " entries per record are exact)");
+}
+
+void summary_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int64_t* summary,
+                       int32_t* hist, int32_t bins, int32_t lo, int32_t width, Semantics sem, int num_threads) {
+  const int64_t n = batch.size();
+  int64_t max_count = 0;
+  for (int64_t i = 0; i < n; ++i) max_count = std::max(max_count, candidate_offsets(L1, batch.length(i), sem));
+  check_summary_args(t.max_abs(), n ? batch.max_length() : 0, max_count, bins, width);
+  if (bins > 0 && !hist) throw Error("summary: bins > 0 need a hist buffer");
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
+    int64_t sum = 0, sumsq = 0, best = 0;
+    int32_t mn = INT32_MAX, mx = INT32_MIN;
+    int32_t* h = bins > 0 ? hist + i * bins : nullptr;
+    if (h) std::fill(h, h + bins, 0);
+    for (int64_t o = 0; o < C; ++o) {
+      const int64_t s = prof[o].score;
+      sum += s;
+      sumsq += s * s;
+      mn = std::min(mn, prof[o].score);
+      if (prof[o].score > mx) {  // strict: the smallest offset keeps a tie
+        mx = prof[o].score;
+        best = o;
+      }
+      if (h) ++h[summary_bin(prof[o].score, lo, width, bins)];
+    }
+    int64_t* row = summary + i * kSummaryCols;
+    row[0] = C;
+    row[1] = sum;
+    row[2] = sumsq;
+    row[3] = mn;
+    row[4] = mx;
+    row[5] = C > 0 ? best : 0;
+    row[6] = C > 0 ? prof[best].k : 0;
+  });
+}
+
 void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
                     Semantics sem, int num_threads, int64_t radius) {
   if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));

@@ -111,7 +111,7 @@ int parse_preload_set(const char* s) {
                {"swipe", kPreloadSwipeByte | kPreloadSwipeP33}, {"swipe8", kPreloadSwipeByte},
                {"swipe33", kPreloadSwipeP33}, {"tile16", kPreloadTile16}, {"mfma", kPreloadMfma},
                {"profile", kPreloadProfile}, {"report", kPreloadReport}, {"hits", kPreloadHits},
-               {"wire", kPreloadWire}, {"peaks", kPreloadPeaks}};
+               {"wire", kPreloadWire}, {"peaks", kPreloadPeaks}, {"summary", kPreloadSummary}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -1003,10 +1003,12 @@ double HipEngine::topk_select_ms() {
 
 // K == 0: the whole batch's profile -> d_dst (ProfileEntry, one chunk). K >= 1: top-K rows -> d_dst (Result
 // [n, K]), chunk by chunk through the bounded scratch. hits (with K == 0, d_dst unused): the same chunks, each
-// followed by count, prefix sum and compaction into the call's buffers. Plan buffer: poffsets (n + 1) | every
-// chunk's wave starts.
+// followed by count, prefix sum and compaction into the call's buffers. summary (likewise, without hits or a
+// radius): the same chunks, each followed by the summary and histogram kernels. Plan buffer: poffsets (n + 1) |
+// every chunk's wave starts.
 void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
-                            int K, void* d_dst, hipStream_t stream, const HitsCall* hits, int64_t radius) {
+                            int K, void* d_dst, hipStream_t stream, const HitsCall* hits, int64_t radius,
+                            const SummaryCall* summary) {
   if (!have_problem_) throw Error("HipEngine: profile / top-K before set_problem");
   if (K < 0 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
   check_peaks_radius(radius);
@@ -1016,8 +1018,11 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   if (n <= 0) return;
   if (n >= (int64_t{1} << 31) - 1) throw Error("profile / top-K: more than 2^31 - 2 records in one call");
   if (!stream) stream = s_compute_;
-  TraceRange tr(hits ? "moc.solve_hits_device" : K ? "moc.solve_topk_device" : "moc.solve_profile_device");
-  const bool chunked = K || hits;  // through the bounded scratch
+  TraceRange tr(summary ? "moc.solve_summary_device"
+                : hits  ? "moc.solve_hits_device"
+                : K     ? "moc.solve_topk_device"
+                        : "moc.solve_profile_device");
+  const bool chunked = K || hits || summary;  // through the bounded scratch
   const bool peaks = chunked && radius > 0;  // the distinct forms: a byte of peak marks beside every scratch entry
   const int64_t entry_bytes = static_cast<int64_t>(sizeof(ProfileEntry)) + (peaks ? 1 : 0);
   std::vector<int64_t> poff(static_cast<size_t>(n) + 1);
@@ -1034,7 +1039,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
     throw Error("Seq1 / Seq2 lengths beyond 2^30 exceed the device engine's offset range");
   // sub-tiles per wave tile, as the LUT tile kernel picks them, narrowed to the batch's widest offset range
   const int u = plan::profile_u(cfg_, sum_l2, n, max_need);
-  // chunks of consecutive records: the whole batch for a profile, bounded scratch for top-K and hits
+  // chunks of consecutive records: the whole batch for a profile, bounded scratch for top-K, hits and the summary
   struct Chunk {
     int64_t r0, r1;
     size_t starts_at, n_starts;
@@ -1123,7 +1128,22 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
         }
         dev::launch_peaks(ka, stream);
       }
-      if (hits) {
+      if (summary) {
+        dev::SummaryArgs sa;
+        sa.prof = pa.prof;
+        sa.poffsets = pa.poffsets;
+        sa.base = pa.base;
+        sa.prof_entries = pa.prof_entries;
+        sa.rec0 = c.r0;
+        sa.n_rec = c.r1 - c.r0;
+        sa.n_total = n;
+        sa.summary = summary->d_summary;
+        sa.hist = summary->d_hist;
+        sa.bins = summary->d_hist ? summary->bins : 0;
+        sa.lo = summary->lo;
+        sa.width = summary->width;
+        dev::launch_summary(sa, stream);
+      } else if (hits) {
         dev::HitsArgs ha;
         ha.prof = pa.prof;
         ha.poffsets = pa.poffsets;
@@ -1156,7 +1176,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   stats_.cells = cells;
   stats_.records = n;
   stats_.chunks = static_cast<int64_t>(chunks.size());
-  stats_.kernels = (hits ? 16 | 64 : 16) | (peaks ? 256 : 0);
+  stats_.kernels = (hits ? 16 | 64 : 16) | (peaks ? 256 : 0) | (summary ? 512 : 0);
 }
 
 void HipEngine::solve_profile_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
@@ -1285,6 +1305,58 @@ void HipEngine::hits_placed(const Placed& p, int32_t min_score, const int32_t* t
   }
   host_call_stats(wall, kernel_ms, p, hbytes * static_cast<size_t>(hits_passes_) + rbytes);
   if (thresholds) stats_.h2d_bytes += static_cast<int64_t>(tbytes);
+}
+
+// ---- profile summary ------------------------------------------------------------------------------------
+void HipEngine::check_summary(const int64_t* h_offsets, int64_t n, int32_t bins, int32_t width) const {
+  if (!have_problem_) throw Error("HipEngine: summary before set_problem");
+  int64_t max_l2 = 0, max_count = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t L2 = h_offsets[i + 1] - h_offsets[i];
+    max_l2 = std::max(max_l2, L2);
+    max_count = std::max(max_count, candidate_offsets(cfg_.L1, L2, sem_));
+  }
+  check_summary_args(table_.max_abs(), max_l2, max_count, bins, width);
+}
+
+void HipEngine::solve_summary_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                     int64_t n, int64_t* d_summary, int32_t* d_hist, int32_t bins, int32_t lo,
+                                     int32_t width, hipStream_t stream) {
+  check_summary(h_offsets, std::max<int64_t>(n, 0), bins, width);  // before any launch or change of state
+  if (n > 0 && !d_summary) throw Error("summary: no summary buffer");
+  if (n > 0 && bins > 0 && !d_hist) throw Error("summary: bins > 0 need a hist buffer");
+  const SummaryCall sc{d_summary, bins > 0 ? d_hist : nullptr, bins, lo, width};
+  run_profile(d_codes, d_offsets, h_offsets, n, 0, nullptr, stream, nullptr, 0, &sc);  // n <= 0: launches nothing
+}
+
+void HipEngine::solve_summary(const uint8_t* codes, const int64_t* offsets, int64_t n, int64_t* summary_out,
+                              int32_t* hist_out, int32_t bins, int32_t lo, int32_t width) {
+  check_summary(offsets, std::max<int64_t>(n, 0), bins, width);
+  if (n > 0 && bins > 0 && !hist_out) throw Error("summary: bins > 0 need a hist buffer");
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  if (n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  const size_t un = static_cast<size_t>(n);
+  const std::vector<int64_t> rebased =
+      upload_batch(codes, offsets, n, sizeof(int64_t) * kSummaryCols * un + sizeof(int32_t) * static_cast<size_t>(bins) * un);
+  summary_placed(placed_upload(rebased, n), summary_out, hist_out, bins, lo, width, wall);
+}
+
+// d_out: summary (7 n int64) | hist (n * bins int32)
+void HipEngine::summary_placed(const Placed& p, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo,
+                               int32_t width, Stopwatch& wall) {
+  Slot& s = *slots_[0];
+  const size_t un = static_cast<size_t>(p.n);
+  const size_t sbytes = sizeof(int64_t) * kSummaryCols * un, hbytes = sizeof(int32_t) * static_cast<size_t>(bins) * un;
+  char* d = static_cast<char*>(s.d_out);
+  solve_summary_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, reinterpret_cast<int64_t*>(d),
+                       reinterpret_cast<int32_t*>(d + sbytes), bins, lo, width, s_compute_);
+  copy_d2h(summary_out, d, sbytes, s_compute_);
+  if (hbytes) copy_d2h(hist_out, d + sbytes, hbytes, s_compute_);
+  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+  host_call_stats(wall, device_kernel_ms(), p, sbytes + hbytes);
 }
 
 // ---- alignment report -----------------------------------------------------------------------------------
@@ -1549,6 +1621,28 @@ void HipEngine::solve_hits_wire(const WireBatch& b, int32_t min_score, const int
   const size_t n = static_cast<size_t>(b.n);
   hits_placed(place_wire(b, sizeof(int64_t) * (n + 1) + sizeof(int32_t) * n), min_score, thresholds, hoffsets_out, rows_out,
               max_rows_hint, wall, radius);
+}
+
+void HipEngine::solve_summary_wire(const WireBatch& b, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo,
+                                   int32_t width) {
+  if (!have_problem_) throw Error("HipEngine: summary before set_problem");
+  validate_wire(b);
+  if (b.device) throw Error("the *_wire host forms take host batches; a device-resident one goes through decode_wire_device");
+  if (b.n > 0) {  // the bound needs the lengths: the host's dense offsets of the batch, before anything is launched
+    std::vector<int64_t> dense(static_cast<size_t>(b.n) + 1);
+    wire_dense_offsets(b, dense.data());
+    check_summary(dense.data(), b.n, bins, width);
+  } else {
+    check_summary(nullptr, 0, bins, width);
+  }
+  if (b.n > 0 && bins > 0 && !hist_out) throw Error("summary: bins > 0 need a hist buffer");
+  finish_wire();
+  if (b.n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  const size_t n = static_cast<size_t>(b.n);
+  summary_placed(place_wire(b, sizeof(int64_t) * kSummaryCols * n + sizeof(int32_t) * static_cast<size_t>(bins) * n),
+                 summary_out, hist_out, bins, lo, width, wall);
 }
 
 void HipEngine::report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks) {

@@ -7,13 +7,14 @@ window. See README.md and SURVEY.md.
 """
 from .models.problem import Problem
 from .models.scoring import PairClass, Semantics, Weights
-from .ops.align import (PROFILE_DTYPE, HipSearchEngine, align_hits_device, align_profile_device,
-                        align_report_device, align_search, align_search_device, align_topk_device,
-                        brute_force_native, decode_keys, decode_wire_cpu, device_count, profile_offsets, report_scores,
-                        search_cpu, search_hip, search_hits_cpu, search_keys_cpu, search_profile_cpu, search_report_cpu,
-                        search_topk_cpu, wire_batch_of)
+from .ops.align import (PROFILE_DTYPE, SUMMARY_COLS, HipSearchEngine, align_hits_device, align_profile_device,
+                        align_report_device, align_search, align_search_device, align_summary_device,
+                        align_topk_device, brute_force_native, decode_keys, decode_wire_cpu, device_count,
+                        profile_offsets, report_scores, search_cpu, search_hip, search_hits_cpu, search_keys_cpu,
+                        search_profile_cpu, search_report_cpu, search_summary_cpu, search_topk_cpu, summary_thresholds,
+                        summary_zscore, wire_batch_of)
 from .parallel.wire import WireSlice
-from .utils.io import format_hits, format_report, format_results, format_topk, write_results
+from .utils.io import format_hits, format_report, format_results, format_summary, format_topk, write_results
 from .utils.synthetic import make_synthetic
 
 __version__ = "0.1.0"
@@ -25,4 +26,6 @@ __all__ = [
     "search_report_cpu", "report_scores", "align_report_device", "format_report",
     "search_hits_cpu", "align_hits_device", "format_hits",
     "WireSlice", "decode_wire_cpu", "wire_batch_of",
+    "SUMMARY_COLS", "search_summary_cpu", "align_summary_device", "summary_zscore", "summary_thresholds",
+    "format_summary",
 ]

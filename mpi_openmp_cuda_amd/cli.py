@@ -16,7 +16,7 @@ from .models.problem import Problem
 from .models.scoring import Semantics
 from .parallel import dist as D
 from .parallel.search import DistributedSearch
-from .utils.io import format_hits, format_report, format_topk, write_results
+from .utils.io import format_hits, format_report, format_summary, format_topk, write_results
 
 
 def main(argv=None) -> int:
@@ -55,6 +55,16 @@ def main(argv=None) -> int:
                          "only when no offset within R of it (0..2048) scores higher, or the same at a smaller n, so "
                          "the one-column shadow of a placement and the rest of its slope drop out. Same line "
                          "formats, fewer lines; R = 0 prints what no flag prints")
+    ap.add_argument("--summary", action="store_true",
+                    help="after every result line print '  summary: offsets: C, min: A, max: B, mean: M, sd: S, z: Z': "
+                         "the record's candidate offsets, the extremes, mean and standard deviation of their scores, "
+                         "and how many standard deviations of the other offsets the best one lies above them (nan when "
+                         "undefined). Not with --top K > 1, --show-alignment, --min-score or --within; record slices "
+                         "on one node only (--partition records)")
+    ap.add_argument("--hist", default=None, metavar="LO:WIDTH:BINS",
+                    help="with --summary: one more line '  hist: c0 c1 ...', the counts of the record's scores in BINS "
+                         "(1..256) bins of WIDTH (>= 1) from LO up; scores outside land in the first and last bin (a "
+                         "negative LO takes the = form, --hist=-50:10:16)")
     a = ap.parse_args(argv)
     if not 1 <= a.top <= 64:
         ap.error("--top K: K must be in 1..64")
@@ -69,6 +79,19 @@ def main(argv=None) -> int:
         if not want_hits and a.top <= 1:
             ap.error("--distinct R filters the lines of --top K (K > 1) or --min-score / --within: give one of them")
     radius = a.distinct or 0
+    hist_args = (0, 0, 1)
+    if a.hist is not None:
+        if not a.summary:
+            ap.error("--hist LO:WIDTH:BINS needs --summary")
+        try:
+            h_lo, h_width, h_bins = (int(x) for x in a.hist.split(":"))
+        except ValueError:
+            ap.error("--hist LO:WIDTH:BINS: three integers separated by colons")
+        if not (-2 ** 31 <= h_lo < 2 ** 31 and 1 <= h_width < 2 ** 31 and 1 <= h_bins <= 256):
+            ap.error("--hist LO:WIDTH:BINS: LO an int32, WIDTH an int32 >= 1, BINS in 1..256")
+        hist_args = (h_bins, h_lo, h_width)
+    if a.summary and (a.top > 1 or a.show_alignment or want_hits):
+        ap.error("--summary does not combine with --top K > 1, --show-alignment, --min-score or --within")
     if a.min_score is not None and not -2 ** 31 <= a.min_score < 2 ** 31:
         ap.error("--min-score T: T must be an int32")
 
@@ -113,8 +136,24 @@ def main(argv=None) -> int:
                   "combines one packed key per record", file=sys.stderr)
         D.finalize(ctx)
         return 2
+    if a.summary and search.partition != "records":
+        if ctx.is_root:
+            print("--summary needs record slices (--partition records, one node); --partition offsets combines one "
+                  "packed key per record", file=sys.stderr)
+        D.finalize(ctx)
+        return 2
     hit_rows = None
-    if want_hits:
+    summary = None
+    if a.summary:
+        try:
+            summary = search.run_summary(problem, *hist_args, semantics=Semantics.parse(a.semantics))
+        except ValueError as e:  # the exactness bound: every rank raises it
+            if ctx.is_root:
+                print(f"input error: {e}", file=sys.stderr)
+            D.finalize(ctx)
+            return 1
+        results = None
+    elif want_hits:
         got = search.run_hits(problem, a.min_score, a.within, Semantics.parse(a.semantics), radius)
         results, hit_rows = (got[0], got[1:]) if ctx.is_root else (None, None)
     elif a.top > 1:
@@ -134,6 +173,9 @@ def main(argv=None) -> int:
             sys.stdout.flush()
         elif want_hits:
             sys.stdout.write(format_hits(results, *hit_rows))
+            sys.stdout.flush()
+        elif a.summary:
+            sys.stdout.write(format_summary(*summary))
             sys.stdout.flush()
         else:
             write_results(results)

@@ -245,6 +245,124 @@ def search_hits_cpu(problem: Problem, min_score=None, thresholds=None, within=No
     return rows, hoffsets
 
 
+# ---- profile summary: per-record moments, extremes and histogram of the profile (csrc/include/moc/cpu_engine.hpp)
+SUMMARY_COLS = ("count", "sum", "sumsq", "min", "max", "n", "k")
+SUMMARY_MAX_BINS = 256  # csrc/include/moc/kernel_bounds.hpp kSummaryMaxBins (tests compare it with the native value)
+_COUNT, _SUM, _SUMSQ, _MIN, _MAX = 0, 1, 2, 3, 4
+
+
+def summary_geometry() -> tuple:
+    """(records per workgroup of the GPU's summary kernels — one wave each —, threads per workgroup, largest
+    ``bins``) — csrc/include/moc/kernel_bounds.hpp; no GPU needed."""
+    g = np.zeros(3, np.int32)
+    _lib.check(_lib.lib().moc_summary_geometry(_lib.ptr(g)))
+    return int(g[0]), int(g[1]), int(g[2])
+
+
+def summary_bound(max_abs_weight: int, max_l2: int) -> int:
+    """The exactness bound of a summary: the most candidate offsets C a record may have so that the int64 sum of
+    squares cannot overflow, floor((2^63 - 1) / M^2) with M = min(2^31, max |W| * the call's longest record). A call
+    with a longer profile is refused before anything runs. No GPU needed."""
+    return int(_lib.lib().moc_summary_bound(int(max_abs_weight), int(max_l2)))
+
+
+def _summary_args(bins, lo, width) -> tuple:
+    bins, lo, width = int(bins), int(lo), int(width)
+    if not 0 <= bins <= SUMMARY_MAX_BINS:
+        raise ValueError(f"summary: bins must be in 0..{SUMMARY_MAX_BINS}, got {bins}")
+    if not 1 <= width <= _I32.max:
+        raise ValueError(f"summary: width must be an int32 of at least 1, got {width}")
+    if not _I32.min <= lo <= _I32.max:
+        raise ValueError(f"summary: lo {lo} is not an int32")
+    return bins, lo, width
+
+
+def _summary_check(rc):
+    """A native summary call's status: its argument and exactness-bound errors (messages that start with
+    "summary:") are ValueErrors, anything else a NativeError."""
+    if rc != 0:
+        msg = _lib.lib().moc_last_error().decode(errors="replace")
+        if msg.startswith("summary:"):
+            raise ValueError(msg)
+        raise _lib.NativeError(msg)
+
+
+def search_summary_cpu(problem: Problem, bins: int = 0, lo: int = 0, width: int = 1, semantics=Semantics.REFERENCE,
+                       threads: int = 0):
+    """Profile summary on the CPU engine: ``(summary, hist)``. ``summary`` is int64 [n, 7] with the columns
+    :data:`SUMMARY_COLS` — ``count`` the record's candidate offsets C, ``sum`` and ``sumsq`` of its profile scores
+    (:func:`search_profile_cpu`; exact), ``min`` and ``max`` over them, and ``(max, n, k)`` search_cpu's row; a
+    record without candidate offsets gives (0, 0, 0, INT32_MAX, INT32_MIN, 0, 0). ``hist`` is None with
+    ``bins = 0``, else int32 [n, bins]: a score s counts in bin clamp(floor((s - lo) / width), 0, bins - 1), so scores
+    below ``lo`` land in bin 0 and scores at or past ``lo + bins * width`` in the last; every row sums to ``count``.
+    ``bins`` in 0..256, ``width`` >= 1; raises ValueError for those and when the exactness bound
+    (:func:`summary_bound`) does not hold for the call."""
+    bins, lo, width = _summary_args(bins, lo, width)
+    sem = Semantics.parse(semantics)
+    summary = np.zeros((problem.n, len(SUMMARY_COLS)), np.int64)
+    hist = np.zeros((problem.n, bins), np.int32) if bins else None
+    _summary_check(_lib.lib().moc_cpu_summary(
+        _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+        _lib.ptr(problem.offsets), problem.n, int(sem), int(threads), bins, lo, width, _lib.ptr(summary),
+        _lib.ptr(hist)))
+    return summary, hist
+
+
+def summary_zscore(summary) -> np.ndarray:
+    """float64 [n]: how far each record's best score lies above its OTHER C - 1 profile entries, in their population
+    standard deviations — with mean' = (sum - max) / (C - 1) and var' = (sumsq - max^2) / (C - 1) - mean'^2,
+    z = (max - mean') / sqrt(var'). NaN when C < 3 or var' <= 0 (an all-equal rest). Reads nothing but the summary.
+    Both numerators, (C - 1) max - (sum - max) and (C - 1)(sumsq - max^2) - (sum - max)^2, are formed in exact
+    Python integers; only the square root and the final division are float64."""
+    import math
+
+    s = np.asarray(summary, dtype=np.int64).reshape(-1, len(SUMMARY_COLS))
+    out = np.full(s.shape[0], np.nan, np.float64)
+    for i, row in enumerate(s.tolist()):
+        c, tot, sq, mx = row[_COUNT], row[_SUM], row[_SUMSQ], row[_MAX]
+        if c < 3:
+            continue
+        rest = tot - mx
+        num = (c - 1) * (sq - mx * mx) - rest * rest  # (C - 1)^2 var'
+        if num > 0:
+            out[i] = ((c - 1) * mx - rest) / math.sqrt(num)
+    return out
+
+
+def summary_thresholds(summary, z):
+    """int32 [n] thresholds "z standard deviations above the rest": ceil(mean' + z * sd') with mean' and sd' of
+    :func:`summary_zscore`, clipped to int32, and INT32_MAX (no hit) where that z-score is NaN (C < 3 or
+    var' <= 0) — ready as ``thresholds`` of the hits calls. ``summary``: a numpy array, or a torch tensor — then the
+    result is a tensor on its device, computed there with float64 ops and no synchronisation, so summary ->
+    thresholds -> ``solve_hits_device`` runs on one stream. Both paths run the same float64 operations: sum - max
+    and sumsq - max^2 are exact int64, the rest rounds (var' = E'[s^2] - mean'^2 loses about mean'^2 / var' ulps)."""
+    z = float(z)
+    if isinstance(summary, np.ndarray) or not hasattr(summary, "device"):
+        s = np.asarray(summary, dtype=np.int64).reshape(-1, len(SUMMARY_COLS))
+        c, mx = s[:, _COUNT], s[:, _MAX]
+        c1 = np.maximum(c - 1, 1).astype(np.float64)
+        mean = (s[:, _SUM] - mx).astype(np.float64) / c1
+        var = (s[:, _SUMSQ] - mx * mx).astype(np.float64) / c1 - mean * mean
+        ok = (c >= 3) & (var > 0)
+        sd = np.sqrt(np.where(ok, var, 0.0))
+        t = np.ceil(mean + z * sd)
+        t = np.where(ok, np.clip(t, float(_I32.min), float(_I32.max)), float(_I32.max))
+        return t.astype(np.int64).astype(np.int32)
+    import torch
+
+    s = summary.reshape(-1, len(SUMMARY_COLS))
+    assert s.dtype == torch.int64
+    c, mx = s[:, _COUNT], s[:, _MAX]
+    c1 = torch.clamp(c - 1, min=1).to(torch.float64)
+    mean = (s[:, _SUM] - mx).to(torch.float64) / c1
+    var = (s[:, _SUMSQ] - mx * mx).to(torch.float64) / c1 - mean * mean
+    ok = (c >= 3) & (var > 0)
+    sd = torch.sqrt(torch.where(ok, var, torch.zeros_like(var)))
+    t = torch.ceil(mean + z * sd)
+    t = torch.where(ok, torch.clamp(t, float(_I32.min), float(_I32.max)), torch.full_like(t, float(_I32.max)))
+    return t.to(torch.int64).to(torch.int32).contiguous()
+
+
 # ---- alignment report: sign counts and marker bytes of result rows (csrc/include/moc/cpu_engine.hpp)
 REPORT_EMPTY = int(np.iinfo(np.int64).min)        # report_scores of an empty row (score INT32_MIN, top-K padding)
 REPORT_INVALID = int(np.iinfo(np.int64).min) + 1  # ... of a row whose (n, k) does not place the record in Seq1
@@ -765,8 +883,75 @@ class HipSearchEngine:
             _lib.check(_lib.lib().moc_engine_solve_hits_device(*head, *tail))
         return rows_t, hoffsets_t
 
+    # ---- profile summary (byte letters, dense offsets; csrc/src/hip/summary_kernels.hip)
+    def solve_summary(self, codes: np.ndarray, offsets: np.ndarray, bins: int = 0, lo: int = 0, width: int = 1):
+        """Host CSR -> ``(summary, hist)`` as :func:`search_summary_cpu` returns them, through the chunks of
+        :meth:`solve_hits` with the summary kernel (and, with ``bins`` > 0, the histogram kernel) behind each chunk's
+        profile: 56 + 4 ``bins`` bytes come back per record, never the profile. Synchronous;
+        ``stats()["kernels"]`` names ``summary``. ValueError as :func:`search_summary_cpu`, raised before anything is
+        launched and without a change to ``stats()``."""
+        bins, lo, width = _summary_args(bins, lo, width)
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        summary = np.zeros((n, len(SUMMARY_COLS)), np.int64)
+        hist = np.zeros((n, bins), np.int32) if bins else None
+        _summary_check(_lib.lib().moc_engine_solve_summary(self._h, _lib.ptr(codes), _lib.ptr(offsets), n, bins, lo,
+                                                           width, _lib.ptr(summary), _lib.ptr(hist)))
+        return summary, hist
+
+    def summary_ms(self) -> float:
+        """Device time (ms) of the summary and histogram launches of the last summary call; 0 unless the engine was
+        created with MOC_PROFILE_TIMING=1 in the environment. Waits for them."""
+        ms = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().moc_engine_summary_ms(self._h, ctypes.addressof(ms)))
+        return float(ms.value)
+
+    def solve_summary_device(self, codes_t, offsets_t, h_offsets: np.ndarray, bins: int = 0, lo: int = 0,
+                             width: int = 1, summary_t=None, hist_t=None, stream=None):
+        """Device-resident batch (as :meth:`solve_device`) -> ``(summary_t, hist_t)``: an int64 [n, 7] tensor and,
+        with ``bins`` > 0, an int32 [n, bins] tensor on the codes' device (allocated when None; every element of
+        both is written). With ``bins = 0`` no histogram work is launched, ``hist_t`` is returned as given (None
+        unless passed) and not touched. Queued on ``stream`` (default: the current stream); returns immediately —
+        :func:`summary_thresholds` of ``summary_t`` and :meth:`solve_hits_device` can follow on the same stream.
+        ValueError as :meth:`solve_summary`."""
+        import torch
+
+        bins, lo, width = _summary_args(bins, lo, width)
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        n = h_offsets.shape[0] - 1
+        assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        if summary_t is None:
+            summary_t = torch.empty((n, len(SUMMARY_COLS)), dtype=torch.int64, device=codes_t.device)
+        if hist_t is None and bins:
+            hist_t = torch.empty((n, bins), dtype=torch.int32, device=codes_t.device)
+        assert summary_t.dtype == torch.int64 and summary_t.is_contiguous()
+        assert tuple(summary_t.shape) == (n, len(SUMMARY_COLS))
+        if bins:
+            assert hist_t.dtype == torch.int32 and hist_t.is_contiguous() and tuple(hist_t.shape) == (n, bins)
+        _summary_check(_lib.lib().moc_engine_solve_summary_device(
+            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
+            n, bins, lo, width, ctypes.c_void_p(summary_t.data_ptr()),
+            ctypes.c_void_p(hist_t.data_ptr()) if bins else None, ctypes.c_void_p(stream.cuda_stream)))
+        return summary_t, hist_t
+
+    def solve_summary_wire(self, ws, bins: int = 0, lo: int = 0, width: int = 1, shift: int = 0):
+        """Host wire batch -> ``(summary, hist)``, as :meth:`solve_summary` on the decoded records. See
+        :meth:`solve_profile_wire`."""
+        bins, lo, width = _summary_args(bins, lo, width)
+        b, keep = wire_batch_of(ws, shift)
+        n = ws.n
+        summary = np.zeros((n, len(SUMMARY_COLS)), np.int64)
+        hist = np.zeros((n, bins), np.int32) if bins else None
+        _summary_check(_lib.lib().moc_engine_solve_summary_wire(self._h, ctypes.byref(b), bins, lo, width,
+                                                                _lib.ptr(summary), _lib.ptr(hist)))
+        del keep
+        return summary, hist
+
     # ---- alignment report (byte letters, dense offsets; csrc/src/hip/report_kernels.hip)
-    def report(self, codes: np.ndarray, offsets: np.ndarray, rows, marks: bool = False):
+    def report(self,codes: np.ndarray, offsets: np.ndarray, rows, marks: bool = False):
         """Host CSR + result rows ([n, 3] or [n, K, 3]) -> the counts (and marker bytes) :func:`search_report_cpu`
         returns, computed by the report kernels against the engine's Seq1. Synchronous; fills ``stats()``."""
         codes = np.ascontiguousarray(codes, dtype=np.uint8)
@@ -992,7 +1177,8 @@ class HipSearchEngine:
         d["r2"] = tuple(int(x) for x in list(v)[10:13])
         d["format"] = _lib.FORMAT_NAMES[int(d["format"])]
         d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16"), (16, "profile"),
-                                             (32, "report"), (64, "hits"), (128, "wire"), (256, "peaks"))
+                                             (32, "report"), (64, "hits"), (128, "wire"), (256, "peaks"),
+                                             (512, "summary"))
                         if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
@@ -1071,6 +1257,14 @@ def align_hits_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, mi
     distinct placements among them)."""
     return engine.solve_hits_device(codes_t, offsets_t, h_offsets, min_score, thresholds_t, within, cap, None, None,
                                     stream, radius)
+
+
+def align_summary_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, bins: int = 0, lo: int = 0,
+                         width: int = 1, stream=None):
+    """torch-facing op: the profile summary as ``(summary_t, hist_t)`` on the codes' device — an int64 [n, 7] tensor
+    (columns :data:`SUMMARY_COLS`) and an int32 [n, bins] tensor, or None with ``bins = 0``; see
+    :meth:`HipSearchEngine.solve_summary_device`."""
+    return engine.solve_summary_device(codes_t, offsets_t, h_offsets, bins, lo, width, None, None, stream)
 
 
 def align_report_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, rows_t, marks: bool = False,

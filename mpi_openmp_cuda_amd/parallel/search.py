@@ -28,8 +28,8 @@ from .. import _lib
 from ..models.problem import Problem
 from ..models.scoring import Semantics
 from ..ops.align import (HipSearchEngine, decode_keys, device_count, keys_to_ordered_int64, ordered_int64_to_keys,
-                        search_cpu, search_hits_cpu, search_keys_cpu, search_report_cpu, search_topk_cpu,
-                        within_thresholds)
+                        profile_offsets, search_cpu, search_hits_cpu, search_keys_cpu, search_report_cpu,
+                        search_summary_cpu, search_topk_cpu, summary_bound, within_thresholds, _summary_args)
 from ..utils.timer import PhaseTimer
 from . import dist as D
 from .partition import CPU_COST, GPU_COST, partition
@@ -240,6 +240,60 @@ class DistributedSearch:
             D.barrier(ctx)
             win.close(unlink=ctx.is_root)
         return (best.astype(np.int32), rows.astype(np.int32), hoffsets) if ctx.is_root else None
+
+    def run_summary(self, problem: Optional[Problem], bins: int = 0, lo: int = 0, width: int = 1,
+                    semantics=Semantics.REFERENCE):
+        """The profile summary (ops.align.search_summary_cpu's ``(summary, hist)``; the same ``bins``, ``lo`` and
+        ``width`` on every rank) for the ``records`` partition: every rank summarises its cost-balanced slice of the
+        node-shared input window into int64 arrays that are INT64_MIN outside the slice — the histogram widened to
+        int64 for the trip — and one MAX all-reduce of each combines them (no new transport). ``summary[:, 4:7]`` are
+        the search's rows. Returns ``(summary, hist)`` on the root (``hist`` None with ``bins = 0``), else None. The
+        exactness bound is checked for the whole batch on the root and every rank raises the same ValueError. One
+        node; byte letters through the engines' summary calls."""
+        if self.partition != "records":
+            raise ValueError("the summary runs on record slices (--partition records, one node): the offsets "
+                             "partition combines one packed key per record and cannot carry a record's moments")
+        bins, lo, width = _summary_args(bins, lo, width)
+        ctx, T = self.ctx, self.timer
+        sem = Semantics.parse(semantics)
+        bad = None
+        if ctx.is_root:  # a slice inside the bound where the batch is not would leave the ranks in different states
+            L2 = np.asarray(problem.lengths, dtype=np.int64)
+            cmax = int(np.diff(profile_offsets(problem.L1, L2, sem)).max()) if problem.n else 0
+            w = max(abs(int(x)) for x in problem.weights.as_list())
+            limit = summary_bound(w, int(L2.max()) if problem.n else 0)
+            bad = np.array([cmax if cmax > limit else 0, limit], np.int64)
+        bad = D.bcast_array(ctx, bad, 2, np.int64)
+        if int(bad[0]):
+            raise ValueError(f"summary: exactness bound: a profile of {int(bad[0])} entries may overflow the int64 sum "
+                             f"of squares (at most {int(bad[1])} entries per record are exact for this batch)")
+        with T.phase("bcast"):
+            prob, sem, n, total, bounds = self._setup(problem, sem)
+        b, e = int(bounds[ctx.rank]), int(bounds[ctx.rank + 1])
+        with T.phase("distribute"):
+            win = self._open_window(problem, n, total)
+        none = np.iinfo(np.int64).min
+        with T.phase("compute"):
+            summary = np.full((n, 7), none, np.int64)
+            hist = np.full((n, bins), none, np.int64)
+            if e > b:
+                offsets = np.asarray(win.offsets[b:e + 1])
+                if self.engine is not None:
+                    s, h = self.engine.solve_summary(np.asarray(win.codes), offsets, bins, lo, width)
+                else:
+                    sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
+                                  offsets - offsets[0])
+                    s, h = search_summary_cpu(sub, bins, lo, width, sem, self.threads)
+                summary[b:e] = s
+                if bins:
+                    hist[b:e] = h
+        with T.phase("gather"):
+            summary = D.allreduce_max_int64(ctx, summary.reshape(-1)).reshape(n, 7)
+            if bins:
+                hist = D.allreduce_max_int64(ctx, hist.reshape(-1)).reshape(n, bins)
+            D.barrier(ctx)
+            win.close(unlink=ctx.is_root)
+        return (summary, hist.astype(np.int32) if bins else None) if ctx.is_root else None
 
     def report(self, problem: Problem, rows: np.ndarray):
         """Root only: ``(counts, marks)`` of the search's rows (ops.align.search_report_cpu's outputs, with the

@@ -69,6 +69,39 @@ def format_hits(results, rows, hoffsets, first_index: int = 0) -> str:
     return "".join(out)
 
 
+def format_summary(summary, hist=None, first_index: int = 0) -> str:
+    """Results with their profile summary (int64 [n, 7] rows of ops.align.SUMMARY_COLS from the summary calls):
+    record i's line as :func:`format_results` prints it — its (score, n, k) are the summary's (max, n, k) — then
+    "  summary: offsets: C, min: A, max: B, mean: M, sd: S, z: Z": mean and population sd over the whole profile to
+    3 decimals, z = ops.align.summary_zscore to 2 decimals, each ``nan`` where it is not defined (no offsets; for z
+    fewer than 3, or an all-equal rest). With ``hist`` (int [n, B]) one more line "  hist: c0 c1 ...". The moments
+    are divided in exact Python integers."""
+    import math
+
+    from ..ops.align import SUMMARY_COLS, summary_zscore
+
+    s = np.asarray(summary, dtype=np.int64)
+    if s.ndim != 2 or s.shape[1] != len(SUMMARY_COLS):
+        raise ValueError(f"format_summary needs an [n, {len(SUMMARY_COLS)}] summary")
+    h = None if hist is None else np.asarray(hist, dtype=np.int64)
+    if h is not None and (h.ndim != 2 or h.shape[0] != s.shape[0]):
+        raise ValueError("format_summary needs a histogram of the summary's n records, [n, B]")
+    z = summary_zscore(s)
+    out = []
+    for i, (c, tot, sq, mn, mx, n, k) in enumerate(s.tolist()):
+        out.append(f"#{i + first_index}: score: {mx}, n: {n}, k: {k}\n")
+        if c > 0:
+            mean = f"{tot / c:.3f}"
+            sd = f"{math.sqrt(max(c * sq - tot * tot, 0) / (c * c)):.3f}"
+        else:
+            mean = sd = "nan"
+        zs = "nan" if math.isnan(z[i]) else f"{z[i]:.2f}"
+        out.append(f"  summary: offsets: {c}, min: {mn}, max: {mx}, mean: {mean}, sd: {sd}, z: {zs}\n")
+        if h is not None:
+            out.append("  hist: " + " ".join(str(v) for v in h[i].tolist()) + "\n")
+    return "".join(out)
+
+
 def format_report(problem, rows, counts, marks, first_index: int = 0) -> str:
     """Results with their alignments. ``rows`` [n, 3] print as :func:`format_results` does and [n, K, 3] as
     :func:`format_topk` does; after the line of every real row — not an empty one (score INT32_MIN), nor one
