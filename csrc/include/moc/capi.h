@@ -302,6 +302,30 @@ int moc_engine_solve_summary_wire(void* e, const moc_wire_batch* b, int32_t bins
                                   int64_t* summary, int32_t* hist);
 /* device time (ms) of the last summary call's summary + histogram launches (MOC_PROFILE_TIMING=1; else 0) */
 int moc_engine_summary_ms(void* e, double* ms);
+/* ---- multi-target search (moc/cpu_engine.hpp targets_batch_cpu) ----
+ * Seq1 is a catalog: T target sequences concatenated without separators, delimited by starts (int64 [T + 1], strictly
+ * rising from 0 to L1; 1 <= T <= 4096). rows: moc_result [n * T], record-major: rows[i * T + t] is what the search
+ * returns for record i against target t alone, n relative to the target's start ((INT32_MIN, 0, 0) where the record
+ * is longer than the target). Errors in T or starts are reported before any work, with a message that starts with
+ * "targets:". The engine forms are as moc_engine_solve_summary*: the host and wire forms synchronous, the device
+ * form queued on `stream` without a sync (d_rows: device moc_result [n * T]; d_starts: a device copy of h_starts, or
+ * NULL — then the engine uploads h_starts with its plan). */
+int moc_cpu_targets(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                    const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics, int threads,
+                    moc_result* rows);
+/* 0 when starts / T describe a target set over a catalog of L1 letters, else the "targets:" error; no GPU needed */
+int moc_check_targets(const int64_t* starts, int64_t T, int64_t L1);
+/* out4: the largest T, threads per workgroup of the GPU's targets kernel, and the longest slices a 4-lane and a
+ * 16-lane group take (moc/kernel_bounds.hpp); no GPU needed */
+int moc_targets_geometry(int32_t* out4);
+int moc_engine_solve_targets(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
+                             int64_t T, moc_result* rows);
+int moc_engine_solve_targets_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                    int64_t n, const int64_t* d_starts, const int64_t* h_starts, int64_t T,
+                                    moc_result* d_rows, void* stream);
+int moc_engine_solve_targets_wire(void* e, const moc_wire_batch* b, const int64_t* starts, int64_t T, moc_result* rows);
+/* device time (ms) of the last targets call's select launches (MOC_PROFILE_TIMING=1; else 0) */
+int moc_engine_targets_ms(void* e, double* ms);
 /* stats: kernel_ms, total_ms, h2d_bytes, d2h_bytes, chunks, cells, records, direct, format, kernels,
  * r2 smin, r2 kw, r2 j, forms (moc::bounds::FormBits of the last solve) */
 int moc_engine_stats(void* e, double* out14);

@@ -133,6 +133,28 @@ void check_summary_args(int32_t max_abs_weight, int64_t max_l2, int64_t max_coun
 void summary_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int64_t* summary,
                        int32_t* hist, int32_t bins, int32_t lo, int32_t width, Semantics sem, int num_threads = 0);
 
+// ---- multi-target search: every record's best alignment against each of T target sequences
+// A target set is T sequences of lengths len_t >= 1, 1 <= T <= bounds::kTargetsMax, stored as their plain
+// concatenation (the catalog, no separator letters) with starts (int64 [T + 1]): starts[0] = 0, starts[t + 1] =
+// starts[t] + len_t, starts[T] = L1. The catalog IS Seq1 (s1, L1). check_targets throws Error ("targets: ...")
+// unless T is in range and starts rises strictly from 0 to L1.
+// out[i * T + t] = exactly solve_record(record i against target t alone), n relative to the target's start. With
+// P the catalog's profile of record i (L2 letters), b = starts[t] and len = len_t:
+//   L2 > len (or L2 > L1, or L2 < 1): no_candidate().
+//   slice: the entries P[b + o], o in [0, len - L2). Every read of such an entry stays inside the target
+//     (b + o + L2 <= b + len - 1) and b + o < L1 - L2, so its mutated candidates exist under either semantics:
+//     they are the target's own profile entries.
+//   boundary diagonal: the un-mutated score(b + len - L2, 0) as the entry (score, k = 0) at local offset len - L2,
+//     taking part iff sem == Spec (the target's final, k = 0-only offset) or len == L2 (equal lengths: (0, 0)
+//     only, under both semantics). Summed from the letters and the table, never read from P: the catalog's entry
+//     there also holds mutated candidates that read the next target's first letter.
+//   row: the better()-maximum over slice and boundary entry — highest score, then smallest local offset, with that
+//     entry's k. The boundary entry has the largest offset, so it wins only with a strictly higher score.
+// T = 1: out equals solve_batch_cpu row for row. One record's catalog profile exists at a time per thread.
+void check_targets(const int64_t* starts, int64_t T, int64_t L1);
+void targets_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                       const int64_t* starts, int64_t T, Result* out, Semantics sem, int num_threads = 0);
+
 // ---- alignment report: the signs under a result row's letter pairs
 // A row is a Result {score, n, k} of record i (L2 letters) against Seq1; rows[i*K .. i*K+K) belong to record i.
 //   empty row   (score == kNoCandidateScore, e.g. top-K padding): counts {0,0,0,0}, marker bytes 0, nothing read

@@ -415,6 +415,27 @@ struct SummaryArgs {
 // Queues the summary kernel and, when bins > 0, the histogram kernel on `stream`.
 void launch_summary(const SummaryArgs& sa, hipStream_t stream);
 
+// ---- multi-target search (targets_kernels.hip; definitions: moc/cpu_engine.hpp targets_batch_cpu)
+// One chunk of consecutive records [rec0, rec0 + n_rec) whose catalog profile lies where hits_count_kernel reads
+// it: prof[poffsets[r] - base + o]. The chunk's n_rec * T (record, target) pairs each get a group of `group`
+// consecutive lanes (4, 16 or 64); pair (r, t) stores its row at out[(r * T + t) * 3 ..) (batch-wide record index;
+// every row is stored, nothing is accumulated into).
+struct TargetsArgs {
+  const ProfileEntry* prof = nullptr;
+  const int64_t* poffsets = nullptr;
+  int64_t base = 0;
+  int64_t prof_entries = 0;  // entries of `prof` (debug builds check the load index against it)
+  int64_t rec0 = 0, n_rec = 0;
+  int64_t n_total = 0;       // records of the batch (debug builds check the store index against it)
+  const int64_t* starts = nullptr;  // device int64 [T + 1]
+  int32_t T = 0;
+  int32_t group = 64;        // lanes per pair: 4, 16 or 64
+  Result* out = nullptr;     // device, [n_total * T]
+};
+// Queues the select kernel (more than one launch when the blocks would pass the grid limit) on `stream`; pv
+// supplies the LUT, Seq1 (padded), L1 and the semantics, bv the records' letters.
+void launch_targets(const TargetsArgs& ta, const ProblemView& pv, const BatchView& bv, hipStream_t stream);
+
 // Loads every kernel file's code object onto the current device now (HIP loads them lazily, at the first
 // launch from each file: milliseconds inside the first timed search of a job otherwise).
 void preload_align_kernels();
@@ -429,6 +450,7 @@ void preload_hits_kernels();
 void preload_wire_kernels();
 void preload_peaks_kernels();
 void preload_summary_kernels();
+void preload_targets_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -444,6 +466,7 @@ enum PreloadSet : unsigned {
   kPreloadWire = 512,    // wire_kernels.hip: likewise
   kPreloadPeaks = 1024,  // peaks_kernels.hip: likewise
   kPreloadSummary = 2048,  // summary_kernels.hip: likewise
+  kPreloadTargets = 4096,  // targets_kernels.hip: likewise
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -458,9 +481,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadWire) preload_wire_kernels();
   if (set & kPreloadPeaks) preload_peaks_kernels();
   if (set & kPreloadSummary) preload_summary_kernels();
+  if (set & kPreloadTargets) preload_targets_kernels();
 }
 // "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
-// profile, report, hits, wire, peaks, summary;
+// profile, report, hits, wire, peaks, summary, targets;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

@@ -63,7 +63,8 @@ struct EngineStats {
                          // (LUT tile kernel), 8 tile16, 16 profile (per-offset profile / top-K), 32 report,
                          // 64 hits (count / scan / compact, next to 16), 128 wire (decode kernels of a *_wire call),
                          // 256 peaks (the peak filter and masked select / hits kernels of a distinct call),
-                         // 512 summary (the summary / histogram kernels, next to 16)
+                         // 512 summary (the summary / histogram kernels, next to 16),
+                         // 1024 targets (the multi-target select kernel, next to 16)
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -195,6 +196,28 @@ class HipEngine {
   // Device time (ms) of the summary (and histogram) launches of the last summary call; as topk_select_ms().
   double summary_ms() { return topk_select_ms(); }
 
+  // ---- multi-target search (definitions: moc/cpu_engine.hpp targets_batch_cpu; kernel:
+  // csrc/src/hip/targets_kernels.hip): the engine's Seq1 is a catalog of T targets delimited by starts (int64
+  // [T + 1], strictly rising from 0 to L1), and every record gets one row per target — what solve would return for
+  // that record against that target alone, n relative to the target's start: rows [n * T], record-major. Limits as
+  // hits: byte letters and dense int64 offsets (wire batches: solve_targets_wire), n < 2^31 - 1. Before anything is
+  // launched or any state changes, T (1 .. bounds::kTargetsMax) and starts are checked, and a call outside them
+  // throws an Error that starts with "targets:".
+  // Device form: queued on `stream` (0 = engine compute stream) with no sync, in the chunks of hits under
+  // profile_scratch_bytes — per chunk the profile kernel over the catalog, then the targets select kernel over the
+  // chunk's (record, target) pairs, its lane-group size chosen from the chunk's longest slice
+  // (bounds::targets_group; MOC_TARGETS_GROUP=4|16|64 at engine start forces one). d_starts: a device copy of
+  // h_starts, or null — then h_starts is uploaded with the plan buffer. h_starts is read during the call only.
+  // d_out: device Result [n * T], every row stored. An empty batch launches nothing.
+  void solve_targets_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                            const int64_t* d_starts, const int64_t* h_starts, int64_t T, Result* d_out,
+                            hipStream_t stream);
+  // Host form (uploads through the pooled buffers; synchronous; fills stats()).
+  void solve_targets(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T,
+                     Result* out);
+  // Device time (ms) of the targets select launches of the last targets call; as topk_select_ms().
+  double targets_ms() { return topk_select_ms(); }
+
   // ---- alignment report (definitions: moc/cpu_engine.hpp report_batch_cpu; kernels:
   // csrc/src/hip/report_kernels.hip): the sign counts and, optionally, the marker bytes of caller-supplied rows.
   // Byte letters and dense int64 offsets (wire batches: report_wire); no Semantics (row validity does not depend on
@@ -241,6 +264,7 @@ class HipEngine {
   void report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks);
   void solve_summary_wire(const WireBatch& b, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo,
                           int32_t width);
+  void solve_targets_wire(const WireBatch& b, const int64_t* starts, int64_t T, Result* out);
   // poffsets[0..n] of a host wire batch (profile_offsets of its decoded lengths; no GPU work)
   void wire_profile_offsets(const WireBatch& b, int64_t* poffsets) const;
 
@@ -353,9 +377,17 @@ class HipEngine {
     int32_t* d_hist;
     int32_t bins, lo, width;
   };
+  struct TargetsCall {  // ... or when it is for a multi-target search
+    const int64_t* d_starts;  // device [T + 1], or null: h_starts goes up with the plan buffer
+    const int64_t* h_starts;
+    int64_t T;
+    Result* d_out;
+  };
   void run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n, int K,
                    void* d_dst, hipStream_t stream, const HitsCall* hits = nullptr, int64_t radius = 0,
-                   const SummaryCall* summary = nullptr);
+                   const SummaryCall* summary = nullptr, const TargetsCall* targets = nullptr);
+  void check_targets_call(const int64_t* h_starts, int64_t T) const;  // throws unless T and starts are valid; touches nothing
+  void targets_placed(const Placed& p, const int64_t* starts, int64_t T, Result* out, Stopwatch& wall);
   // throws unless bins, width and the batch's exactness bound (bounds::summary_exact) allow the call; touches nothing
   void check_summary(const int64_t* h_offsets, int64_t n, int32_t bins, int32_t width) const;
   void summary_placed(const Placed& p, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo, int32_t width,
@@ -402,6 +434,7 @@ class HipEngine {
   void* d_prof_scratch_ = nullptr;
   size_t d_prof_scratch_cap_ = 0;
   bool profile_timing_ = false;
+  int targets_group_ = 0;  // MOC_TARGETS_GROUP: 4, 16 or 64 forces that lane-group size; 0: chosen per chunk
   std::vector<hipEvent_t> ev_select_;
   size_t ev_select_used_ = 0;
   // hits: the scan's block sums, the host form's row buffer, and its pass count

@@ -148,6 +148,21 @@ inline bool summary_exact(int32_t max_abs_weight, int64_t max_l2, int64_t max_co
   return max_count <= summary_max_count(max_abs_weight, max_l2);
 }
 
+// ---- multi-target search (targets_kernels.hip; definitions: moc/cpu_engine.hpp targets_batch_cpu): a target set
+// holds 1 .. kTargetsMax sequences. A group of G consecutive lanes (4, 16 or 64) owns one (record, target) pair;
+// the host picks G per chunk from the chunk's longest slice (entries of a pair's slice of the catalog profile):
+// up to kTargetsGroup4MaxSlice entries G = 4, up to kTargetsGroup16MaxSlice G = 16, else a wave. Tuning constants
+// only, every G gives the same rows for any slice length. Measured on input6-shaped records (profiles/targets/
+// README.md): at slices of up to 20 entries G = 4 takes 0.88 ms where G = 16 takes 1.39, at 46 they tie, from 98 on
+// G = 16 is ahead; G = 16 still leads a wave at 410 (0.67 against 0.74 ms) and trails it at 826 (0.78 against 0.65).
+constexpr int32_t kTargetsMax = 4096;
+constexpr int32_t kTargetsThreads = 256;
+constexpr int64_t kTargetsGroup4MaxSlice = 32;
+constexpr int64_t kTargetsGroup16MaxSlice = 512;
+inline int targets_group(int64_t max_slice) {
+  return max_slice <= kTargetsGroup4MaxSlice ? 4 : max_slice <= kTargetsGroup16MaxSlice ? 16 : 64;
+}
+
 // Form bits reported per solve (EngineStats::forms; Python: stats()["forms"]).
 enum FormBits : int32_t {
   kFormSwipeKBits = 1,    // swipe, int16 keys with k bits

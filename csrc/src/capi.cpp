@@ -816,6 +816,60 @@ int moc_engine_summary_ms(void* e, double* ms) {
   return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->summary_ms(); });
 }
 
+// ---- multi-target search
+int moc_targets_geometry(int32_t* out4) {
+  out4[0] = moc::bounds::kTargetsMax;
+  out4[1] = moc::bounds::kTargetsThreads;
+  out4[2] = static_cast<int32_t>(moc::bounds::kTargetsGroup4MaxSlice);
+  out4[3] = static_cast<int32_t>(moc::bounds::kTargetsGroup16MaxSlice);
+  return 0;
+}
+
+int moc_check_targets(const int64_t* starts, int64_t T, int64_t L1) {
+  return guard([&] { moc::check_targets(starts, T, L1); });
+}
+
+int moc_cpu_targets(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                    const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics, int threads,
+                    moc_result* rows) {
+  return guard([&] {
+    moc::check_targets(starts, T, L1);
+    moc::Weights w = weights_of(weights4);
+    moc::RecordBatch b = view_batch(codes, offsets, n);
+    moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
+    moc::ScoreTable t = moc::ScoreTable::build(w);
+    moc::targets_batch_cpu(t, seq1, L1, b, starts, T, reinterpret_cast<moc::Result*>(rows),
+                           static_cast<moc::Semantics>(semantics), threads);
+  });
+}
+
+int moc_engine_solve_targets(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
+                             int64_t T, moc_result* rows) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_targets(codes, offsets, n, starts, T, reinterpret_cast<moc::Result*>(rows));
+  });
+}
+
+int moc_engine_solve_targets_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                    int64_t n, const int64_t* d_starts, const int64_t* h_starts, int64_t T,
+                                    moc_result* d_rows, void* stream) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_targets_device(d_codes, d_offsets, h_offsets, n, d_starts, h_starts, T,
+                                                          reinterpret_cast<moc::Result*>(d_rows),
+                                                          static_cast<hipStream_t>(stream));
+  });
+}
+
+int moc_engine_solve_targets_wire(void* e, const moc_wire_batch* w, const int64_t* starts, int64_t T, moc_result* rows) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_targets_wire(wire_batch(w), starts, T, reinterpret_cast<moc::Result*>(rows));
+  });
+}
+
+int moc_engine_targets_ms(void* e, double* ms) {
+  return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->targets_ms(); });
+}
+
 int moc_engine_stats(void* e, double* out14) {
   return guard([&] {
     double* out13 = out14;

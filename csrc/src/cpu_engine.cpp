@@ -377,6 +377,54 @@ void summary_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const
   });
 }
 
+void check_targets(const int64_t* starts, int64_t T, int64_t L1) {
+  if (T < 1 || T > bounds::kTargetsMax)
+    throw Error("targets: T must be in 1.." + std::to_string(bounds::kTargetsMax) + ", got " + std::to_string(T));
+  if (!starts) throw Error("targets: no starts");
+  if (starts[0] != 0) throw Error("targets: starts[0] must be 0, got " + std::to_string(starts[0]));
+  for (int64_t t = 0; t < T; ++t)
+    if (starts[t + 1] <= starts[t])
+      throw Error("targets: starts must rise strictly (every target holds at least one letter): starts[" +
+                  std::to_string(t + 1) + "] = " + std::to_string(starts[t + 1]) + " after " + std::to_string(starts[t]));
+  if (starts[T] != L1)
+    throw Error("targets: starts[T] must be the catalog's length " + std::to_string(L1) + ", got " + std::to_string(starts[T]));
+}
+
+void targets_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                       const int64_t* starts, int64_t T, Result* out, Semantics sem, int num_threads) {
+  check_targets(starts, T, L1);
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
+    const int64_t L2 = batch.length(i);
+    const uint8_t* s2 = batch.record(i);
+    Result* rows = out + i * T;
+    for (int64_t q = 0; q < T; ++q) {
+      const int64_t b = starts[q], len = starts[q + 1] - b;
+      if (L2 < 1 || L2 > len || L2 > L1) {
+        rows[q] = no_candidate();
+        continue;
+      }
+      Result best = no_candidate();
+      bool have = false;
+      const int64_t slice = len - L2;  // b + slice <= L1 - L2 <= C
+      for (int64_t o = 0; o < slice; ++o) {
+        const ProfileEntry& e = prof[b + o];
+        if (!have || e.score > best.score) {  // strict: the smallest offset keeps a tie
+          best = Result{e.score, static_cast<int32_t>(o), e.k};
+          have = true;
+        }
+      }
+      if (sem == Semantics::Spec || slice == 0) {  // the boundary diagonal, from the letters
+        const uint8_t* a = s1 + b + slice;
+        int32_t s = 0;
+        for (int64_t l = 0; l < L2; ++l) s += t.lut[s2[l] * kLutStride + a[l]];
+        if (!have || s > best.score) best = Result{s, static_cast<int32_t>(slice), 0};
+      }
+      rows[q] = best;
+    }
+    (void)C;
+  });
+}
+
 void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
                     Semantics sem, int num_threads, int64_t radius) {
   if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));

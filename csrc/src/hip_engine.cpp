@@ -111,7 +111,8 @@ int parse_preload_set(const char* s) {
                {"swipe", kPreloadSwipeByte | kPreloadSwipeP33}, {"swipe8", kPreloadSwipeByte},
                {"swipe33", kPreloadSwipeP33}, {"tile16", kPreloadTile16}, {"mfma", kPreloadMfma},
                {"profile", kPreloadProfile}, {"report", kPreloadReport}, {"hits", kPreloadHits},
-               {"wire", kPreloadWire}, {"peaks", kPreloadPeaks}, {"summary", kPreloadSummary}};
+               {"wire", kPreloadWire}, {"peaks", kPreloadPeaks}, {"summary", kPreloadSummary},
+               {"targets", kPreloadTargets}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -163,6 +164,10 @@ HipEngine::HipEngine(const EngineOptions& opt) : opt_(opt) {
   }
   if (const char* t16 = std::getenv("MOC_TILE16")) tile16_ = std::atoi(t16) != 0;
   if (const char* pt = std::getenv("MOC_PROFILE_TIMING")) profile_timing_ = std::atoi(pt) != 0;
+  if (const char* tg = std::getenv("MOC_TARGETS_GROUP")) {  // forces one lane-group size of the targets kernel
+    const int g = std::atoi(tg);
+    if (g == 4 || g == 16 || g == 64) targets_group_ = g;
+  }
   // MOC_TILE16_WINWIDE=0: short records on an L1 ~ 1500..3050 problem keep the whole byte-pair image (A/B)
   if (const char* ww = std::getenv("MOC_TILE16_WINWIDE")) cfg_.tile16_window_wide = std::atoi(ww) != 0;
   if (const char* w8 = std::getenv("MOC_TILE16_WIN_U8")) cfg_.short_window_u8 = std::atoi(w8) != 0;
@@ -1004,11 +1009,12 @@ double HipEngine::topk_select_ms() {
 // K == 0: the whole batch's profile -> d_dst (ProfileEntry, one chunk). K >= 1: top-K rows -> d_dst (Result
 // [n, K]), chunk by chunk through the bounded scratch. hits (with K == 0, d_dst unused): the same chunks, each
 // followed by count, prefix sum and compaction into the call's buffers. summary (likewise, without hits or a
-// radius): the same chunks, each followed by the summary and histogram kernels. Plan buffer: poffsets (n + 1) |
-// every chunk's wave starts.
+// radius): the same chunks, each followed by the summary and histogram kernels. targets (likewise): the same chunks,
+// each followed by the targets select kernel over the chunk's (record, target) pairs. Plan buffer: poffsets (n + 1)
+// | every chunk's wave starts | the targets call's starts (T + 1; when the caller gave no device copy).
 void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
                             int K, void* d_dst, hipStream_t stream, const HitsCall* hits, int64_t radius,
-                            const SummaryCall* summary) {
+                            const SummaryCall* summary, const TargetsCall* targets) {
   if (!have_problem_) throw Error("HipEngine: profile / top-K before set_problem");
   if (K < 0 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
   check_peaks_radius(radius);
@@ -1018,11 +1024,12 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   if (n <= 0) return;
   if (n >= (int64_t{1} << 31) - 1) throw Error("profile / top-K: more than 2^31 - 2 records in one call");
   if (!stream) stream = s_compute_;
-  TraceRange tr(summary ? "moc.solve_summary_device"
+  TraceRange tr(targets   ? "moc.solve_targets_device"
+                : summary ? "moc.solve_summary_device"
                 : hits  ? "moc.solve_hits_device"
                 : K     ? "moc.solve_topk_device"
                         : "moc.solve_profile_device");
-  const bool chunked = K || hits || summary;  // through the bounded scratch
+  const bool chunked = K || hits || summary || targets;  // through the bounded scratch
   const bool peaks = chunked && radius > 0;  // the distinct forms: a byte of peak marks beside every scratch entry
   const int64_t entry_bytes = static_cast<int64_t>(sizeof(ProfileEntry)) + (peaks ? 1 : 0);
   std::vector<int64_t> poff(static_cast<size_t>(n) + 1);
@@ -1066,7 +1073,9 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
     max_records = std::max(max_records, c.r1 - c.r0);
   }
   const size_t poff_bytes = sizeof(int64_t) * poff.size();
-  const size_t plan_bytes = poff_bytes + sizeof(dev::WaveStart) * starts.size();
+  const size_t starts_at = poff_bytes + sizeof(dev::WaveStart) * starts.size();  // 8-byte aligned: both parts are
+  const size_t tstarts_bytes = targets && !targets->d_starts ? sizeof(int64_t) * (static_cast<size_t>(targets->T) + 1) : 0;
+  const size_t plan_bytes = starts_at + tstarts_bytes;
   MOC_HIP_CHECK(hipEventSynchronize(ev_plan_));  // previous call's plan buffers are free again
   ensure(d_plan_, d_plan_cap_, plan_bytes);
   ensure_host(h_plan_, h_plan_cap_, plan_bytes);
@@ -1079,6 +1088,10 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
            sizeof(int64_t) * static_cast<size_t>((max_records + bounds::kHitsScanBlockRecords - 1) / bounds::kHitsScanBlockRecords));
   std::memcpy(h_plan_, poff.data(), poff_bytes);
   std::memcpy(static_cast<char*>(h_plan_) + poff_bytes, starts.data(), sizeof(dev::WaveStart) * starts.size());
+  if (tstarts_bytes) std::memcpy(static_cast<char*>(h_plan_) + starts_at, targets->h_starts, tstarts_bytes);
+  int64_t max_target = 0;  // the longest target: with a chunk's shortest record, its longest slice
+  if (targets)
+    for (int64_t t = 0; t < targets->T; ++t) max_target = std::max(max_target, targets->h_starts[t + 1] - targets->h_starts[t]);
   upload_staged(d_plan_, h_plan_, plan_bytes, stream);
   dev::ProblemView pv = problem_view(max_l2);
   pv.prof16 = nullptr;  // the LUT sweep: exact int32 for any weights
@@ -1128,7 +1141,24 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
         }
         dev::launch_peaks(ka, stream);
       }
-      if (summary) {
+      if (targets) {
+        dev::TargetsArgs ta;
+        ta.prof = pa.prof;
+        ta.poffsets = pa.poffsets;
+        ta.base = pa.base;
+        ta.prof_entries = pa.prof_entries;
+        ta.rec0 = c.r0;
+        ta.n_rec = c.r1 - c.r0;
+        ta.n_total = n;
+        ta.starts = targets->d_starts ? targets->d_starts
+                                      : reinterpret_cast<const int64_t*>(static_cast<const char*>(d_plan_) + starts_at);
+        ta.T = static_cast<int32_t>(targets->T);
+        int64_t min_l2 = INT64_MAX;
+        for (int64_t r = c.r0; r < c.r1; ++r) min_l2 = std::min(min_l2, h_offsets[r + 1] - h_offsets[r]);
+        ta.group = targets_group_ ? targets_group_ : bounds::targets_group(std::max<int64_t>(max_target - min_l2, 0));
+        ta.out = targets->d_out;
+        dev::launch_targets(ta, pv, bv, stream);
+      } else if (summary) {
         dev::SummaryArgs sa;
         sa.prof = pa.prof;
         sa.poffsets = pa.poffsets;
@@ -1176,7 +1206,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   stats_.cells = cells;
   stats_.records = n;
   stats_.chunks = static_cast<int64_t>(chunks.size());
-  stats_.kernels = (hits ? 16 | 64 : 16) | (peaks ? 256 : 0) | (summary ? 512 : 0);
+  stats_.kernels = (hits ? 16 | 64 : 16) | (peaks ? 256 : 0) | (summary ? 512 : 0) | (targets ? 1024 : 0);
 }
 
 void HipEngine::solve_profile_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
@@ -1357,6 +1387,46 @@ void HipEngine::summary_placed(const Placed& p, int64_t* summary_out, int32_t* h
   if (hbytes) copy_d2h(hist_out, d + sbytes, hbytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
   host_call_stats(wall, device_kernel_ms(), p, sbytes + hbytes);
+}
+
+// ---- multi-target search --------------------------------------------------------------------------------
+void HipEngine::check_targets_call(const int64_t* h_starts, int64_t T) const {
+  if (!have_problem_) throw Error("HipEngine: targets before set_problem");
+  check_targets(h_starts, T, cfg_.L1);
+}
+
+void HipEngine::solve_targets_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                     int64_t n, const int64_t* d_starts, const int64_t* h_starts, int64_t T,
+                                     Result* d_out, hipStream_t stream) {
+  check_targets_call(h_starts, T);  // before any launch or change of state
+  if (n > 0 && !d_out) throw Error("targets: no rows buffer");
+  const TargetsCall tc{d_starts, h_starts, T, d_out};
+  run_profile(d_codes, d_offsets, h_offsets, n, 0, nullptr, stream, nullptr, 0, nullptr, &tc);  // n <= 0: no launch
+}
+
+void HipEngine::solve_targets(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T,
+                              Result* out) {
+  check_targets_call(starts, T);
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  if (n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  const std::vector<int64_t> rebased =
+      upload_batch(codes, offsets, n, sizeof(Result) * static_cast<size_t>(n) * static_cast<size_t>(T));
+  targets_placed(placed_upload(rebased, n), starts, T, out, wall);
+}
+
+// d_out: rows (n * T Result); starts travel with the plan buffer
+void HipEngine::targets_placed(const Placed& p, const int64_t* starts, int64_t T, Result* out, Stopwatch& wall) {
+  Slot& s = *slots_[0];
+  const size_t obytes = sizeof(Result) * static_cast<size_t>(p.n) * static_cast<size_t>(T);
+  solve_targets_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, static_cast<Result*>(s.d_out),
+                       s_compute_);
+  copy_d2h(out, s.d_out, obytes, s_compute_);
+  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+  host_call_stats(wall, device_kernel_ms(), p, obytes);
+  stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1);
 }
 
 // ---- alignment report -----------------------------------------------------------------------------------
@@ -1643,6 +1713,17 @@ void HipEngine::solve_summary_wire(const WireBatch& b, int64_t* summary_out, int
   const size_t n = static_cast<size_t>(b.n);
   summary_placed(place_wire(b, sizeof(int64_t) * kSummaryCols * n + sizeof(int32_t) * static_cast<size_t>(bins) * n),
                  summary_out, hist_out, bins, lo, width, wall);
+}
+
+void HipEngine::solve_targets_wire(const WireBatch& b, const int64_t* starts, int64_t T, Result* out) {
+  check_targets_call(starts, T);
+  validate_wire(b);
+  if (b.device) throw Error("the *_wire host forms take host batches; a device-resident one goes through decode_wire_device");
+  finish_wire();
+  if (b.n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  targets_placed(place_wire(b, sizeof(Result) * static_cast<size_t>(b.n) * static_cast<size_t>(T)), starts, T, out, wall);
 }
 
 void HipEngine::report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks) {

@@ -135,6 +135,15 @@ def _decl(lib):
                                                     c_int32, c_void_p, c_void_p, c_void_p]),
         "moc_engine_solve_summary_wire": (c_int, [c_void_p, P(WireBatch), c_int32, c_int32, c_int32, c_void_p, c_void_p]),
         "moc_engine_summary_ms": (c_int, [c_void_p, c_void_p]),
+        "moc_cpu_targets": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                    c_int, c_void_p]),
+        "moc_check_targets": (c_int, [c_void_p, c_int64, c_int64]),
+        "moc_targets_geometry": (c_int, [c_void_p]),
+        "moc_engine_solve_targets": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+        "moc_engine_solve_targets_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                                    c_int64, c_void_p, c_void_p]),
+        "moc_engine_solve_targets_wire": (c_int, [c_void_p, P(WireBatch), c_void_p, c_int64, c_void_p]),
+        "moc_engine_targets_ms": (c_int, [c_void_p, c_void_p]),
         "moc_partition": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_double, c_void_p]),
         "moc_device_count": (c_int, []),
         "moc_host_register": (c_int, [c_void_p, c_size_t]),

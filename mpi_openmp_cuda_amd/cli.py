@@ -16,7 +16,7 @@ from .models.problem import Problem
 from .models.scoring import Semantics
 from .parallel import dist as D
 from .parallel.search import DistributedSearch
-from .utils.io import format_hits, format_report, format_summary, format_topk, write_results
+from .utils.io import format_hits, format_report, format_summary, format_targets, format_topk, write_results
 
 
 def main(argv=None) -> int:
@@ -65,6 +65,14 @@ def main(argv=None) -> int:
                     help="with --summary: one more line '  hist: c0 c1 ...', the counts of the record's scores in BINS "
                          "(1..256) bins of WIDTH (>= 1) from LO up; scores outside land in the first and last bin (a "
                          "negative LO takes the = form, --hist=-50:10:16)")
+    ap.add_argument("--targets", default=None, metavar="FILE",
+                    help="multi-target search: FILE holds one more target sequence per line (letters, as Seq1). The "
+                         "target set is the input's own Seq1 as target 1, then the file's lines; under every "
+                         "result line print one line per target, '  target t: score: S, n: N, k: K' with n relative "
+                         "to that target, or '  target t: none' where the record is longer than the target, and a "
+                         "final '  best: t'. No placement straddles two targets. Not with --top K > 1, "
+                         "--show-alignment, --min-score, --within, --distinct, --summary or --hist; record slices on "
+                         "one node only (--partition records)")
     a = ap.parse_args(argv)
     if not 1 <= a.top <= 64:
         ap.error("--top K: K must be in 1..64")
@@ -94,6 +102,13 @@ def main(argv=None) -> int:
         ap.error("--summary does not combine with --top K > 1, --show-alignment, --min-score or --within")
     if a.min_score is not None and not -2 ** 31 <= a.min_score < 2 ** 31:
         ap.error("--min-score T: T must be an int32")
+    if a.targets is not None:
+        if a.top > 1 or a.show_alignment or want_hits or a.distinct is not None or a.summary or a.hist is not None:
+            ap.error("--targets does not combine with --top K > 1, --show-alignment, --min-score, --within, "
+                     "--distinct, --summary or --hist")
+        if a.partition == "offsets":
+            ap.error("--targets needs record slices (--partition records, one node); --partition offsets combines "
+                     "one packed key per record")
 
     from .ops.align import device_count
 
@@ -101,11 +116,22 @@ def main(argv=None) -> int:
     ctx = D.init(a.dist_backend, use_gpu=use_gpu and a.dist_backend != "gloo")
     rc = 0
     problem = None
+    target_set = None
     err = ""
     if ctx.is_root:
         try:
             data = sys.stdin.buffer.read() if a.input == "-" else open(a.input, "rb").read()
             problem = Problem.parse(data, a.strict_limits)
+            if a.targets is not None:
+                from .ops.align import TargetSet
+
+                with open(a.targets, "r", encoding="ascii") as f:
+                    lines = [ln.strip() for ln in f.read().splitlines()]
+                lines = [ln for ln in lines if ln]
+                if a.strict_limits and any(len(ln) > 3000 for ln in lines):
+                    raise ValueError("--targets: a target sequence is longer than 3000 letters")
+                target_set = TargetSet.from_sequences([problem.seq1] + [TargetSet.from_strings([ln]).seq1 for ln in lines])
+                problem = Problem(problem.weights, target_set.seq1, problem.codes, problem.offsets)
         except Exception as e:  # report, then make every rank exit consistently
             err = str(e)
     import numpy as np
@@ -142,9 +168,25 @@ def main(argv=None) -> int:
                   "packed key per record", file=sys.stderr)
         D.finalize(ctx)
         return 2
+    if a.targets is not None and search.partition != "records":
+        if ctx.is_root:
+            print("--targets needs record slices (--partition records, one node); --partition offsets combines one "
+                  "packed key per record", file=sys.stderr)
+        D.finalize(ctx)
+        return 2
     hit_rows = None
     summary = None
-    if a.summary:
+    target_rows = None
+    if a.targets is not None:
+        try:
+            target_rows = search.run_targets(problem, target_set, Semantics.parse(a.semantics))
+        except ValueError as e:  # an invalid target set (more than 4096 targets): every rank raises it
+            if ctx.is_root:
+                print(f"input error: {e}", file=sys.stderr)
+            D.finalize(ctx)
+            return 1
+        results = None
+    elif a.summary:
         try:
             summary = search.run_summary(problem, *hist_args, semantics=Semantics.parse(a.semantics))
         except ValueError as e:  # the exactness bound: every rank raises it
@@ -176,6 +218,9 @@ def main(argv=None) -> int:
             sys.stdout.flush()
         elif a.summary:
             sys.stdout.write(format_summary(*summary))
+            sys.stdout.flush()
+        elif a.targets is not None:
+            sys.stdout.write(format_targets(target_rows[:, 0], target_rows))
             sys.stdout.flush()
         else:
             write_results(results)

@@ -363,6 +363,151 @@ def summary_thresholds(summary, z):
     return t.to(torch.int64).to(torch.int32).contiguous()
 
 
+# ---- multi-target search: every record's best alignment against each of T targets (csrc/include/moc/cpu_engine.hpp)
+TARGETS_MAX = 4096  # csrc/include/moc/kernel_bounds.hpp kTargetsMax (tests compare it with the native value)
+
+
+def targets_geometry() -> tuple:
+    """(largest T, threads per workgroup of the GPU's targets kernel, longest slice a 4-lane group takes, longest
+    slice a 16-lane group takes) — csrc/include/moc/kernel_bounds.hpp; no GPU needed."""
+    g = np.zeros(4, np.int32)
+    _lib.check(_lib.lib().moc_targets_geometry(_lib.ptr(g)))
+    return tuple(int(x) for x in g)
+
+
+def _targets_check(rc):
+    """A native targets call's status: its target-set errors (messages that start with "targets:") are
+    ValueErrors, anything else a NativeError."""
+    if rc != 0:
+        msg = _lib.lib().moc_last_error().decode(errors="replace")
+        if msg.startswith("targets:"):
+            raise ValueError(msg)
+        raise _lib.NativeError(msg)
+
+
+def check_targets(starts, L1: int) -> np.ndarray:
+    """``starts`` as a contiguous int64 [T + 1] array, checked: 1 <= T <= 4096 and strictly rising from 0 to ``L1``
+    (every target holds at least one letter), else a ValueError whose message starts with ``targets:``."""
+    s = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+    _targets_check(_lib.lib().moc_check_targets(_lib.ptr(s) if s.size else None, int(s.size) - 1, int(L1)))
+    return s
+
+
+class TargetSet:
+    """T target sequences stored as their plain concatenation, the catalog (``seq1``: uint8 codes, no separator
+    letters), with ``starts`` (int64 [T + 1]): target t is ``seq1[starts[t]:starts[t + 1]]``. The catalog is the
+    engines' Seq1: ``Problem(weights, ts.seq1, codes, offsets)`` / ``set_problem(weights, ts.seq1)``."""
+
+    def __init__(self, seq1, starts):
+        self.seq1 = np.ascontiguousarray(seq1, dtype=np.uint8)
+        self.starts = check_targets(starts, self.seq1.shape[0])
+
+    @classmethod
+    def from_sequences(cls, seqs) -> "TargetSet":
+        """From T arrays of letter codes (each at least one letter)."""
+        seqs = [np.ascontiguousarray(s, dtype=np.uint8).reshape(-1) for s in seqs]
+        starts = np.zeros(len(seqs) + 1, np.int64)
+        if seqs:
+            np.cumsum([s.shape[0] for s in seqs], out=starts[1:])
+        return cls(np.concatenate(seqs) if seqs else np.zeros(0, np.uint8), starts)
+
+    @classmethod
+    def from_strings(cls, strings) -> "TargetSet":
+        """From T strings of letters A-Z (case-insensitive, as Seq1)."""
+        from ..models.scoring import encode
+
+        return cls.from_sequences([encode(s) for s in strings])
+
+    @property
+    def T(self) -> int:
+        return int(self.starts.shape[0] - 1)
+
+    @property
+    def lengths(self) -> np.ndarray:
+        return np.diff(self.starts)
+
+    def target(self, t: int) -> np.ndarray:
+        return self.seq1[self.starts[t]:self.starts[t + 1]]
+
+
+def _starts_of(targets, L1: int) -> np.ndarray:
+    """``targets`` (a :class:`TargetSet` or a starts array) -> checked int64 starts over a catalog of L1 letters."""
+    starts = targets.starts if isinstance(targets, TargetSet) else targets
+    if L1 is None:  # an engine without a problem: the native call says so
+        L1 = int(np.asarray(starts).reshape(-1)[-1]) if np.size(starts) else 0
+    return check_targets(starts, L1)
+
+
+def search_targets_cpu(problem: Problem, targets, semantics=Semantics.REFERENCE, threads: int = 0) -> np.ndarray:
+    """Multi-target search on the CPU engine. ``problem.seq1`` is the catalog and ``targets`` its
+    :class:`TargetSet` (or just the starts). Returns int32 [n, T, 3]: row [i, t] = (score, n, k) is exactly
+    search_cpu's row for record i against target t alone, n relative to the target's start; (INT32_MIN, 0, 0) where
+    the record is longer than the target. No placement straddles two targets: a target's rows come from the
+    catalog profile's entries that read inside it, plus its own un-mutated final diagonal summed from the letters.
+    With T = 1 the [n, 1, 3] result equals search_cpu row for row. ValueError for an invalid target set."""
+    starts = _starts_of(targets, problem.L1)
+    T = starts.shape[0] - 1
+    out = np.zeros((problem.n, T, 3), np.int32)
+    _targets_check(_lib.lib().moc_cpu_targets(
+        _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+        _lib.ptr(problem.offsets), problem.n, _lib.ptr(starts), T, int(Semantics.parse(semantics)), int(threads),
+        _lib.ptr(out)))
+    return out
+
+
+def targets_best(rows):
+    """The best target per record of multi-target rows [n, T, 3]: ``(target int32 [n], row int32 [n, 3])`` — the
+    highest score, then the smallest target index; -1 and (INT32_MIN, 0, 0) where no target fits the record.
+    ``rows``: a numpy array, or a torch tensor — then both results are tensors on its device, computed there
+    without a synchronisation."""
+    if isinstance(rows, np.ndarray) or not hasattr(rows, "device"):
+        r = np.asarray(rows, dtype=np.int32)
+        if r.ndim != 3 or r.shape[2] != 3 or r.shape[1] < 1:
+            raise ValueError(f"targets_best needs [n, T, 3] rows, got {r.shape}")
+        t = np.argmax(r[:, :, 0], axis=1)  # the first maximum: the smallest target index
+        row = np.ascontiguousarray(r[np.arange(r.shape[0]), t])
+        none = row[:, 0] == _I32.min
+        row[none] = (_I32.min, 0, 0)
+        return np.where(none, -1, t).astype(np.int32), row
+    import torch
+
+    assert rows.dtype == torch.int32 and rows.dim() == 3 and rows.shape[2] == 3 and rows.shape[1] >= 1
+    score = rows[:, :, 0]
+    mx = score.max(dim=1, keepdim=True).values
+    idx = torch.arange(rows.shape[1], device=rows.device).expand_as(score)
+    t = torch.where(score == mx, idx, torch.full_like(idx, rows.shape[1])).min(dim=1).values  # first maximum
+    row = rows.gather(1, t.view(-1, 1, 1).expand(-1, 1, 3)).squeeze(1)
+    none = mx.squeeze(1) == _I32.min
+    empty = torch.tensor([_I32.min, 0, 0], dtype=torch.int32, device=rows.device)
+    row = torch.where(none.unsqueeze(1), empty.expand_as(row), row).contiguous()
+    return torch.where(none, torch.full_like(t, -1), t).to(torch.int32), row
+
+
+def targets_catalog_rows(rows, targets):
+    """Multi-target rows [n, T, 3] with their offsets moved from the targets to the catalog: n + starts[t]; empty
+    rows (score INT32_MIN) stay untouched. The result is a [n, T, 3] row block the report calls take as it is
+    (``search_report_cpu`` / ``report`` / ``report_device`` work on the catalog; T <= 64 there). ``rows``: a numpy
+    array, or a torch tensor — then the result is a tensor on its device, computed there without a
+    synchronisation (the starts go up with a non-blocking copy)."""
+    starts = np.ascontiguousarray(targets.starts if isinstance(targets, TargetSet) else targets, dtype=np.int64)
+    if isinstance(rows, np.ndarray) or not hasattr(rows, "device"):
+        r = np.array(rows, dtype=np.int32)
+        if r.ndim != 3 or r.shape[2] != 3 or r.shape[1] != starts.shape[0] - 1:
+            raise ValueError(f"targets_catalog_rows needs [n, T, 3] rows for the T = {starts.shape[0] - 1} targets")
+        shift = np.where(r[:, :, 0] == _I32.min, 0, starts[None, :-1])
+        r[:, :, 1] = (r[:, :, 1] + shift).astype(np.int32)
+        return r
+    import torch
+
+    assert rows.dtype == torch.int32 and rows.dim() == 3 and rows.shape[2] == 3
+    assert rows.shape[1] == starts.shape[0] - 1
+    b = torch.from_numpy(starts[:-1].astype(np.int32)).to(rows.device, non_blocking=True)
+    shift = torch.where(rows[:, :, 0] == _I32.min, torch.zeros_like(b).expand(rows.shape[0], -1), b.expand(rows.shape[0], -1))
+    out = rows.clone()
+    out[:, :, 1] += shift
+    return out.contiguous()
+
+
 # ---- alignment report: sign counts and marker bytes of result rows (csrc/include/moc/cpu_engine.hpp)
 REPORT_EMPTY = int(np.iinfo(np.int64).min)        # report_scores of an empty row (score INT32_MIN, top-K padding)
 REPORT_INVALID = int(np.iinfo(np.int64).min) + 1  # ... of a row whose (n, k) does not place the record in Seq1
@@ -950,6 +1095,70 @@ class HipSearchEngine:
         del keep
         return summary, hist
 
+    # ---- multi-target search (byte letters, dense offsets; csrc/src/hip/targets_kernels.hip)
+    def solve_targets(self, codes: np.ndarray, offsets: np.ndarray, targets) -> np.ndarray:
+        """Host CSR -> int32 [n, T, 3] rows as :func:`search_targets_cpu` returns them, against the engine's Seq1
+        as the catalog of ``targets`` (a :class:`TargetSet` or its starts; ``set_problem(weights, ts.seq1)``
+        first). One pass: the chunks of :meth:`solve_hits` with the targets select kernel behind each chunk's
+        catalog profile — 12 T bytes come back per record, never the profile. Synchronous;
+        ``stats()["kernels"]`` names ``targets``. ValueError for an invalid target set, raised before anything is
+        launched and without a change to ``stats()``."""
+        starts = _starts_of(targets, self.problem_L1)
+        T = starts.shape[0] - 1
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        out = np.zeros((n, T, 3), np.int32)
+        _targets_check(_lib.lib().moc_engine_solve_targets(self._h, _lib.ptr(codes), _lib.ptr(offsets), n,
+                                                           _lib.ptr(starts), T, _lib.ptr(out)))
+        return out
+
+    def targets_ms(self) -> float:
+        """Device time (ms) of the targets select launches of the last targets call; 0 unless the engine was
+        created with MOC_PROFILE_TIMING=1 in the environment. Waits for them."""
+        ms = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().moc_engine_targets_ms(self._h, ctypes.addressof(ms)))
+        return float(ms.value)
+
+    def solve_targets_device(self, codes_t, offsets_t, h_offsets: np.ndarray, targets, out_t=None, starts_t=None,
+                             stream=None):
+        """Device-resident batch (as :meth:`solve_device`) -> ``out_t``, an int32 [n, T, 3] tensor of multi-target
+        rows on the codes' device (allocated when None; every row is written). ``starts_t``: an int64 [T + 1]
+        device copy of the starts, or None — then the engine uploads them with its plan. Queued on ``stream``
+        (default: the current stream); returns immediately — :func:`targets_catalog_rows` and
+        :meth:`report_device` can follow on the same stream. ValueError as :meth:`solve_targets`."""
+        import torch
+
+        starts = _starts_of(targets, self.problem_L1)
+        T = starts.shape[0] - 1
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        n = h_offsets.shape[0] - 1
+        assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        if out_t is None:
+            out_t = torch.empty((n, T, 3), dtype=torch.int32, device=codes_t.device)
+        assert out_t.dtype == torch.int32 and out_t.is_contiguous() and tuple(out_t.shape) == (n, T, 3)
+        if starts_t is not None:
+            assert starts_t.dtype == torch.int64 and starts_t.is_contiguous() and starts_t.numel() == T + 1
+        _targets_check(_lib.lib().moc_engine_solve_targets_device(
+            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
+            n, ctypes.c_void_p(starts_t.data_ptr()) if starts_t is not None else None, _lib.ptr(starts), T,
+            ctypes.c_void_p(out_t.data_ptr()), ctypes.c_void_p(stream.cuda_stream)))
+        return out_t
+
+    def solve_targets_wire(self, ws, targets, shift: int = 0) -> np.ndarray:
+        """Host wire batch -> int32 [n, T, 3] multi-target rows, as :meth:`solve_targets` on the decoded records.
+        See :meth:`solve_profile_wire`."""
+        starts = _starts_of(targets, self.problem_L1)
+        T = starts.shape[0] - 1
+        b, keep = wire_batch_of(ws, shift)
+        out = np.zeros((ws.n, T, 3), np.int32)
+        _targets_check(_lib.lib().moc_engine_solve_targets_wire(self._h, ctypes.byref(b), _lib.ptr(starts), T,
+                                                                _lib.ptr(out)))
+        del keep
+        return out
+
     # ---- alignment report (byte letters, dense offsets; csrc/src/hip/report_kernels.hip)
     def report(self,codes: np.ndarray, offsets: np.ndarray, rows, marks: bool = False):
         """Host CSR + result rows ([n, 3] or [n, K, 3]) -> the counts (and marker bytes) :func:`search_report_cpu`
@@ -1178,7 +1387,7 @@ class HipSearchEngine:
         d["format"] = _lib.FORMAT_NAMES[int(d["format"])]
         d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16"), (16, "profile"),
                                              (32, "report"), (64, "hits"), (128, "wire"), (256, "peaks"),
-                                             (512, "summary"))
+                                             (512, "summary"), (1024, "targets"))
                         if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
@@ -1265,6 +1474,12 @@ def align_summary_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets,
     (columns :data:`SUMMARY_COLS`) and an int32 [n, bins] tensor, or None with ``bins = 0``; see
     :meth:`HipSearchEngine.solve_summary_device`."""
     return engine.solve_summary_device(codes_t, offsets_t, h_offsets, bins, lo, width, None, None, stream)
+
+
+def align_targets_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, targets, stream=None):
+    """torch-facing op: the multi-target rows as an int32 [n, T, 3] tensor on the codes' device; see
+    :meth:`HipSearchEngine.solve_targets_device`."""
+    return engine.solve_targets_device(codes_t, offsets_t, h_offsets, targets, None, None, stream)
 
 
 def align_report_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, rows_t, marks: bool = False,

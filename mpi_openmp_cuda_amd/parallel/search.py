@@ -29,7 +29,8 @@ from ..models.problem import Problem
 from ..models.scoring import Semantics
 from ..ops.align import (HipSearchEngine, decode_keys, device_count, keys_to_ordered_int64, ordered_int64_to_keys,
                         profile_offsets, search_cpu, search_hits_cpu, search_keys_cpu, search_report_cpu,
-                        search_summary_cpu, search_topk_cpu, summary_bound, within_thresholds, _summary_args)
+                        search_summary_cpu, search_targets_cpu, search_topk_cpu, summary_bound, within_thresholds,
+                         TargetSet, check_targets, _summary_args)
 from ..utils.timer import PhaseTimer
 from . import dist as D
 from .partition import CPU_COST, GPU_COST, partition
@@ -294,6 +295,48 @@ class DistributedSearch:
             D.barrier(ctx)
             win.close(unlink=ctx.is_root)
         return (summary, hist.astype(np.int32) if bins else None) if ctx.is_root else None
+
+    def run_targets(self, problem: Optional[Problem], targets=None, semantics=Semantics.REFERENCE):
+        """Multi-target search (ops.align.search_targets_cpu's int32 [n, T, 3] rows; ``problem.seq1`` is the catalog
+        of ``targets``, a TargetSet or its starts, both needed on the root only) for the ``records`` partition: the
+        root broadcasts the starts, every rank searches its cost-balanced slice of the node-shared input window
+        against every target, and one MAX all-reduce of an int64 array that a rank fills only in its own slice
+        collects the rows (no new transport). Returns the rows on the root, else None. An invalid target set raises
+        the same ValueError on every rank. One node; byte letters through the engines' targets calls."""
+        if self.partition != "records":
+            raise ValueError("the multi-target search runs on record slices (--partition records, one node): the "
+                             "offsets partition combines one packed key per record and cannot carry T rows")
+        ctx, T = self.ctx, self.timer
+        sem = Semantics.parse(semantics)
+        hdr = None
+        if ctx.is_root:
+            starts = np.ascontiguousarray(targets.starts if isinstance(targets, TargetSet) else targets,
+                                          dtype=np.int64).reshape(-1)
+            hdr = np.array([starts.shape[0], problem.L1], np.int64)
+        hdr = D.bcast_array(ctx, hdr, 2, np.int64)
+        starts = D.bcast_array(ctx, starts if ctx.is_root else None, int(hdr[0]), np.int64)
+        starts = check_targets(starts, int(hdr[1]))  # every rank raises alike
+        nt = starts.shape[0] - 1
+        with T.phase("bcast"):
+            prob, sem, n, total, bounds = self._setup(problem, sem)
+        b, e = int(bounds[ctx.rank]), int(bounds[ctx.rank + 1])
+        with T.phase("distribute"):
+            win = self._open_window(problem, n, total)
+        with T.phase("compute"):
+            rows = np.full((n, nt, 3), np.iinfo(np.int64).min, np.int64)
+            if e > b:
+                offsets = np.asarray(win.offsets[b:e + 1])
+                if self.engine is not None:
+                    rows[b:e] = self.engine.solve_targets(np.asarray(win.codes), offsets, starts)
+                else:
+                    sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
+                                  offsets - offsets[0])
+                    rows[b:e] = search_targets_cpu(sub, starts, sem, self.threads)
+        with T.phase("gather"):
+            rows = D.allreduce_max_int64(ctx, rows.reshape(-1)).reshape(n, nt, 3)
+            D.barrier(ctx)
+            win.close(unlink=ctx.is_root)
+        return rows.astype(np.int32) if ctx.is_root else None
 
     def report(self, problem: Problem, rows: np.ndarray):
         """Root only: ``(counts, marks)`` of the search's rows (ops.align.search_report_cpu's outputs, with the

@@ -119,7 +119,8 @@ class WireSlice:
             kept[shift][:] = s
         return kept[shift]
 
-    # ---- profile, top-K, hits, report and summary of the slice on a HipSearchEngine: decoded on the GPU from these arrays
+    # ---- profile, top-K, hits, report, summary and multi-target rows of the slice on a HipSearchEngine: decoded on the
+    # GPU from these arrays
     def solve_profile_wire(self, engine, shift: int = 0):
         return engine.solve_profile_wire(self, shift)
 
@@ -135,6 +136,9 @@ class WireSlice:
 
     def solve_summary_wire(self, engine, bins: int = 0, lo: int = 0, width: int = 1, shift: int = 0):
         return engine.solve_summary_wire(self, bins, lo, width, shift)
+
+    def solve_targets_wire(self, engine, targets, shift: int = 0):
+        return engine.solve_targets_wire(self, targets, shift)
 
     def decode_cpu(self, shift: int = 0):
         """``(codes, offsets)`` of the slice from the native host decode (ops.align.decode_wire_cpu)."""

@@ -102,6 +102,29 @@ def format_summary(summary, hist=None, first_index: int = 0) -> str:
     return "".join(out)
 
 
+def format_targets(results, rows, first_index: int = 0) -> str:
+    """Results with their multi-target rows (int32 [n, T, 3] from the targets calls): record i's line as
+    :func:`format_results` prints it, then one line per target, numbered from 1 — "  target t: score: S, n: N, k: K"
+    with n relative to that target's start, or "  target t: none" where the record is longer than the target — and
+    a final "  best: t" (ops.align.targets_best: the highest score, then the first target; "  best: none" when no
+    target fits)."""
+    from ..ops.align import as_triples, targets_best
+
+    r = np.asarray(rows, dtype=np.int32)
+    res = as_triples(results)
+    if r.ndim != 3 or r.shape[2] != 3 or r.shape[0] != res.shape[0]:
+        raise ValueError("format_targets needs [n, T, 3] rows for the results' n records")
+    best, _ = targets_best(r)
+    none = np.iinfo(np.int32).min
+    out = []
+    for i, (score, n, k) in enumerate(res.tolist()):
+        out.append(f"#{i + first_index}: score: {score}, n: {n}, k: {k}\n")
+        for t, (ts, tn, tk) in enumerate(r[i].tolist()):
+            out.append(f"  target {t + 1}: none\n" if ts == none else f"  target {t + 1}: score: {ts}, n: {tn}, k: {tk}\n")
+        out.append(f"  best: {int(best[i]) + 1}\n" if best[i] >= 0 else "  best: none\n")
+    return "".join(out)
+
+
 def format_report(problem, rows, counts, marks, first_index: int = 0) -> str:
     """Results with their alignments. ``rows`` [n, 3] print as :func:`format_results` does and [n, K, 3] as
     :func:`format_topk` does; after the line of every real row — not an empty one (score INT32_MIN), nor one
