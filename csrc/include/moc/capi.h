@@ -326,6 +326,31 @@ int moc_engine_solve_targets_device(void* e, const uint8_t* d_codes, const int64
 int moc_engine_solve_targets_wire(void* e, const moc_wire_batch* b, const int64_t* starts, int64_t T, moc_result* rows);
 /* device time (ms) of the last targets call's select launches (MOC_PROFILE_TIMING=1; else 0) */
 int moc_engine_targets_ms(void* e, double* ms);
+/* ---- per-target profile summary (moc/cpu_engine.hpp targets_summary_batch_cpu) ----
+ * Seq1 is a catalog delimited by starts as above. summary: int64 [n * T * 7], record-major: row (i * T + t) holds
+ * (count, sum, sumsq, min, max, n, k) of record i's profile against target t alone, n relative to the target's start;
+ * (0, 0, 0, INT32_MAX, INT32_MIN, 0, 0) where the record is longer than the target. hist: int32 [n * T * bins], the
+ * bins, lo and width of moc_cpu_summary (bins = 0: none, hist may be NULL and is not touched). Errors, all reported
+ * before any work: the target set's ("targets:"), then bins, width and the exactness bound over the largest target
+ * profile of the call ("summary:"). The engine forms are as moc_engine_solve_targets*. */
+int moc_cpu_targets_summary(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                            const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics,
+                            int threads, int32_t bins, int32_t lo, int32_t width, int64_t* summary, int32_t* hist);
+/* out4: threads per workgroup of the GPU's per-target summary kernels, the largest bins, the most bins a 4-lane group
+ * takes in the histogram kernel (above it a 4-lane choice becomes 16 lanes), and the LDS bytes a workgroup's
+ * counters stay within (moc/kernel_bounds.hpp); no GPU needed */
+int moc_targets_summary_geometry(int32_t* out4);
+int moc_engine_solve_targets_summary(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n,
+                                     const int64_t* starts, int64_t T, int32_t bins, int32_t lo, int32_t width,
+                                     int64_t* summary, int32_t* hist);
+int moc_engine_solve_targets_summary_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                            const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
+                                            const int64_t* h_starts, int64_t T, int32_t bins, int32_t lo, int32_t width,
+                                            int64_t* d_summary, int32_t* d_hist, void* stream);
+int moc_engine_solve_targets_summary_wire(void* e, const moc_wire_batch* b, const int64_t* starts, int64_t T,
+                                          int32_t bins, int32_t lo, int32_t width, int64_t* summary, int32_t* hist);
+/* device time (ms) of the last per-target summary call's summary + histogram launches (MOC_PROFILE_TIMING=1; else 0) */
+int moc_engine_targets_summary_ms(void* e, double* ms);
 /* stats: kernel_ms, total_ms, h2d_bytes, d2h_bytes, chunks, cells, records, direct, format, kernels,
  * r2 smin, r2 kw, r2 j, forms (moc::bounds::FormBits of the last solve) */
 int moc_engine_stats(void* e, double* out14);

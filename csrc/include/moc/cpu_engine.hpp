@@ -155,6 +155,25 @@ void check_targets(const int64_t* starts, int64_t T, int64_t L1);
 void targets_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
                        const int64_t* starts, int64_t T, Result* out, Semantics sem, int num_threads = 0);
 
+// ---- per-target profile summary: the summary row and histogram of every (record, target) pair's target profile
+// Terms as above (catalog, starts, b = starts[t], len = len_t, P the catalog's profile of record i, L2 letters).
+// The pair (i, t) fits iff 1 <= L2 <= len. Its target profile holds the slice entries P[b + o], o in [0, len - L2),
+// and the boundary entry (sum_l LUT[s2[l]][s1[b + len - L2 + l]], k = 0) at local offset len - L2 iff sem == Spec
+// or len == L2 — exactly when it takes part in targets_batch_cpu, summed from the letters and never read from P. By
+// the slice identity this is profile_record's profile of the record against target t alone.
+// summary[(i * T + t) * 7 ..): (count, sum, sumsq, min, max, n, k) over those entries as summary_batch_cpu defines
+// them, n local to the target: (max, n, k) is targets_batch_cpu's row [i, t]. A pair that does not fit gives
+// (0, 0, 0, INT32_MAX, INT32_MIN, 0, 0). hist[(i * T + t) * bins ..) (bins > 0): summary_bin of every entry; the row
+// sums to count; zeros where the pair does not fit. bins == 0: hist may be null and is not touched.
+// Errors before any work: check_targets' ("targets: ..."), then check_summary_args' ("summary: ...") with M from the
+// call's longest record and the largest count of any pair, targets_max_count — reached at the longest target with
+// the shortest record that fits it. A catalog whose own profile summary_batch_cpu would refuse is accepted as long
+// as every target's profile is within the bound.
+int64_t targets_max_count(const int64_t* starts, int64_t T, const int64_t* offsets, int64_t n, Semantics sem);
+void targets_summary_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                               const int64_t* starts, int64_t T, int64_t* summary, int32_t* hist, int32_t bins,
+                               int32_t lo, int32_t width, Semantics sem, int num_threads = 0);
+
 // ---- alignment report: the signs under a result row's letter pairs
 // A row is a Result {score, n, k} of record i (L2 letters) against Seq1; rows[i*K .. i*K+K) belong to record i.
 //   empty row   (score == kNoCandidateScore, e.g. top-K padding): counts {0,0,0,0}, marker bytes 0, nothing read

@@ -436,6 +436,22 @@ struct TargetsArgs {
 // supplies the LUT, Seq1 (padded), L1 and the semantics, bv the records' letters.
 void launch_targets(const TargetsArgs& ta, const ProblemView& pv, const BatchView& bv, hipStream_t stream);
 
+// ---- per-target profile summary (targets_summary_kernels.hip; definitions: moc/cpu_engine.hpp
+// targets_summary_batch_cpu)
+// The chunk, pairs and lane groups of TargetsArgs (`ta`; ta.out is not used). Pair (r, t) stores its seven values at
+// summary[(r * T + t) * 7 ..) and, with bins > 0, its histogram row at hist[(r * T + t) * bins ..) (batch-wide record
+// index; every value of both is stored, nothing is accumulated into).
+struct TargetsSummaryArgs {
+  TargetsArgs ta;
+  int64_t* summary = nullptr;  // device int64 [n_total * T * 7]
+  int32_t* hist = nullptr;     // device int32 [n_total * T * bins], or null with bins == 0
+  int32_t bins = 0, lo = 0, width = 1;
+};
+// Queues the summary kernel with ta.group lanes per pair and, when bins > 0, the histogram kernel with
+// bounds::targets_hist_group(ta.group, bins) lanes per pair on `stream` (more than one launch each when the blocks
+// would pass the grid limit).
+void launch_targets_summary(const TargetsSummaryArgs& sa, const ProblemView& pv, const BatchView& bv, hipStream_t stream);
+
 // Loads every kernel file's code object onto the current device now (HIP loads them lazily, at the first
 // launch from each file: milliseconds inside the first timed search of a job otherwise).
 void preload_align_kernels();
@@ -451,6 +467,7 @@ void preload_wire_kernels();
 void preload_peaks_kernels();
 void preload_summary_kernels();
 void preload_targets_kernels();
+void preload_targets_summary_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -467,6 +484,7 @@ enum PreloadSet : unsigned {
   kPreloadPeaks = 1024,  // peaks_kernels.hip: likewise
   kPreloadSummary = 2048,  // summary_kernels.hip: likewise
   kPreloadTargets = 4096,  // targets_kernels.hip: likewise
+  kPreloadTargetsSummary = 8192,  // targets_summary_kernels.hip: likewise
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -482,9 +500,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadPeaks) preload_peaks_kernels();
   if (set & kPreloadSummary) preload_summary_kernels();
   if (set & kPreloadTargets) preload_targets_kernels();
+  if (set & kPreloadTargetsSummary) preload_targets_summary_kernels();
 }
 // "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
-// profile, report, hits, wire, peaks, summary, targets;
+// profile, report, hits, wire, peaks, summary, targets, targets_summary;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

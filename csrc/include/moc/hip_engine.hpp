@@ -64,7 +64,8 @@ struct EngineStats {
                          // 64 hits (count / scan / compact, next to 16), 128 wire (decode kernels of a *_wire call),
                          // 256 peaks (the peak filter and masked select / hits kernels of a distinct call),
                          // 512 summary (the summary / histogram kernels, next to 16),
-                         // 1024 targets (the multi-target select kernel, next to 16)
+                         // 1024 targets (the multi-target select kernel, next to 16),
+                         // 2048 targets_summary (the per-target summary / histogram kernels, next to 16)
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -218,6 +219,27 @@ class HipEngine {
   // Device time (ms) of the targets select launches of the last targets call; as topk_select_ms().
   double targets_ms() { return topk_select_ms(); }
 
+  // ---- per-target profile summary (definitions: moc/cpu_engine.hpp targets_summary_batch_cpu; kernels:
+  // csrc/src/hip/targets_summary_kernels.hip): the engine's Seq1 is a catalog as for solve_targets, and every
+  // (record, target) pair gets the summary row (count, sum, sumsq, min, max, n, k) of its target profile as seven
+  // int64 — summary [n * T * 7], record-major — and, with bins > 0, an int32 [bins] histogram of its scores, hist
+  // [n * T * bins]. Limits as solve_targets. Before anything is launched or any state changes, the target set is
+  // checked ("targets:" errors), then bins, width and the exactness bound over the largest target profile of the
+  // call (targets_max_count; "summary:" errors) — the catalog's own profile may be past the bound.
+  // Device form: queued on `stream` (0 = engine compute stream) with no sync, in the chunks of solve_targets — per
+  // chunk the profile kernel over the catalog, then the per-target summary kernel and, with bins > 0, the histogram
+  // kernel over the chunk's pairs, the lane group chosen as solve_targets chooses it. d_starts / h_starts as
+  // solve_targets_device. d_hist is never touched with bins == 0. An empty batch launches nothing.
+  void solve_targets_summary_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                    int64_t n, const int64_t* d_starts, const int64_t* h_starts, int64_t T,
+                                    int64_t* d_summary, int32_t* d_hist, int32_t bins, int32_t lo, int32_t width,
+                                    hipStream_t stream);
+  // Host form (uploads through the pooled buffers; synchronous; fills stats()). hist_out may be null with bins == 0.
+  void solve_targets_summary(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T,
+                             int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo, int32_t width);
+  // Device time (ms) of the per-target summary (and histogram) launches of the last such call; as topk_select_ms().
+  double targets_summary_ms() { return topk_select_ms(); }
+
   // ---- alignment report (definitions: moc/cpu_engine.hpp report_batch_cpu; kernels:
   // csrc/src/hip/report_kernels.hip): the sign counts and, optionally, the marker bytes of caller-supplied rows.
   // Byte letters and dense int64 offsets (wire batches: report_wire); no Semantics (row validity does not depend on
@@ -265,6 +287,8 @@ class HipEngine {
   void solve_summary_wire(const WireBatch& b, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo,
                           int32_t width);
   void solve_targets_wire(const WireBatch& b, const int64_t* starts, int64_t T, Result* out);
+  void solve_targets_summary_wire(const WireBatch& b, const int64_t* starts, int64_t T, int64_t* summary_out,
+                                  int32_t* hist_out, int32_t bins, int32_t lo, int32_t width);
   // poffsets[0..n] of a host wire batch (profile_offsets of its decoded lengths; no GPU work)
   void wire_profile_offsets(const WireBatch& b, int64_t* poffsets) const;
 
@@ -382,12 +406,19 @@ class HipEngine {
     const int64_t* h_starts;
     int64_t T;
     Result* d_out;
+    const SummaryCall* summary = nullptr;  // ... and when it is for the per-target summary (d_out unused)
   };
   void run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n, int K,
                    void* d_dst, hipStream_t stream, const HitsCall* hits = nullptr, int64_t radius = 0,
                    const SummaryCall* summary = nullptr, const TargetsCall* targets = nullptr);
   void check_targets_call(const int64_t* h_starts, int64_t T) const;  // throws unless T and starts are valid; touches nothing
   void targets_placed(const Placed& p, const int64_t* starts, int64_t T, Result* out, Stopwatch& wall);
+  // throws unless the target set, bins, width and the exactness bound of the call's largest target profile allow
+  // the call; touches nothing
+  void check_targets_summary(const int64_t* h_offsets, int64_t n, const int64_t* h_starts, int64_t T, int32_t bins,
+                             int32_t width) const;
+  void targets_summary_placed(const Placed& p, const int64_t* starts, int64_t T, int64_t* summary_out,
+                              int32_t* hist_out, int32_t bins, int32_t lo, int32_t width, Stopwatch& wall);
   // throws unless bins, width and the batch's exactness bound (bounds::summary_exact) allow the call; touches nothing
   void check_summary(const int64_t* h_offsets, int64_t n, int32_t bins, int32_t width) const;
   void summary_placed(const Placed& p, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo, int32_t width,

@@ -163,6 +163,28 @@ inline int targets_group(int64_t max_slice) {
   return max_slice <= kTargetsGroup4MaxSlice ? 4 : max_slice <= kTargetsGroup16MaxSlice ? 16 : 64;
 }
 
+// ---- per-target profile summary (targets_summary_kernels.hip; definitions: moc/cpu_engine.hpp
+// targets_summary_batch_cpu): the lane groups and cut-overs of the multi-target search (targets_group above), one
+// summary row per (record, target) pair. The histogram kernel keeps one int32 LDS counter per bin and group; a
+// workgroup's counters stay within kTargetsHistLdsBytes = 16 KiB, so that the eight 256-thread workgroups that fill a
+// CU's 32 wave slots need 128 of its 160 KiB and LDS never limits occupancy. With G lanes per group a workgroup
+// holds kTargetsThreads / G groups: 64 groups of 4 lanes fit up to kTargetsHistGroup4MaxBins = 64 bins each, 16
+// groups of 16 lanes (and 4 waves) the full kSummaryMaxBins. targets_hist_group widens a 4-lane choice to 16 lanes
+// past 64 bins and leaves every other choice alone; every group size gives the same rows.
+constexpr int32_t kTargetsHistLdsBytes = 16 * 1024;
+constexpr int32_t kTargetsHistGroup4MaxBins = kTargetsHistLdsBytes / 4 / (kTargetsThreads / 4);
+static_assert(kTargetsHistGroup4MaxBins == 64, "targets summary: 64 four-lane groups of 64 bins fill 16 KiB");
+static_assert((kTargetsThreads / 16) * kSummaryMaxBins * 4 <= kTargetsHistLdsBytes, "targets summary: 16-lane groups fit");
+inline int targets_hist_group(int group, int32_t bins) {
+  return group == 4 && bins > kTargetsHistGroup4MaxBins ? 16 : group;
+}
+// Entries of the target profile of a record of L2 letters against a target of `len` letters (0: it does not fit):
+// the slice's len - L2 entries plus the boundary entry under the spec semantics or with len == L2.
+inline int64_t targets_pair_count(int64_t len, int64_t L2, bool spec) {
+  if (L2 < 1 || L2 > len) return 0;
+  return len - L2 + (spec || len == L2 ? 1 : 0);
+}
+
 // Form bits reported per solve (EngineStats::forms; Python: stats()["forms"]).
 enum FormBits : int32_t {
   kFormSwipeKBits = 1,    // swipe, int16 keys with k bits

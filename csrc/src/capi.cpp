@@ -870,6 +870,59 @@ int moc_engine_targets_ms(void* e, double* ms) {
   return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->targets_ms(); });
 }
 
+// ---- per-target profile summary
+int moc_targets_summary_geometry(int32_t* out4) {
+  out4[0] = moc::bounds::kTargetsThreads;
+  out4[1] = moc::bounds::kSummaryMaxBins;
+  out4[2] = moc::bounds::kTargetsHistGroup4MaxBins;
+  out4[3] = moc::bounds::kTargetsHistLdsBytes;
+  return 0;
+}
+
+int moc_cpu_targets_summary(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                            const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics,
+                            int threads, int32_t bins, int32_t lo, int32_t width, int64_t* summary, int32_t* hist) {
+  return guard([&] {
+    moc::check_targets(starts, T, L1);
+    moc::Weights w = weights_of(weights4);
+    moc::RecordBatch b = view_batch(codes, offsets, n);
+    moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
+    moc::ScoreTable t = moc::ScoreTable::build(w);
+    moc::targets_summary_batch_cpu(t, seq1, L1, b, starts, T, summary, hist, bins, lo, width,
+                                   static_cast<moc::Semantics>(semantics), threads);
+  });
+}
+
+int moc_engine_solve_targets_summary(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n,
+                                     const int64_t* starts, int64_t T, int32_t bins, int32_t lo, int32_t width,
+                                     int64_t* summary, int32_t* hist) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_targets_summary(codes, offsets, n, starts, T, summary, hist, bins, lo, width);
+  });
+}
+
+int moc_engine_solve_targets_summary_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                            const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
+                                            const int64_t* h_starts, int64_t T, int32_t bins, int32_t lo, int32_t width,
+                                            int64_t* d_summary, int32_t* d_hist, void* stream) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_targets_summary_device(d_codes, d_offsets, h_offsets, n, d_starts, h_starts, T,
+                                                                  d_summary, d_hist, bins, lo, width,
+                                                                  static_cast<hipStream_t>(stream));
+  });
+}
+
+int moc_engine_solve_targets_summary_wire(void* e, const moc_wire_batch* w, const int64_t* starts, int64_t T,
+                                          int32_t bins, int32_t lo, int32_t width, int64_t* summary, int32_t* hist) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_targets_summary_wire(wire_batch(w), starts, T, summary, hist, bins, lo, width);
+  });
+}
+
+int moc_engine_targets_summary_ms(void* e, double* ms) {
+  return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->targets_summary_ms(); });
+}
+
 int moc_engine_stats(void* e, double* out14) {
   return guard([&] {
     double* out13 = out14;

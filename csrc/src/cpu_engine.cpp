@@ -425,6 +425,70 @@ void targets_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const
   });
 }
 
+int64_t targets_max_count(const int64_t* starts, int64_t T, const int64_t* offsets, int64_t n, Semantics sem) {
+  int64_t max_len = 0;
+  for (int64_t q = 0; q < T; ++q) max_len = std::max(max_len, starts[q + 1] - starts[q]);
+  int64_t min_l2 = INT64_MAX;  // the shortest record that fits the longest target (and so any target at all)
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t L2 = offsets[i + 1] - offsets[i];
+    if (L2 >= 1 && L2 <= max_len) min_l2 = std::min(min_l2, L2);
+  }
+  return min_l2 == INT64_MAX ? 0 : bounds::targets_pair_count(max_len, min_l2, sem == Semantics::Spec);
+}
+
+void targets_summary_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                               const int64_t* starts, int64_t T, int64_t* summary, int32_t* hist, int32_t bins,
+                               int32_t lo, int32_t width, Semantics sem, int num_threads) {
+  check_targets(starts, T, L1);
+  const int64_t n = batch.size();
+  check_summary_args(t.max_abs(), n ? batch.max_length() : 0, targets_max_count(starts, T, batch.offsets.data(), n, sem),
+                     bins, width);
+  if (bins > 0 && !hist) throw Error("summary: bins > 0 need a hist buffer");
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
+    const int64_t L2 = batch.length(i);
+    const uint8_t* s2 = batch.record(i);
+    for (int64_t q = 0; q < T; ++q) {
+      const int64_t b = starts[q], len = starts[q + 1] - b;
+      int64_t* row = summary + (i * T + q) * kSummaryCols;
+      int32_t* h = bins > 0 ? hist + (i * T + q) * bins : nullptr;
+      if (h) std::fill(h, h + bins, 0);
+      int64_t count = 0, sum = 0, sumsq = 0, best = 0;
+      int32_t mn = INT32_MAX, mx = INT32_MIN, bk = 0;
+      auto take = [&](int32_t score, int64_t o, int32_t k) {
+        const int64_t s = score;
+        ++count;
+        sum += s;
+        sumsq += s * s;
+        mn = std::min(mn, score);
+        if (score > mx) {  // strict: the smallest offset keeps a tie
+          mx = score;
+          best = o;
+          bk = k;
+        }
+        if (h) ++h[summary_bin(score, lo, width, bins)];
+      };
+      if (L2 >= 1 && L2 <= len) {
+        const int64_t slice = len - L2;  // b + slice <= L1 - L2 <= C
+        for (int64_t o = 0; o < slice; ++o) take(prof[b + o].score, o, prof[b + o].k);
+        if (sem == Semantics::Spec || slice == 0) {  // the boundary entry, from the letters
+          const uint8_t* a = s1 + b + slice;
+          int32_t s = 0;
+          for (int64_t l = 0; l < L2; ++l) s += t.lut[s2[l] * kLutStride + a[l]];
+          take(s, slice, 0);
+        }
+      }
+      row[0] = count;
+      row[1] = sum;
+      row[2] = sumsq;
+      row[3] = mn;
+      row[4] = mx;
+      row[5] = best;
+      row[6] = bk;
+    }
+    (void)C;
+  });
+}
+
 void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
                     Semantics sem, int num_threads, int64_t radius) {
   if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));

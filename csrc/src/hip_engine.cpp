@@ -112,7 +112,7 @@ int parse_preload_set(const char* s) {
                {"swipe33", kPreloadSwipeP33}, {"tile16", kPreloadTile16}, {"mfma", kPreloadMfma},
                {"profile", kPreloadProfile}, {"report", kPreloadReport}, {"hits", kPreloadHits},
                {"wire", kPreloadWire}, {"peaks", kPreloadPeaks}, {"summary", kPreloadSummary},
-               {"targets", kPreloadTargets}};
+               {"targets", kPreloadTargets}, {"targets_summary", kPreloadTargetsSummary}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -1010,7 +1010,8 @@ double HipEngine::topk_select_ms() {
 // [n, K]), chunk by chunk through the bounded scratch. hits (with K == 0, d_dst unused): the same chunks, each
 // followed by count, prefix sum and compaction into the call's buffers. summary (likewise, without hits or a
 // radius): the same chunks, each followed by the summary and histogram kernels. targets (likewise): the same chunks,
-// each followed by the targets select kernel over the chunk's (record, target) pairs. Plan buffer: poffsets (n + 1)
+// each followed by the targets select kernel over the chunk's (record, target) pairs — or, with targets->summary, by
+// the per-target summary and histogram kernels over the same pairs. Plan buffer: poffsets (n + 1)
 // | every chunk's wave starts | the targets call's starts (T + 1; when the caller gave no device copy).
 void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
                             int K, void* d_dst, hipStream_t stream, const HitsCall* hits, int64_t radius,
@@ -1024,7 +1025,8 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   if (n <= 0) return;
   if (n >= (int64_t{1} << 31) - 1) throw Error("profile / top-K: more than 2^31 - 2 records in one call");
   if (!stream) stream = s_compute_;
-  TraceRange tr(targets   ? "moc.solve_targets_device"
+  TraceRange tr(targets && targets->summary ? "moc.solve_targets_summary_device"
+                : targets ? "moc.solve_targets_device"
                 : summary ? "moc.solve_summary_device"
                 : hits  ? "moc.solve_hits_device"
                 : K     ? "moc.solve_topk_device"
@@ -1157,7 +1159,18 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
         for (int64_t r = c.r0; r < c.r1; ++r) min_l2 = std::min(min_l2, h_offsets[r + 1] - h_offsets[r]);
         ta.group = targets_group_ ? targets_group_ : bounds::targets_group(std::max<int64_t>(max_target - min_l2, 0));
         ta.out = targets->d_out;
-        dev::launch_targets(ta, pv, bv, stream);
+        if (const SummaryCall* ts = targets->summary) {
+          dev::TargetsSummaryArgs tsa;
+          tsa.ta = ta;
+          tsa.summary = ts->d_summary;
+          tsa.hist = ts->d_hist;
+          tsa.bins = ts->d_hist ? ts->bins : 0;
+          tsa.lo = ts->lo;
+          tsa.width = ts->width;
+          dev::launch_targets_summary(tsa, pv, bv, stream);
+        } else {
+          dev::launch_targets(ta, pv, bv, stream);
+        }
       } else if (summary) {
         dev::SummaryArgs sa;
         sa.prof = pa.prof;
@@ -1206,7 +1219,8 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   stats_.cells = cells;
   stats_.records = n;
   stats_.chunks = static_cast<int64_t>(chunks.size());
-  stats_.kernels = (hits ? 16 | 64 : 16) | (peaks ? 256 : 0) | (summary ? 512 : 0) | (targets ? 1024 : 0);
+  stats_.kernels = (hits ? 16 | 64 : 16) | (peaks ? 256 : 0) | (summary ? 512 : 0) |
+                   (targets ? (targets->summary ? 2048 : 1024) : 0);
 }
 
 void HipEngine::solve_profile_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
@@ -1426,6 +1440,59 @@ void HipEngine::targets_placed(const Placed& p, const int64_t* starts, int64_t T
   copy_d2h(out, s.d_out, obytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
   host_call_stats(wall, device_kernel_ms(), p, obytes);
+  stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1);
+}
+
+// ---- per-target profile summary -------------------------------------------------------------------------
+void HipEngine::check_targets_summary(const int64_t* h_offsets, int64_t n, const int64_t* h_starts, int64_t T,
+                                      int32_t bins, int32_t width) const {
+  check_targets_call(h_starts, T);
+  int64_t max_l2 = 0;
+  for (int64_t i = 0; i < n; ++i) max_l2 = std::max(max_l2, h_offsets[i + 1] - h_offsets[i]);
+  check_summary_args(table_.max_abs(), max_l2, targets_max_count(h_starts, T, h_offsets, n, sem_), bins, width);
+}
+
+void HipEngine::solve_targets_summary_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                             int64_t n, const int64_t* d_starts, const int64_t* h_starts, int64_t T,
+                                             int64_t* d_summary, int32_t* d_hist, int32_t bins, int32_t lo,
+                                             int32_t width, hipStream_t stream) {
+  check_targets_summary(h_offsets, std::max<int64_t>(n, 0), h_starts, T, bins, width);  // before any launch or change of state
+  if (n > 0 && !d_summary) throw Error("summary: no summary buffer");
+  if (n > 0 && bins > 0 && !d_hist) throw Error("summary: bins > 0 need a hist buffer");
+  const SummaryCall sc{d_summary, bins > 0 ? d_hist : nullptr, bins, lo, width};
+  const TargetsCall tc{d_starts, h_starts, T, nullptr, &sc};
+  run_profile(d_codes, d_offsets, h_offsets, n, 0, nullptr, stream, nullptr, 0, nullptr, &tc);  // n <= 0: no launch
+}
+
+void HipEngine::solve_targets_summary(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
+                                      int64_t T, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo,
+                                      int32_t width) {
+  check_targets_summary(offsets, std::max<int64_t>(n, 0), starts, T, bins, width);
+  if (n > 0 && bins > 0 && !hist_out) throw Error("summary: bins > 0 need a hist buffer");
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  if (n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  const size_t pairs = static_cast<size_t>(n) * static_cast<size_t>(T);
+  const std::vector<int64_t> rebased =
+      upload_batch(codes, offsets, n, sizeof(int64_t) * kSummaryCols * pairs + sizeof(int32_t) * static_cast<size_t>(bins) * pairs);
+  targets_summary_placed(placed_upload(rebased, n), starts, T, summary_out, hist_out, bins, lo, width, wall);
+}
+
+// d_out: summary (7 n T int64) | hist (n T bins int32); starts travel with the plan buffer
+void HipEngine::targets_summary_placed(const Placed& p, const int64_t* starts, int64_t T, int64_t* summary_out,
+                                       int32_t* hist_out, int32_t bins, int32_t lo, int32_t width, Stopwatch& wall) {
+  Slot& s = *slots_[0];
+  const size_t pairs = static_cast<size_t>(p.n) * static_cast<size_t>(T);
+  const size_t sbytes = sizeof(int64_t) * kSummaryCols * pairs, hbytes = sizeof(int32_t) * static_cast<size_t>(bins) * pairs;
+  char* d = static_cast<char*>(s.d_out);
+  solve_targets_summary_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, reinterpret_cast<int64_t*>(d),
+                               reinterpret_cast<int32_t*>(d + sbytes), bins, lo, width, s_compute_);
+  copy_d2h(summary_out, d, sbytes, s_compute_);
+  if (hbytes) copy_d2h(hist_out, d + sbytes, hbytes, s_compute_);
+  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+  host_call_stats(wall, device_kernel_ms(), p, sbytes + hbytes);
   stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1);
 }
 
@@ -1724,6 +1791,28 @@ void HipEngine::solve_targets_wire(const WireBatch& b, const int64_t* starts, in
   Stopwatch wall;
   wall.start();
   targets_placed(place_wire(b, sizeof(Result) * static_cast<size_t>(b.n) * static_cast<size_t>(T)), starts, T, out, wall);
+}
+
+void HipEngine::solve_targets_summary_wire(const WireBatch& b, const int64_t* starts, int64_t T, int64_t* summary_out,
+                                           int32_t* hist_out, int32_t bins, int32_t lo, int32_t width) {
+  check_targets_call(starts, T);
+  validate_wire(b);
+  if (b.device) throw Error("the *_wire host forms take host batches; a device-resident one goes through decode_wire_device");
+  if (b.n > 0) {  // the bound needs the lengths: the host's dense offsets of the batch, before anything is launched
+    std::vector<int64_t> dense(static_cast<size_t>(b.n) + 1);
+    wire_dense_offsets(b, dense.data());
+    check_targets_summary(dense.data(), b.n, starts, T, bins, width);
+  } else {
+    check_targets_summary(nullptr, 0, starts, T, bins, width);
+  }
+  if (b.n > 0 && bins > 0 && !hist_out) throw Error("summary: bins > 0 need a hist buffer");
+  finish_wire();
+  if (b.n <= 0) return;
+  Stopwatch wall;
+  wall.start();
+  const size_t pairs = static_cast<size_t>(b.n) * static_cast<size_t>(T);
+  targets_summary_placed(place_wire(b, sizeof(int64_t) * kSummaryCols * pairs + sizeof(int32_t) * static_cast<size_t>(bins) * pairs),
+                         starts, T, summary_out, hist_out, bins, lo, width, wall);
 }
 
 void HipEngine::report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks) {

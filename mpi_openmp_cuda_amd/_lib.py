@@ -144,6 +144,17 @@ def _decl(lib):
                                                     c_int64, c_void_p, c_void_p]),
         "moc_engine_solve_targets_wire": (c_int, [c_void_p, P(WireBatch), c_void_p, c_int64, c_void_p]),
         "moc_engine_targets_ms": (c_int, [c_void_p, c_void_p]),
+        "moc_cpu_targets_summary": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                            c_int, c_int, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+        "moc_targets_summary_geometry": (c_int, [c_void_p]),
+        "moc_engine_solve_targets_summary": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32,
+                                                     c_int32, c_int32, c_void_p, c_void_p]),
+        "moc_engine_solve_targets_summary_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                                            c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p,
+                                                            c_void_p, c_void_p]),
+        "moc_engine_solve_targets_summary_wire": (c_int, [c_void_p, P(WireBatch), c_void_p, c_int64, c_int32, c_int32,
+                                                          c_int32, c_void_p, c_void_p]),
+        "moc_engine_targets_summary_ms": (c_int, [c_void_p, c_void_p]),
         "moc_partition": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_double, c_void_p]),
         "moc_device_count": (c_int, []),
         "moc_host_register": (c_int, [c_void_p, c_size_t]),

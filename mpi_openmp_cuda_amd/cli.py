@@ -16,7 +16,8 @@ from .models.problem import Problem
 from .models.scoring import Semantics
 from .parallel import dist as D
 from .parallel.search import DistributedSearch
-from .utils.io import format_hits, format_report, format_summary, format_targets, format_topk, write_results
+from .utils.io import (format_hits, format_report, format_summary, format_targets, format_targets_summary, format_topk,
+                       write_results)
 
 
 def main(argv=None) -> int:
@@ -73,6 +74,13 @@ def main(argv=None) -> int:
                          "final '  best: t'. No placement straddles two targets. Not with --top K > 1, "
                          "--show-alignment, --min-score, --within, --distinct, --summary or --hist; record slices on "
                          "one node only (--partition records)")
+    ap.add_argument("--target-summary", action="store_true",
+                    help="with --targets: under each '  target t: ...' line print '    summary: offsets: C, min: A, "
+                         "max: B, mean: M, sd: S, z: Z', the --summary line of the record against that target alone, "
+                         "and after '  best: t' a line '  best by z: t' (or 'none'): the target whose best score lies "
+                         "the most standard deviations above the rest of its own profile")
+    ap.add_argument("--target-hist", default=None, metavar="LO:WIDTH:BINS",
+                    help="with --target-summary: one more line '    hist: c0 c1 ...' per target, the bins of --hist")
     a = ap.parse_args(argv)
     if not 1 <= a.top <= 64:
         ap.error("--top K: K must be in 1..64")
@@ -98,6 +106,19 @@ def main(argv=None) -> int:
         if not (-2 ** 31 <= h_lo < 2 ** 31 and 1 <= h_width < 2 ** 31 and 1 <= h_bins <= 256):
             ap.error("--hist LO:WIDTH:BINS: LO an int32, WIDTH an int32 >= 1, BINS in 1..256")
         hist_args = (h_bins, h_lo, h_width)
+    if a.target_summary and a.targets is None:
+        ap.error("--target-summary needs --targets FILE")
+    target_hist_args = (0, 0, 1)
+    if a.target_hist is not None:
+        if not a.target_summary:
+            ap.error("--target-hist LO:WIDTH:BINS needs --target-summary")
+        try:
+            h_lo, h_width, h_bins = (int(x) for x in a.target_hist.split(":"))
+        except ValueError:
+            ap.error("--target-hist LO:WIDTH:BINS: three integers separated by colons")
+        if not (-2 ** 31 <= h_lo < 2 ** 31 and 1 <= h_width < 2 ** 31 and 1 <= h_bins <= 256):
+            ap.error("--target-hist LO:WIDTH:BINS: LO an int32, WIDTH an int32 >= 1, BINS in 1..256")
+        target_hist_args = (h_bins, h_lo, h_width)
     if a.summary and (a.top > 1 or a.show_alignment or want_hits):
         ap.error("--summary does not combine with --top K > 1, --show-alignment, --min-score or --within")
     if a.min_score is not None and not -2 ** 31 <= a.min_score < 2 ** 31:
@@ -177,10 +198,15 @@ def main(argv=None) -> int:
     hit_rows = None
     summary = None
     target_rows = None
+    target_summary = None
     if a.targets is not None:
         try:
-            target_rows = search.run_targets(problem, target_set, Semantics.parse(a.semantics))
-        except ValueError as e:  # an invalid target set (more than 4096 targets): every rank raises it
+            if a.target_summary:
+                target_summary = search.run_targets_summary(problem, target_set, *target_hist_args,
+                                                            semantics=Semantics.parse(a.semantics))
+            else:
+                target_rows = search.run_targets(problem, target_set, Semantics.parse(a.semantics))
+        except ValueError as e:  # an invalid target set (more than 4096 targets) or the exactness bound: every rank raises it
             if ctx.is_root:
                 print(f"input error: {e}", file=sys.stderr)
             D.finalize(ctx)
@@ -218,6 +244,9 @@ def main(argv=None) -> int:
             sys.stdout.flush()
         elif a.summary:
             sys.stdout.write(format_summary(*summary))
+            sys.stdout.flush()
+        elif a.target_summary:
+            sys.stdout.write(format_targets_summary(*target_summary))
             sys.stdout.flush()
         elif a.targets is not None:
             sys.stdout.write(format_targets(target_rows[:, 0], target_rows))

@@ -455,11 +455,57 @@ def search_targets_cpu(problem: Problem, targets, semantics=Semantics.REFERENCE,
     return out
 
 
-def targets_best(rows):
+def _targets_best_z(rows, z):
+    """targets_best's ranking by z-score; see there."""
+    if isinstance(rows, np.ndarray) or not hasattr(rows, "device"):
+        r = np.asarray(rows, dtype=np.int32)
+        zz = np.asarray(z, dtype=np.float64)
+        if r.ndim != 3 or r.shape[2] != 3 or r.shape[1] < 1:
+            raise ValueError(f"targets_best needs [n, T, 3] rows, got {r.shape}")
+        if zz.shape != r.shape[:2]:
+            raise ValueError(f"targets_best needs z of the rows' shape [n, T] = {r.shape[:2]}, got {zz.shape}")
+        score = r[:, :, 0].astype(np.int64)
+        fit = score != _I32.min
+        zk = np.where(fit & ~np.isnan(zz), zz, -np.inf)  # a NaN ranks below every defined z
+        cand = fit & (zk == zk.max(axis=1, keepdims=True))
+        sk = np.where(cand, score, np.iinfo(np.int64).min)
+        cand &= sk == sk.max(axis=1, keepdims=True)  # ties: the higher score
+        t = np.argmax(cand, axis=1)                  # then the smallest target index
+        none = ~fit.any(axis=1)
+        row = np.ascontiguousarray(r[np.arange(r.shape[0]), t])
+        row[none] = (_I32.min, 0, 0)
+        return np.where(none, -1, t).astype(np.int32), row
+    import torch
+
+    assert rows.dtype == torch.int32 and rows.dim() == 3 and rows.shape[2] == 3 and rows.shape[1] >= 1
+    assert z.dtype == torch.float64 and tuple(z.shape) == tuple(rows.shape[:2]) and z.device == rows.device
+    T = rows.shape[1]
+    score = rows[:, :, 0].to(torch.int64)
+    fit = score != _I32.min
+    zk = torch.where(fit & ~torch.isnan(z), z, torch.full_like(z, float("-inf")))
+    cand = fit & (zk == zk.max(dim=1, keepdim=True).values)
+    sk = torch.where(cand, score, torch.full_like(score, int(np.iinfo(np.int64).min)))
+    cand = cand & (sk == sk.max(dim=1, keepdim=True).values)
+    idx = torch.arange(T, device=rows.device).expand_as(score)
+    t = torch.where(cand, idx, torch.full_like(idx, T)).min(dim=1).values
+    none = ~fit.any(dim=1)
+    t = torch.where(none, torch.zeros_like(t), t)
+    row = rows.gather(1, t.view(-1, 1, 1).expand(-1, 1, 3)).squeeze(1)
+    empty = torch.tensor([_I32.min, 0, 0], dtype=torch.int32, device=rows.device)
+    row = torch.where(none.unsqueeze(1), empty.expand_as(row), row).contiguous()
+    return torch.where(none, torch.full_like(t, -1), t).to(torch.int32), row
+
+
+def targets_best(rows, z=None):
     """The best target per record of multi-target rows [n, T, 3]: ``(target int32 [n], row int32 [n, 3])`` — the
     highest score, then the smallest target index; -1 and (INT32_MIN, 0, 0) where no target fits the record.
     ``rows``: a numpy array, or a torch tensor — then both results are tensors on its device, computed there
-    without a synchronisation."""
+    without a synchronisation.
+    With ``z`` (float64 [n, T] from :func:`targets_zscore`, numpy or torch like ``rows``) the ranking is by z-score
+    among the targets that fit: the highest z wins, a NaN ranks below every defined z, ties go to the higher score
+    and then to the smaller target index; -1 and the empty row only where no target fits."""
+    if z is not None:
+        return _targets_best_z(rows, z)
     if isinstance(rows, np.ndarray) or not hasattr(rows, "device"):
         r = np.asarray(rows, dtype=np.int32)
         if r.ndim != 3 or r.shape[2] != 3 or r.shape[1] < 1:
@@ -506,6 +552,73 @@ def targets_catalog_rows(rows, targets):
     out = rows.clone()
     out[:, :, 1] += shift
     return out.contiguous()
+
+
+# ---- per-target profile summary: one summary row and histogram per (record, target) pair
+def targets_summary_geometry() -> tuple:
+    """(threads per workgroup of the GPU's per-target summary kernels, largest ``bins``, the most bins a 4-lane group
+    takes in the histogram kernel — past it a 4-lane choice becomes 16 lanes —, the LDS bytes a workgroup's counters
+    stay within) — csrc/include/moc/kernel_bounds.hpp; no GPU needed."""
+    g = np.zeros(4, np.int32)
+    _lib.check(_lib.lib().moc_targets_summary_geometry(_lib.ptr(g)))
+    return tuple(int(x) for x in g)
+
+
+def _targets_summary_check(rc):
+    """A native per-target summary call's status: target-set errors ("targets:") and argument or exactness-bound
+    errors ("summary:") are ValueErrors, anything else a NativeError."""
+    if rc != 0:
+        msg = _lib.lib().moc_last_error().decode(errors="replace")
+        if msg.startswith("targets:") or msg.startswith("summary:"):
+            raise ValueError(msg)
+        raise _lib.NativeError(msg)
+
+
+def search_targets_summary_cpu(problem: Problem, targets, bins: int = 0, lo: int = 0, width: int = 1,
+                               semantics=Semantics.REFERENCE, threads: int = 0):
+    """Per-target profile summary on the CPU engine: ``(summary, hist)``. ``problem.seq1`` is the catalog and
+    ``targets`` its :class:`TargetSet` (or just the starts). ``summary`` is int64 [n, T, 7] with the columns
+    :data:`SUMMARY_COLS`: row [i, t] is exactly :func:`search_summary_cpu`'s row of record i against target t alone
+    — ``(max, n, k)`` is :func:`search_targets_cpu`'s row, n relative to the target's start — and
+    (0, 0, 0, INT32_MAX, INT32_MIN, 0, 0) where the record is longer than the target. ``hist`` is None with
+    ``bins = 0``, else int32 [n, T, bins] with search_summary_cpu's bin rule; every row sums to its pair's ``count``.
+    No entry straddles two targets. ValueError for an invalid target set ("targets: ..."), for ``bins`` / ``width``
+    out of range and when the exactness bound (:func:`summary_bound`) does not hold for the largest target profile
+    of the call ("summary: ...") — the catalog's own profile may be past it."""
+    bins, lo, width = _summary_args(bins, lo, width)
+    starts = _starts_of(targets, problem.L1)
+    T = starts.shape[0] - 1
+    summary = np.zeros((problem.n, T, len(SUMMARY_COLS)), np.int64)
+    hist = np.zeros((problem.n, T, bins), np.int32) if bins else None
+    _targets_summary_check(_lib.lib().moc_cpu_targets_summary(
+        _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+        _lib.ptr(problem.offsets), problem.n, _lib.ptr(starts), T, int(Semantics.parse(semantics)), int(threads), bins,
+        lo, width, _lib.ptr(summary), _lib.ptr(hist)))
+    return summary, hist
+
+
+def targets_zscore(summary):
+    """float64 [n, T]: :func:`summary_zscore` of every (record, target) pair of a per-target summary [n, T, 7] — how
+    far the pair's best score lies above the other entries of its target profile; NaN where summary_zscore is (fewer
+    than 3 entries, a pair that does not fit, or an all-equal rest). ``summary``: a numpy array — exact-integer
+    numerators, as summary_zscore — or a torch tensor — then the result is a tensor on its device, computed there
+    with float64 operations and no synchronisation, as :func:`summary_thresholds` does (sum - max and sumsq - max^2
+    are exact int64, the rest rounds)."""
+    if isinstance(summary, np.ndarray) or not hasattr(summary, "device"):
+        s = np.asarray(summary, dtype=np.int64)
+        if s.ndim != 3 or s.shape[2] != len(SUMMARY_COLS):
+            raise ValueError(f"targets_zscore needs a [n, T, 7] summary, got {s.shape}")
+        return summary_zscore(s).reshape(s.shape[0], s.shape[1])
+    import torch
+
+    assert summary.dtype == torch.int64 and summary.dim() == 3 and summary.shape[2] == len(SUMMARY_COLS)
+    c, mx = summary[:, :, _COUNT], summary[:, :, _MAX]
+    c1 = torch.clamp(c - 1, min=1).to(torch.float64)
+    mean = (summary[:, :, _SUM] - mx).to(torch.float64) / c1
+    var = (summary[:, :, _SUMSQ] - mx * mx).to(torch.float64) / c1 - mean * mean
+    ok = (c >= 3) & (var > 0)
+    sd = torch.sqrt(torch.where(ok, var, torch.ones_like(var)))
+    return torch.where(ok, (mx.to(torch.float64) - mean) / sd, torch.full_like(mean, float("nan"))).contiguous()
 
 
 # ---- alignment report: sign counts and marker bytes of result rows (csrc/include/moc/cpu_engine.hpp)
@@ -1159,6 +1272,86 @@ class HipSearchEngine:
         del keep
         return out
 
+    # ---- per-target profile summary (byte letters, dense offsets; csrc/src/hip/targets_summary_kernels.hip)
+    def solve_targets_summary(self, codes: np.ndarray, offsets: np.ndarray, targets, bins: int = 0, lo: int = 0,
+                              width: int = 1):
+        """Host CSR -> ``(summary, hist)`` as :func:`search_targets_summary_cpu` returns them, against the engine's
+        Seq1 as the catalog of ``targets``. One pass: the chunks of :meth:`solve_targets` with the per-target summary
+        kernel (and, with ``bins`` > 0, the histogram kernel) behind each chunk's catalog profile — (56 + 4 ``bins``)
+        T bytes come back per record, never the profile. Synchronous; ``stats()["kernels"]`` names
+        ``targets_summary``. ValueError as search_targets_summary_cpu, raised before anything is launched and
+        without a change to ``stats()``."""
+        bins, lo, width = _summary_args(bins, lo, width)
+        starts = _starts_of(targets, self.problem_L1)
+        T = starts.shape[0] - 1
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        summary = np.zeros((n, T, len(SUMMARY_COLS)), np.int64)
+        hist = np.zeros((n, T, bins), np.int32) if bins else None
+        _targets_summary_check(_lib.lib().moc_engine_solve_targets_summary(
+            self._h, _lib.ptr(codes), _lib.ptr(offsets), n, _lib.ptr(starts), T, bins, lo, width, _lib.ptr(summary),
+            _lib.ptr(hist)))
+        return summary, hist
+
+    def targets_summary_ms(self) -> float:
+        """Device time (ms) of the per-target summary and histogram launches of the last such call; 0 unless the
+        engine was created with MOC_PROFILE_TIMING=1 in the environment. Waits for them."""
+        ms = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().moc_engine_targets_summary_ms(self._h, ctypes.addressof(ms)))
+        return float(ms.value)
+
+    def solve_targets_summary_device(self, codes_t, offsets_t, h_offsets: np.ndarray, targets, bins: int = 0,
+                                     lo: int = 0, width: int = 1, summary_t=None, hist_t=None, starts_t=None,
+                                     stream=None):
+        """Device-resident batch (as :meth:`solve_device`) -> ``(summary_t, hist_t)``: an int64 [n, T, 7] tensor and,
+        with ``bins`` > 0, an int32 [n, T, bins] tensor on the codes' device (allocated when None; every element of
+        both is written). With ``bins = 0`` no histogram work is launched, ``hist_t`` is returned as given and not
+        touched. ``starts_t`` as :meth:`solve_targets_device`. Queued on ``stream`` (default: the current stream);
+        returns immediately — :func:`targets_zscore` and :func:`targets_best` can follow on the same stream.
+        ValueError as :meth:`solve_targets_summary`."""
+        import torch
+
+        bins, lo, width = _summary_args(bins, lo, width)
+        starts = _starts_of(targets, self.problem_L1)
+        T = starts.shape[0] - 1
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        n = h_offsets.shape[0] - 1
+        assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        if summary_t is None:
+            summary_t = torch.empty((n, T, len(SUMMARY_COLS)), dtype=torch.int64, device=codes_t.device)
+        if hist_t is None and bins:
+            hist_t = torch.empty((n, T, bins), dtype=torch.int32, device=codes_t.device)
+        assert summary_t.dtype == torch.int64 and summary_t.is_contiguous()
+        assert tuple(summary_t.shape) == (n, T, len(SUMMARY_COLS))
+        if bins:
+            assert hist_t.dtype == torch.int32 and hist_t.is_contiguous() and tuple(hist_t.shape) == (n, T, bins)
+        if starts_t is not None:
+            assert starts_t.dtype == torch.int64 and starts_t.is_contiguous() and starts_t.numel() == T + 1
+        _targets_summary_check(_lib.lib().moc_engine_solve_targets_summary_device(
+            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
+            n, ctypes.c_void_p(starts_t.data_ptr()) if starts_t is not None else None, _lib.ptr(starts), T, bins, lo,
+            width, ctypes.c_void_p(summary_t.data_ptr()), ctypes.c_void_p(hist_t.data_ptr()) if bins else None,
+            ctypes.c_void_p(stream.cuda_stream)))
+        return summary_t, hist_t
+
+    def solve_targets_summary_wire(self, ws, targets, bins: int = 0, lo: int = 0, width: int = 1, shift: int = 0):
+        """Host wire batch -> ``(summary, hist)``, as :meth:`solve_targets_summary` on the decoded records. See
+        :meth:`solve_profile_wire`."""
+        bins, lo, width = _summary_args(bins, lo, width)
+        starts = _starts_of(targets, self.problem_L1)
+        T = starts.shape[0] - 1
+        b, keep = wire_batch_of(ws, shift)
+        n = ws.n
+        summary = np.zeros((n, T, len(SUMMARY_COLS)), np.int64)
+        hist = np.zeros((n, T, bins), np.int32) if bins else None
+        _targets_summary_check(_lib.lib().moc_engine_solve_targets_summary_wire(
+            self._h, ctypes.byref(b), _lib.ptr(starts), T, bins, lo, width, _lib.ptr(summary), _lib.ptr(hist)))
+        del keep
+        return summary, hist
+
     # ---- alignment report (byte letters, dense offsets; csrc/src/hip/report_kernels.hip)
     def report(self,codes: np.ndarray, offsets: np.ndarray, rows, marks: bool = False):
         """Host CSR + result rows ([n, 3] or [n, K, 3]) -> the counts (and marker bytes) :func:`search_report_cpu`
@@ -1387,7 +1580,8 @@ class HipSearchEngine:
         d["format"] = _lib.FORMAT_NAMES[int(d["format"])]
         d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16"), (16, "profile"),
                                              (32, "report"), (64, "hits"), (128, "wire"), (256, "peaks"),
-                                             (512, "summary"), (1024, "targets"))
+                                             (512, "summary"), (1024, "targets"),
+                                             (2048, "targets_summary"))
                         if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
@@ -1480,6 +1674,15 @@ def align_targets_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets,
     """torch-facing op: the multi-target rows as an int32 [n, T, 3] tensor on the codes' device; see
     :meth:`HipSearchEngine.solve_targets_device`."""
     return engine.solve_targets_device(codes_t, offsets_t, h_offsets, targets, None, None, stream)
+
+
+def align_targets_summary_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, targets, bins: int = 0,
+                                 lo: int = 0, width: int = 1, stream=None):
+    """torch-facing op: ``(summary_t, hist_t)``, the per-target summary as an int64 [n, T, 7] tensor and (``bins`` > 0)
+    the histograms as an int32 [n, T, bins] tensor on the codes' device; see
+    :meth:`HipSearchEngine.solve_targets_summary_device`."""
+    return engine.solve_targets_summary_device(codes_t, offsets_t, h_offsets, targets, bins, lo, width, None, None,
+                                               None, stream)
 
 
 def align_report_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, rows_t, marks: bool = False,

@@ -29,7 +29,8 @@ from ..models.problem import Problem
 from ..models.scoring import Semantics
 from ..ops.align import (HipSearchEngine, decode_keys, device_count, keys_to_ordered_int64, ordered_int64_to_keys,
                         profile_offsets, search_cpu, search_hits_cpu, search_keys_cpu, search_report_cpu,
-                        search_summary_cpu, search_targets_cpu, search_topk_cpu, summary_bound, within_thresholds,
+                        search_summary_cpu, search_targets_cpu, search_targets_summary_cpu, search_topk_cpu,
+                         summary_bound, within_thresholds,
                          TargetSet, check_targets, _summary_args)
 from ..utils.timer import PhaseTimer
 from . import dist as D
@@ -337,6 +338,75 @@ class DistributedSearch:
             D.barrier(ctx)
             win.close(unlink=ctx.is_root)
         return rows.astype(np.int32) if ctx.is_root else None
+
+    def run_targets_summary(self, problem: Optional[Problem], targets=None, bins: int = 0, lo: int = 0, width: int = 1,
+                            semantics=Semantics.REFERENCE):
+        """The per-target profile summary (ops.align.search_targets_summary_cpu's ``(summary, hist)``, int64
+        [n, T, 7] and int32 [n, T, bins]; ``problem.seq1`` is the catalog of ``targets``, both needed on the root
+        only; the same ``bins``, ``lo`` and ``width`` on every rank) for the ``records`` partition: as
+        :meth:`run_targets` the root broadcasts the starts, and as :meth:`run_summary` every rank fills int64 arrays
+        that are INT64_MIN outside its slice and one MAX all-reduce of each combines them (no new transport).
+        Returns ``(summary, hist)`` on the root (``hist`` None with ``bins = 0``), else None. The target set and the
+        exactness bound of the whole batch are checked on the root, and every rank raises the same ValueError. One
+        node; byte letters through the engines' per-target summary calls."""
+        if self.partition != "records":
+            raise ValueError("the per-target summary runs on record slices (--partition records, one node): the "
+                             "offsets partition combines one packed key per record and cannot carry T summary rows")
+        bins, lo, width = _summary_args(bins, lo, width)
+        ctx, T = self.ctx, self.timer
+        sem = Semantics.parse(semantics)
+        hdr = None
+        if ctx.is_root:
+            starts = np.ascontiguousarray(targets.starts if isinstance(targets, TargetSet) else targets,
+                                          dtype=np.int64).reshape(-1)
+            hdr = np.array([starts.shape[0], problem.L1], np.int64)
+        hdr = D.bcast_array(ctx, hdr, 2, np.int64)
+        starts = D.bcast_array(ctx, starts if ctx.is_root else None, int(hdr[0]), np.int64)
+        starts = check_targets(starts, int(hdr[1]))  # every rank raises alike
+        nt = starts.shape[0] - 1
+        bad = None
+        if ctx.is_root:  # the largest target profile of the whole batch: the longest target, the shortest record in it
+            L2 = np.asarray(problem.lengths, dtype=np.int64)
+            longest = int(np.diff(starts).max())
+            fits = L2[(L2 >= 1) & (L2 <= longest)]
+            cmax = 0
+            if fits.size:
+                shortest = int(fits.min())
+                cmax = longest - shortest + (1 if sem == Semantics.SPEC or shortest == longest else 0)
+            w = max(abs(int(x)) for x in problem.weights.as_list())
+            limit = summary_bound(w, int(L2.max()) if problem.n else 0)
+            bad = np.array([cmax if cmax > limit else 0, limit], np.int64)
+        bad = D.bcast_array(ctx, bad, 2, np.int64)
+        if int(bad[0]):
+            raise ValueError(f"summary: exactness bound: a target profile of {int(bad[0])} entries may overflow the "
+                             f"int64 sum of squares (at most {int(bad[1])} entries per pair are exact for this batch)")
+        with T.phase("bcast"):
+            prob, sem, n, total, bounds = self._setup(problem, sem)
+        b, e = int(bounds[ctx.rank]), int(bounds[ctx.rank + 1])
+        with T.phase("distribute"):
+            win = self._open_window(problem, n, total)
+        none = np.iinfo(np.int64).min
+        with T.phase("compute"):
+            summary = np.full((n, nt, 7), none, np.int64)
+            hist = np.full((n, nt, bins), none, np.int64)
+            if e > b:
+                offsets = np.asarray(win.offsets[b:e + 1])
+                if self.engine is not None:
+                    s, h = self.engine.solve_targets_summary(np.asarray(win.codes), offsets, starts, bins, lo, width)
+                else:
+                    sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
+                                  offsets - offsets[0])
+                    s, h = search_targets_summary_cpu(sub, starts, bins, lo, width, sem, self.threads)
+                summary[b:e] = s
+                if bins:
+                    hist[b:e] = h
+        with T.phase("gather"):
+            summary = D.allreduce_max_int64(ctx, summary.reshape(-1)).reshape(n, nt, 7)
+            if bins:
+                hist = D.allreduce_max_int64(ctx, hist.reshape(-1)).reshape(n, nt, bins)
+            D.barrier(ctx)
+            win.close(unlink=ctx.is_root)
+        return (summary, hist.astype(np.int32) if bins else None) if ctx.is_root else None
 
     def report(self, problem: Problem, rows: np.ndarray):
         """Root only: ``(counts, marks)`` of the search's rows (ops.align.search_report_cpu's outputs, with the

@@ -119,8 +119,8 @@ class WireSlice:
             kept[shift][:] = s
         return kept[shift]
 
-    # ---- profile, top-K, hits, report, summary and multi-target rows of the slice on a HipSearchEngine: decoded on the
-    # GPU from these arrays
+    # ---- profile, top-K, hits, report, summary, multi-target rows and per-target summary of the slice on a
+    # HipSearchEngine: decoded on the GPU from these arrays
     def solve_profile_wire(self, engine, shift: int = 0):
         return engine.solve_profile_wire(self, shift)
 
@@ -139,6 +139,9 @@ class WireSlice:
 
     def solve_targets_wire(self, engine, targets, shift: int = 0):
         return engine.solve_targets_wire(self, targets, shift)
+
+    def solve_targets_summary_wire(self, engine, targets, bins: int = 0, lo: int = 0, width: int = 1, shift: int = 0):
+        return engine.solve_targets_summary_wire(self, targets, bins, lo, width, shift)
 
     def decode_cpu(self, shift: int = 0):
         """``(codes, offsets)`` of the slice from the native host decode (ops.align.decode_wire_cpu)."""

@@ -125,6 +125,47 @@ def format_targets(results, rows, first_index: int = 0) -> str:
     return "".join(out)
 
 
+def format_targets_summary(summary, hist=None, first_index: int = 0) -> str:
+    """:func:`format_targets` with every target's profile summary (int64 [n, T, 7] from the per-target summary calls;
+    its (max, n, k) are the multi-target rows, and record i's own line is target 1's row): under each
+    "  target t: ..." line "    summary: offsets: C, min: A, max: B, mean: M, sd: S, z: Z" in :func:`format_summary`'s
+    number formats and, with ``hist`` (int [n, T, B]), "    hist: c0 c1 ..."; after "  best: t" one more line
+    "  best by z: t" — ops.align.targets_best ranked by ops.align.targets_zscore — or "  best by z: none"."""
+    import math
+
+    from ..ops.align import SUMMARY_COLS, targets_best, targets_zscore
+
+    s = np.asarray(summary, dtype=np.int64)
+    if s.ndim != 3 or s.shape[2] != len(SUMMARY_COLS) or s.shape[1] < 1:
+        raise ValueError(f"format_targets_summary needs an [n, T, {len(SUMMARY_COLS)}] summary")
+    h = None if hist is None else np.asarray(hist, dtype=np.int64)
+    if h is not None and (h.ndim != 3 or h.shape[:2] != s.shape[:2]):
+        raise ValueError("format_targets_summary needs a histogram of the summary's pairs, [n, T, B]")
+    none = np.iinfo(np.int32).min
+    rows = np.ascontiguousarray(s[:, :, 4:7]).astype(np.int32)
+    z = targets_zscore(s)
+    best, _ = targets_best(rows)
+    best_z, _ = targets_best(rows, z)
+    out = []
+    for i in range(s.shape[0]):
+        score, n, k = rows[i, 0].tolist()
+        out.append(f"#{i + first_index}: score: {score}, n: {n}, k: {k}\n")
+        for t, (c, tot, sq, mn, mx, tn, tk) in enumerate(s[i].tolist()):
+            out.append(f"  target {t + 1}: none\n" if mx == none else f"  target {t + 1}: score: {mx}, n: {tn}, k: {tk}\n")
+            if c > 0:
+                mean = f"{tot / c:.3f}"
+                sd = f"{math.sqrt(max(c * sq - tot * tot, 0) / (c * c)):.3f}"
+            else:
+                mean = sd = "nan"
+            zs = "nan" if math.isnan(z[i, t]) else f"{z[i, t]:.2f}"
+            out.append(f"    summary: offsets: {c}, min: {mn}, max: {mx}, mean: {mean}, sd: {sd}, z: {zs}\n")
+            if h is not None:
+                out.append("    hist: " + " ".join(str(v) for v in h[i, t].tolist()) + "\n")
+        out.append(f"  best: {int(best[i]) + 1}\n" if best[i] >= 0 else "  best: none\n")
+        out.append(f"  best by z: {int(best_z[i]) + 1}\n" if best_z[i] >= 0 else "  best by z: none\n")
+    return "".join(out)
+
+
 def format_report(problem, rows, counts, marks, first_index: int = 0) -> str:
     """Results with their alignments. ``rows`` [n, 3] print as :func:`format_results` does and [n, K, 3] as
     :func:`format_topk` does; after the line of every real row — not an empty one (score INT32_MIN), nor one
