@@ -294,8 +294,15 @@ __device__ __forceinline__ void nt_store16(void* p, uint4 x) {
 }
 
 // Copies a block's staged results (LDS) to the output: dwords, plus a trailing halfword for R2 tiles
-// of odd length. `dst` is 4-byte aligned (tiles start at multiples of 64 records).
+// of odd length. `dst` has the natural alignment of the result format (tiles start at multiples of 64
+// records of an output that may itself be a slice of a larger array): 4 bytes, or 2 for R2.
 __device__ __forceinline__ void copy_results(void* dst, const uint8_t* src, int bytes, int tid, int nthreads) {
+  if (reinterpret_cast<uintptr_t>(dst) & 3) {  // R2 results from an odd element on: no store wider than a halfword
+    const int nh = bytes >> 1;
+    for (int q = tid; q < nh; q += nthreads)
+      static_cast<uint16_t*>(dst)[q] = reinterpret_cast<const uint16_t*>(src)[q];
+    return;
+  }
   // 16-byte stores when the destination allows (tile starts are multiples of 128 bytes): to host memory
   // (zero-copy) fewer, fuller write requests share the link with the tile loads' read requests
   int done = 0;

@@ -849,8 +849,12 @@ class HipSearchEngine:
 
     def solve_device(self, codes_t, offsets_t, h_offsets: np.ndarray, out_t, stream=None):
         """Device-resident batch (torch tensors on this engine's device). ``codes_t`` is the base so that
-        record i starts at codes_t[offsets[i]]; ``out_t`` is int32 [n, 3]. Queued on ``stream``
-        (torch.cuda.Stream, default: the current stream); returns immediately."""
+        record i starts at codes_t[offsets[i]] (absolute offsets: the batch may be a slice of a larger CSR array,
+        any first offset, any byte alignment); ``out_t`` is int32 [n, 3], possibly a row slice of a larger tensor.
+        Queued on ``stream`` (torch.cuda.Stream, default: the current stream); returns immediately. In every device
+        form torch's default stream (handle 0) stands for the engine's own compute stream, which torch's operations
+        on the default stream are not ordered with: synchronise, or pass a stream of your own, before torch reads
+        the results."""
         import torch
 
         h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
@@ -1090,7 +1094,9 @@ class HipSearchEngine:
         ``hoffsets_t[-1]`` with ``cap`` after a sync. ``cap = 0`` counts only. Exactly one of ``min_score``,
         ``thresholds_t`` (an int32 [n] tensor on the same device, e.g. built from a search's scores) and ``within``
         (a search queued on the same stream first). Both tensors are allocated when None. Queued on ``stream``
-        (default: the current stream); returns immediately. ``radius``: as :meth:`solve_hits`."""
+        (default: the current stream); returns immediately — except ``within`` on torch's default stream, which
+        stands for the engine's own compute stream: that call waits for its search on the host, since torch's
+        operations on the default stream are not ordered with that stream. ``radius``: as :meth:`solve_hits`."""
         import torch
 
         radius = _check_radius(radius)
@@ -1107,8 +1113,16 @@ class HipSearchEngine:
                 raise ValueError(f"hits: within must be >= 0, got {d}")
             best = torch.empty((n, 3), dtype=torch.int32, device=codes_t.device)
             self.solve_device(codes_t, offsets_t, h_offsets, best, stream)
+            # torch's default stream (handle 0) stands for the engine's own compute stream, which torch's operations
+            # are not ordered with: there the search is waited for before the thresholds are formed, and the
+            # thresholds before the hits kernels are queued. Any other stream orders the three by itself.
+            own = not stream.cuda_stream
+            if own and n > 0:
+                self.device_kernel_ms()
             with torch.cuda.stream(stream):
                 thresholds_t = (best[:, 0].to(torch.int64) - d).clamp(_I32.min, _I32.max).to(torch.int32).contiguous()
+            if own:
+                stream.synchronize()
         m = 0
         if min_score is not None:
             m = int(min_score)
