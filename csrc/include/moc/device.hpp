@@ -290,25 +290,34 @@ inline int tile16_waves_per_cu(int lds_bytes) {
   return kTile16WavesPerBlock * (blocks < 1 ? 1 : blocks > 2 ? 2 : blocks);
 }
 
-// ---- per-offset score profile and top-K selection (profile_kernels.hip; definitions: moc/cpu_engine.hpp)
-// One chunk of consecutive records [rec0, rec0 + n) of a batch: `starts` is a wave plan in the LUT-tile
-// geometry (63·u offsets per wave tile) over ALL of the chunk's records, its li relative to rec0; `poffsets`
-// is the batch's profile index (n_batch + 1 entries, device) and the chunk's profile is written to
-// prof[poffsets[r] - base + o], base = poffsets[rec0].
+// ---- per-offset score profile and its consumers (definitions: moc/cpu_engine.hpp)
+// One chunk of consecutive records [rec0, rec0 + n_rec) of a batch of n_total and where its profile lies: entry o of
+// record r at prof[poffsets[r] - base + o], base = poffsets[rec0]. `poffsets` is the batch's profile index (n_total
+// + 1 entries, device). What every kernel after offset_profile_kernel reads of a chunk; they reach the entries
+// through kc::chunk_first / kc::chunk_count (kernel_common.hpp), which hold the debug builds' bounds checks.
+struct ChunkView {
+  const ProfileEntry* prof = nullptr;
+  const int64_t* poffsets = nullptr;
+  int64_t base = 0;
+  int64_t prof_entries = 0;  // entries of `prof` (and bytes of a peak-mark array beside it)
+  int64_t rec0 = 0, n_rec = 0;
+  int64_t n_total = 0;
+};
+
+// ---- per-offset score profile and top-K selection (profile_kernels.hip)
+// The chunk `view` is written through `prof` (the same memory as view.prof): `starts` is a wave plan in the LUT-tile
+// geometry (63·u offsets per wave tile) over ALL of the chunk's records, its li relative to view.rec0.
 struct ProfileArgs {
   const WaveStart* starts = nullptr;  // device, n_waves + 1 entries
   int64_t n_waves = 0;
   int32_t u = 2;                      // sub-tiles per wave tile (1, 2 or 4)
-  int64_t rec0 = 0;
-  const int64_t* poffsets = nullptr;
-  int64_t base = 0;
   ProfileEntry* prof = nullptr;
-  int64_t prof_entries = 0;           // entries of `prof` (debug builds check the store index against it)
+  ChunkView view;
 };
 void launch_offset_profile(const ProblemView& pv, const BatchView& bv, const ProfileArgs& pa, hipStream_t stream);
-// The K best offsets of records [pa.rec0, pa.rec0 + n_rec) from their profile -> out[r * K + j] (batch-wide
-// record index r), padded with no_candidate(); 1 <= K <= kMaxTopK.
-void launch_topk_select(const ProfileArgs& pa, int64_t n_rec, int K, Result* out, hipStream_t stream);
+// The K best offsets of the chunk's records from their profile -> out[r * K + j] (batch-wide record index r),
+// padded with no_candidate(); 1 <= K <= kMaxTopK.
+void launch_topk_select(const ChunkView& view, int K, Result* out, hipStream_t stream);
 
 // ---- alignment report (report_kernels.hip; definitions: moc/cpu_engine.hpp report_batch_cpu)
 // The 32x32 pair classes (ScoreTable::cls), two bits each: entry e in word e / 16 at bit 2 * (e % 16). They do
@@ -348,17 +357,12 @@ void launch_alignment_report(const ProblemView& pv, const BatchView& bv, const R
                              hipStream_t stream);
 
 // ---- threshold hits (hits_kernels.hip; definitions: moc/cpu_engine.hpp hits_batch_cpu)
-// One chunk of consecutive records [rec0, rec0 + n_rec) whose profile lies where topk_select_kernel reads it:
-// prof[poffsets[r] - base + o]. hoffsets is the batch's int64 [n + 1] hit index: the count kernel leaves record
-// r's count in hoffsets[r + 1] (and 0 in hoffsets[0] when the chunk starts the batch), the scan turns the chunk's
+// One chunk (`view`) after its profile is written. hoffsets is the batch's int64 [n + 1] hit index: the count kernel
+// leaves record r's count in hoffsets[r + 1] (and 0 in hoffsets[0] when the chunk starts the batch), the scan turns the chunk's
 // counts into running totals on top of hoffsets[rec0] — complete since the previous chunk's scan on the same
 // stream — and the compaction stores record r's hits, ascending in o, at rows[hoffsets[r] ..) below `cap`.
 struct HitsArgs {
-  const ProfileEntry* prof = nullptr;
-  const int64_t* poffsets = nullptr;
-  int64_t base = 0;
-  int64_t prof_entries = 0;             // entries of `prof` (debug builds check the load index against it)
-  int64_t rec0 = 0, n_rec = 0;
+  ChunkView view;
   const int32_t* thresholds = nullptr;  // device int32 [n] (batch-wide record index), or null: min_score for all
   int32_t min_score = 0;
   int64_t* hoffsets = nullptr;          // device int64 [n + 1]
@@ -372,18 +376,13 @@ void launch_hits(const HitsArgs& ha, hipStream_t stream);
 void launch_hits_scan(const HitsArgs& ha, hipStream_t stream);
 
 // ---- distinct placements (peaks_kernels.hip; definitions: moc/cpu_engine.hpp peaks_filter)
-// One chunk of consecutive records [rec0, rec0 + n_rec) whose profile lies at prof[poffsets[r] - base + o]:
-// peak[poffsets[r] - base + o] <- 1 when entry o is a peak of radius `radius` of record r, else 0, for every entry
-// of the chunk. The host states what the chunk holds: any_short (a record of 1 .. bounds::kPeaksWaveEntries
+// One chunk (`view`) after its profile is written: peak[poffsets[r] - base + o] <- 1 when entry o is a peak of radius
+// `radius` of record r, else 0, for every entry of the chunk. The host states what the chunk holds: any_short (a record of 1 .. bounds::kPeaksWaveEntries
 // entries: the wave kernel runs), max_tiles (tiles of bounds::kPeaksTile entries of its longest record when that
 // is longer, else 0: the tile kernel runs) and lds_keys (the most keys a tile of the chunk puts into LDS, halo
 // included: at most kPeaksTile + 2 kPeaksMaxRadius).
 struct PeaksArgs {
-  const ProfileEntry* prof = nullptr;
-  const int64_t* poffsets = nullptr;
-  int64_t base = 0;
-  int64_t prof_entries = 0;  // entries of `prof` and bytes of `peak` (debug builds check indices against it)
-  int64_t rec0 = 0, n_rec = 0;
+  ChunkView view;
   int32_t radius = 0;        // 1 .. bounds::kPeaksMaxRadius
   int32_t any_short = 0;
   int32_t max_tiles = 0;
@@ -393,21 +392,14 @@ struct PeaksArgs {
 };
 void launch_peaks(const PeaksArgs& a, hipStream_t stream);
 // launch_topk_select / launch_hits over the peaks only (peak: what launch_peaks stored for the same chunk)
-void launch_topk_select_peaks(const ProfileArgs& pa, const uint8_t* peak, int64_t n_rec, int K, Result* out,
-                              hipStream_t stream);
+void launch_topk_select_peaks(const ChunkView& view, const uint8_t* peak, int K, Result* out, hipStream_t stream);
 void launch_hits_peaks(const HitsArgs& ha, const uint8_t* peak, hipStream_t stream);
 
 // ---- profile summary (summary_kernels.hip; definitions: moc/cpu_engine.hpp summary_batch_cpu)
-// One chunk of consecutive records [rec0, rec0 + n_rec) whose profile lies where hits_count_kernel reads it:
-// prof[poffsets[r] - base + o]. Record r's row goes to summary[r * 7 ..) and, with bins > 0, its histogram to
-// hist[r * bins ..) (batch-wide record index; every value of both is stored, nothing is accumulated into).
+// One chunk (`view`) after its profile is written. Record r's row goes to summary[r * 7 ..) and, with bins > 0, its
+// histogram to hist[r * bins ..) (batch-wide record index; every value of both is stored, nothing is accumulated into).
 struct SummaryArgs {
-  const ProfileEntry* prof = nullptr;
-  const int64_t* poffsets = nullptr;
-  int64_t base = 0;
-  int64_t prof_entries = 0;  // entries of `prof` (debug builds check the load index against it)
-  int64_t rec0 = 0, n_rec = 0;
-  int64_t n_total = 0;       // records of the batch (debug builds check the store indices against it)
+  ChunkView view;
   int64_t* summary = nullptr;  // device int64 [n * 7]
   int32_t* hist = nullptr;     // device int32 [n * bins], or null with bins == 0
   int32_t bins = 0, lo = 0, width = 1;
@@ -416,17 +408,11 @@ struct SummaryArgs {
 void launch_summary(const SummaryArgs& sa, hipStream_t stream);
 
 // ---- multi-target search (targets_kernels.hip; definitions: moc/cpu_engine.hpp targets_batch_cpu)
-// One chunk of consecutive records [rec0, rec0 + n_rec) whose catalog profile lies where hits_count_kernel reads
-// it: prof[poffsets[r] - base + o]. The chunk's n_rec * T (record, target) pairs each get a group of `group`
-// consecutive lanes (4, 16 or 64); pair (r, t) stores its row at out[(r * T + t) * 3 ..) (batch-wide record index;
+// One chunk (`view`) after its catalog profile is written. The chunk's n_rec * T (record, target) pairs each get a
+// group of `group` consecutive lanes (4, 16 or 64); pair (r, t) stores its row at out[(r * T + t) * 3 ..) (batch-wide record index;
 // every row is stored, nothing is accumulated into).
 struct TargetsArgs {
-  const ProfileEntry* prof = nullptr;
-  const int64_t* poffsets = nullptr;
-  int64_t base = 0;
-  int64_t prof_entries = 0;  // entries of `prof` (debug builds check the load index against it)
-  int64_t rec0 = 0, n_rec = 0;
-  int64_t n_total = 0;       // records of the batch (debug builds check the store index against it)
+  ChunkView view;
   const int64_t* starts = nullptr;  // device int64 [T + 1]
   int32_t T = 0;
   int32_t group = 64;        // lanes per pair: 4, 16 or 64

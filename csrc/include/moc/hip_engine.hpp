@@ -22,6 +22,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+#include <initializer_list>
 #include <memory>
 #include <utility>
 #include <vector>
@@ -341,26 +342,40 @@ class HipEngine {
   void upload_plan(const PlannedBatch& pb, void*& h_plan, size_t& h_cap, void*& d_plan, size_t& d_cap, hipStream_t s);
   Ran launch_planned(PlannedBatch& pb, const dev::BatchView& bv, int64_t first_offset, void* d_out, unsigned* counter,
                      void* d_plan, ResultFormat fmt, hipStream_t s);
-  std::vector<int64_t> upload_batch(const uint8_t* codes, const int64_t* offsets, int64_t n, size_t out_bytes);
-  // A host call's batch once it is on the device (uploaded by upload_batch, or decoded by decode_wire_device),
-  // with what the placement adds to stats(): the second halves of the host forms below take it from there.
+  // A host call's batch once it is on the device, with what the placement adds to stats() and the call's wall
+  // clock, started before the placement: the host forms' bodies (*_placed) take it from there. n <= 0: nothing placed.
   struct Placed {
-    const uint8_t* d_codes;
-    const int64_t* d_offsets;
-    const int64_t* h_offsets;
-    int64_t n;
-    int64_t h2d_bytes;
-    int32_t kernels;
+    const uint8_t* d_codes = nullptr;
+    const int64_t* d_offsets = nullptr;
+    const int64_t* h_offsets = nullptr;
+    int64_t n = 0;
+    int64_t h2d_bytes = 0;
+    int32_t kernels = 0;
+    Stopwatch wall;
   };
-  Placed placed_upload(const std::vector<int64_t>& rebased, int64_t n) const;
+  // Host byte letters and dense offsets -> slot 0's pooled buffers on the compute stream, its d_out grown to
+  // out_bytes, after finish_wire and hipSetDevice. The offsets go up rebased to 0; h_offsets is that copy.
+  Placed place_host(const uint8_t* codes, const int64_t* offsets, int64_t n, size_t out_bytes);
+  // A validated host wire batch decoded on the compute stream (decode_wire_device), d_out likewise.
   Placed place_wire(const WireBatch& b, size_t out_bytes);
-  void profile_placed(const Placed& p, ProfileEntry* prof_out, const int64_t* poffsets, Stopwatch& wall);
-  void topk_placed(const Placed& p, int K, Result* out, Stopwatch& wall, int64_t radius);
-  void hits_placed(const Placed& p, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
-                   std::vector<Result>& rows_out, int64_t max_rows_hint, Stopwatch& wall, int64_t radius);
-  void report_placed(const Placed& p, int K, const Result* rows, int32_t* counts, uint8_t* marks, Stopwatch& wall);
+  // The *_placed bodies' tail: the device form has filled consecutive segments of slot 0's d_out; copies each
+  // non-empty one back, waits for the compute stream and fills stats().
+  struct OutSegment {
+    void* host;
+    size_t bytes;
+  };
+  void finish_placed(Placed& p, std::initializer_list<OutSegment> segments);
+  void host_call_stats(Placed& p, double kernel_ms, size_t d2h_bytes);
   static size_t report_out_bytes(int64_t n, int K, int64_t mark_letters);
-  void host_call_stats(Stopwatch& wall, double kernel_ms, const Placed& p, size_t d2h_bytes);
+  void profile_placed(Placed& p, ProfileEntry* prof_out, const int64_t* poffsets);
+  void topk_placed(Placed& p, int K, Result* out, int64_t radius);
+  void hits_placed(Placed& p, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
+                   std::vector<Result>& rows_out, int64_t max_rows_hint, int64_t radius);
+  void summary_placed(Placed& p, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo, int32_t width);
+  void targets_placed(Placed& p, const int64_t* starts, int64_t T, Result* out);
+  void targets_summary_placed(Placed& p, const int64_t* starts, int64_t T, int64_t* summary_out, int32_t* hist_out,
+                              int32_t bins, int32_t lo, int32_t width);
+  void report_placed(Placed& p, int K, const Result* rows, int32_t* counts, uint8_t* marks);
   void ensure_device_events();  // ev_d0_ / ev_d1_, made by the first call that records them
   dev::Plan device_plan(void* d_plan, size_t n_starts, bool has_long_recs, int64_t n_long, const plan::TilePlan& tp,
                         unsigned long long* keys = nullptr) const;
@@ -389,40 +404,43 @@ class HipEngine {
   void run_staged(const uint8_t* codes, const int64_t* offsets, int64_t n, void* out, ResultFormat fmt,
                   bool packed5);
   void solve_wire_impl(const WireBatch& b, void* out, ResultFormat fmt, bool async);
-  struct HitsCall {  // what run_profile's chunks do instead of a select when the call is for hits
+  // ---- the profile family: one run loop over plan::plan_profile's chunks; a ProfileCall names the form
+  enum class ProfileKind { Profile, TopK, Hits, Summary, Targets, TargetsSummary };
+  struct HitsCall {
     int32_t min_score;
     const int32_t* d_thresholds;
     int64_t* d_hoffsets;
     Result* d_rows;
     int64_t cap;
   };
-  struct SummaryCall {  // ... or when it is for a summary
+  struct SummaryCall {
     int64_t* d_summary;
-    int32_t* d_hist;
+    int32_t* d_hist;  // null: no histogram
     int32_t bins, lo, width;
   };
-  struct TargetsCall {  // ... or when it is for a multi-target search
+  struct TargetsCall {
     const int64_t* d_starts;  // device [T + 1], or null: h_starts goes up with the plan buffer
     const int64_t* h_starts;
     int64_t T;
-    Result* d_out;
-    const SummaryCall* summary = nullptr;  // ... and when it is for the per-target summary (d_out unused)
+    Result* d_out;            // Targets only
   };
-  void run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n, int K,
-                   void* d_dst, hipStream_t stream, const HitsCall* hits = nullptr, int64_t radius = 0,
-                   const SummaryCall* summary = nullptr, const TargetsCall* targets = nullptr);
-  void check_targets_call(const int64_t* h_starts, int64_t T) const;  // throws unless T and starts are valid; touches nothing
-  void targets_placed(const Placed& p, const int64_t* starts, int64_t T, Result* out, Stopwatch& wall);
-  // throws unless the target set, bins, width and the exactness bound of the call's largest target profile allow
-  // the call; touches nothing
+  struct ProfileCall {
+    ProfileKind kind = ProfileKind::Profile;
+    void* d_dst = nullptr;  // Profile: ProfileEntry [poffsets[n]], written in one chunk; TopK: Result [n, K]
+    int K = 0;              // TopK
+    int64_t radius = 0;     // TopK, Hits: > 0 selects among the peaks of that radius only
+    HitsCall hits{};        // Hits
+    SummaryCall summary{};  // Summary, TargetsSummary
+    TargetsCall targets{};  // Targets, TargetsSummary
+  };
+  void run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                   const ProfileCall& call, hipStream_t stream);
+  // These throw unless the call is allowed and touch nothing: T and starts; bins, width and the batch's exactness
+  // bound (bounds::summary_exact); the target set, then the summary's checks over the call's largest target profile.
+  void check_targets_call(const int64_t* h_starts, int64_t T) const;
+  void check_summary(const int64_t* h_offsets, int64_t n, int32_t bins, int32_t width) const;
   void check_targets_summary(const int64_t* h_offsets, int64_t n, const int64_t* h_starts, int64_t T, int32_t bins,
                              int32_t width) const;
-  void targets_summary_placed(const Placed& p, const int64_t* starts, int64_t T, int64_t* summary_out,
-                              int32_t* hist_out, int32_t bins, int32_t lo, int32_t width, Stopwatch& wall);
-  // throws unless bins, width and the batch's exactness bound (bounds::summary_exact) allow the call; touches nothing
-  void check_summary(const int64_t* h_offsets, int64_t n, int32_t bins, int32_t width) const;
-  void summary_placed(const Placed& p, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo, int32_t width,
-                      Stopwatch& wall);
 
   EngineOptions opt_;
   int device_ = 0;
@@ -481,6 +499,7 @@ class HipEngine {
   void* d_wire_in_ = nullptr;
   size_t d_wire_in_cap_ = 0;
   std::vector<int64_t> wire_h_offsets_;
+  std::vector<int64_t> host_offsets_;  // place_host: the rebased offsets as uploaded
   int64_t wire_h2d_ = 0;
   int32_t wire_kernels_ = 0;
   std::vector<void*> pinned_;

@@ -1,6 +1,6 @@
 // Host-side work planning for the tile kernels (LUT tiles, tile16 whole / windowed / sliding, MFMA, the
-// per-offset profile): which records go to which kernel, and the cost-balanced runs of wave tiles every
-// persistent wave walks. Pure integer arithmetic over host offsets — no HIP runtime call — so a plan can be
+// per-offset profile): which records go to which kernel, the cost-balanced runs of wave tiles every
+// persistent wave walks, and the chunks of records the profile family passes through its bounded scratch. Pure integer arithmetic over host offsets — no HIP runtime call — so a plan can be
 // built and checked without a device (csrc/tests/test_core.cpp walks every plan the way the kernels do).
 // HipEngine owns one plan::Config, uploads what these functions return and launches from it.
 #pragma once
@@ -99,6 +99,39 @@ std::vector<dev::WaveStart> plan_waves(const Config& c, const int64_t* offsets, 
 // sum_l2 letters whose widest record needs max_need lanes; profile_runs: one chunk's runs with them.
 int profile_u(const Config& c, int64_t sum_l2, int64_t n, int64_t max_need);
 std::vector<dev::WaveStart> profile_runs(const Config& c, const int64_t* offsets, int64_t n, int u);
+
+// ---- the profile family (profile, top-K, hits, summary, targets, per-target summary): the chunks of consecutive
+// records that share a pass through the bounded profile scratch, and each chunk's wave runs. A profile call is one
+// chunk whatever the budget (its entries go to the caller's buffer); the others take records while their entries fit
+// scratch_bytes / entry_bytes (at least one entry), a record alone when its own profile is larger.
+struct ProfileChunk {
+  int64_t r0 = 0, r1 = 0;              // records [r0, r1)
+  size_t starts_at = 0, n_starts = 0;  // its runs: ProfilePlan::starts[starts_at .. starts_at + n_starts), n_starts - 1 waves
+  int64_t entries = 0;                 // poff[r1] - poff[r0]
+  int64_t min_l2 = 0, max_l2 = 0;      // its shortest and longest record
+  // distinct forms (radius > 0), what dev::PeaksArgs states of a chunk: a record of 1 .. bounds::kPeaksWaveEntries
+  // entries; tiles of bounds::kPeaksTile entries of its longest profile when that is longer, else 0; the most keys
+  // such a tile puts into LDS, halo included
+  int32_t any_short = 0, max_tiles = 0, lds_keys = 0;
+};
+struct ProfilePlan {
+  std::vector<int64_t> poff;           // the batch's profile index, n + 1 entries
+  int u = 2;                           // sub-tiles per wave tile, one choice for the batch
+  std::vector<dev::WaveStart> starts;  // every chunk's runs, li relative to the chunk's r0
+  std::vector<ProfileChunk> chunks;    // in order, together [0, n)
+  int64_t max_entries = 0, max_records = 0;  // of the largest chunk
+  int64_t max_l2 = 0, cells = 0;       // of the batch
+  int64_t max_target = 0;              // the longest target (0 without targets): with a chunk's min_l2, its longest slice
+  // plan buffer: poff at 0 | starts at starts_off | the target starts (T + 1, when they travel with the plan) at
+  // targets_off; every part 8-byte aligned
+  size_t starts_off = 0, targets_off = 0, bytes = 0;
+};
+// entry_bytes: 8, or 9 with a byte of peak marks beside every entry. radius: 0, or the peaks radius (the chunks'
+// peaks facts are filled only then). target_starts: null, or T + 1 host entries; upload_targets: they go into the
+// plan buffer. Throws Error for n >= 2^31 - 1 and for Seq1 / Seq2 lengths of 2^30 and more; n >= 1.
+ProfilePlan plan_profile(const Config& c, Semantics sem, const int64_t* offsets, int64_t n, bool chunked,
+                         int64_t entry_bytes, int64_t scratch_bytes, int64_t radius, const int64_t* target_starts = nullptr,
+                         int64_t T = 0, bool upload_targets = false);
 
 // ---- alignment report (report_kernels.hip): which records' rows take a lane each and which a wave each.
 // Records of at most bounds::kReportShortMaxL2 letters are short. A wave of the lane-per-row kernel takes up to

@@ -56,19 +56,18 @@ __device__ __forceinline__ long long block_exclusive_sum(long long v, long long*
 
 __global__ __launch_bounds__(256) void hits_count_kernel(HitsArgs ha) {
   const int64_t li = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (li >= ha.n_rec) return;  // wave-uniform
+  if (li >= ha.view.n_rec) return;  // wave-uniform
   const int lane = threadIdx.x & 63;
-  const int64_t r = ha.rec0 + li;
-  const int64_t pb = ha.poffsets[r] - ha.base;
-  const int C = __builtin_amdgcn_readfirstlane(static_cast<int>(ha.poffsets[r + 1] - ha.poffsets[r]));
+  const int64_t r = ha.view.rec0 + li;
+  const int64_t pb = chunk_first(ha.view, r);
+  const int C = __builtin_amdgcn_readfirstlane(chunk_count(ha.view, r));
   const int t = ha.thresholds ? ha.thresholds[r] : ha.min_score;
   int count = 0;  // C < 2^30
   for (int o0 = 0; o0 < C; o0 += 64) {  // wave-uniform: every lane reaches the ballot
     const int o = o0 + lane;
     bool hit = false;
     if (o < C) {
-      MOC_DCHECK(pb + o >= 0 && pb + o < ha.prof_entries);
-      hit = ha.prof[pb + o].score >= t;
+      hit = ha.view.prof[pb + o].score >= t;
     }
     count += __popcll(__builtin_amdgcn_ballot_w64(hit));
   }
@@ -82,10 +81,10 @@ __global__ __launch_bounds__(256) void hits_count_kernel(HitsArgs ha) {
 __global__ __launch_bounds__(256) void hits_block_sums_kernel(HitsArgs ha) {
   __shared__ long long ws[kWavesPerBlock];
   const int64_t li0 = static_cast<int64_t>(blockIdx.x) * bounds::kHitsScanBlockRecords + threadIdx.x * kPerThread;
-  const int64_t* cnt = ha.hoffsets + ha.rec0 + 1;
+  const int64_t* cnt = ha.hoffsets + ha.view.rec0 + 1;
   long long v = 0;
 #pragma unroll
-  for (int q = 0; q < kPerThread; ++q) v += li0 + q < ha.n_rec ? cnt[li0 + q] : 0;
+  for (int q = 0; q < kPerThread; ++q) v += li0 + q < ha.view.n_rec ? cnt[li0 + q] : 0;
   long long total;
   (void)block_exclusive_sum(v, ws, total);
   if (threadIdx.x == 0) ha.sums[blockIdx.x] = total;
@@ -94,7 +93,7 @@ __global__ __launch_bounds__(256) void hits_block_sums_kernel(HitsArgs ha) {
 // One block: sums[b] <- hoffsets[rec0] + sums[0] + ... + sums[b - 1], kHitsScanSumsPerPass sums per pass
 __global__ __launch_bounds__(256) void hits_scan_sums_kernel(HitsArgs ha, int64_t n_sums) {
   __shared__ long long ws[kWavesPerBlock];
-  long long carry = ha.hoffsets[ha.rec0];
+  long long carry = ha.hoffsets[ha.view.rec0];
   for (int64_t p0 = 0; p0 < n_sums; p0 += bounds::kHitsScanSumsPerPass) {  // block-uniform
     const int64_t i0 = p0 + threadIdx.x * kSumsPerThread;
     long long v[kSumsPerThread], mine = 0;
@@ -116,30 +115,30 @@ __global__ __launch_bounds__(256) void hits_scan_sums_kernel(HitsArgs ha, int64_
 __global__ __launch_bounds__(256) void hits_rescan_kernel(HitsArgs ha, int use_sums) {
   __shared__ long long ws[kWavesPerBlock];
   const int64_t li0 = static_cast<int64_t>(blockIdx.x) * bounds::kHitsScanBlockRecords + threadIdx.x * kPerThread;
-  int64_t* cnt = ha.hoffsets + ha.rec0 + 1;
-  const long long base = use_sums ? ha.sums[blockIdx.x] : ha.hoffsets[ha.rec0];
+  int64_t* cnt = ha.hoffsets + ha.view.rec0 + 1;
+  const long long base = use_sums ? ha.sums[blockIdx.x] : ha.hoffsets[ha.view.rec0];
   long long v[kPerThread], mine = 0;
 #pragma unroll
-  for (int q = 0; q < kPerThread; ++q) mine += v[q] = li0 + q < ha.n_rec ? cnt[li0 + q] : 0;
+  for (int q = 0; q < kPerThread; ++q) mine += v[q] = li0 + q < ha.view.n_rec ? cnt[li0 + q] : 0;
   long long total;
   // a thread stores only over the counts it read itself; hoffsets[rec0] is never stored here
   long long run = base + block_exclusive_sum(mine, ws, total);
 #pragma unroll
   for (int q = 0; q < kPerThread; ++q) {
     run += v[q];
-    if (li0 + q < ha.n_rec) cnt[li0 + q] = run;
+    if (li0 + q < ha.view.n_rec) cnt[li0 + q] = run;
   }
 }
 
 __global__ __launch_bounds__(256) void hits_compact_kernel(HitsArgs ha) {
   const int64_t li = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (li >= ha.n_rec) return;  // wave-uniform
+  if (li >= ha.view.n_rec) return;  // wave-uniform
   const int lane = threadIdx.x & 63;
-  const int64_t r = ha.rec0 + li;
+  const int64_t r = ha.view.rec0 + li;
   const int64_t out0 = ha.hoffsets[r], out1 = ha.hoffsets[r + 1];
   if (out0 >= ha.cap || out1 == out0) return;  // wave-uniform: nothing of this record lands below cap
-  const int64_t pb = ha.poffsets[r] - ha.base;
-  const int C = __builtin_amdgcn_readfirstlane(static_cast<int>(ha.poffsets[r + 1] - ha.poffsets[r]));
+  const int64_t pb = chunk_first(ha.view, r);
+  const int C = __builtin_amdgcn_readfirstlane(chunk_count(ha.view, r));
   const int t = ha.thresholds ? ha.thresholds[r] : ha.min_score;
   int base = 0;  // hits of the passes before this one (wave-uniform)
   for (int o0 = 0; o0 < C; o0 += 64) {  // wave-uniform: every lane reaches the ballot
@@ -147,8 +146,7 @@ __global__ __launch_bounds__(256) void hits_compact_kernel(HitsArgs ha) {
     ProfileEntry e{0, 0};
     bool hit = false;
     if (o < C) {
-      MOC_DCHECK(pb + o >= 0 && pb + o < ha.prof_entries);
-      e = ha.prof[pb + o];
+      e = ha.view.prof[pb + o];
       hit = e.score >= t;
     }
     const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
@@ -171,8 +169,8 @@ void preload_hits_kernels() {
 }
 
 void launch_hits_scan(const HitsArgs& ha, hipStream_t stream) {
-  if (ha.n_rec <= 0) return;
-  const int64_t n_sums = (ha.n_rec + bounds::kHitsScanBlockRecords - 1) / bounds::kHitsScanBlockRecords;
+  if (ha.view.n_rec <= 0) return;
+  const int64_t n_sums = (ha.view.n_rec + bounds::kHitsScanBlockRecords - 1) / bounds::kHitsScanBlockRecords;
   if (n_sums > 1) {
     hipLaunchKernelGGL(hits_block_sums_kernel, dim3(static_cast<unsigned>(n_sums)), dim3(kBlock), 0, stream, ha);
     hipLaunchKernelGGL(hits_scan_sums_kernel, dim3(1), dim3(kBlock), 0, stream, ha, n_sums);
@@ -182,8 +180,8 @@ void launch_hits_scan(const HitsArgs& ha, hipStream_t stream) {
 }
 
 void launch_hits(const HitsArgs& ha, hipStream_t stream) {
-  if (ha.n_rec <= 0) return;
-  const unsigned wave_blocks = static_cast<unsigned>((ha.n_rec + kWavesPerBlock - 1) / kWavesPerBlock);
+  if (ha.view.n_rec <= 0) return;
+  const unsigned wave_blocks = static_cast<unsigned>((ha.view.n_rec + kWavesPerBlock - 1) / kWavesPerBlock);
   hipLaunchKernelGGL(hits_count_kernel, dim3(wave_blocks), dim3(kBlock), 0, stream, ha);
   launch_hits_scan(ha, stream);
   if (ha.cap > 0 && ha.rows)

@@ -331,6 +331,21 @@ __device__ __forceinline__ void stage_bytes(uint8_t* dst, const uint8_t* src, in
   for (int t = threadIdx.x; t < n4; t += blockDim.x) d[t] = s[t];
 }
 
+// ---- a chunk's profile (dev::ChunkView) --------------------------------------------------------------
+// Index in v.prof (and in a peak-mark array beside it) of entry 0 of record r, a batch-wide index of one of the
+// chunk's records. Debug builds check here that r is the chunk's and that all of its entries lie inside prof: an
+// entry o in [0, chunk_count) of it then does too, and r indexes the batch-wide outputs.
+__device__ __forceinline__ int64_t chunk_first(const ChunkView& v, int64_t r) {
+  MOC_DCHECK(r >= v.rec0 && r < v.rec0 + v.n_rec && r < v.n_total);
+  MOC_DCHECK(v.poffsets[r] - v.base >= 0 && v.poffsets[r + 1] - v.base <= v.prof_entries);
+  return v.poffsets[r] - v.base;
+}
+// Entries of record r's profile: its candidate offsets (< 2^30; 0 for a record longer than Seq1).
+__device__ __forceinline__ int chunk_count(const ChunkView& v, int64_t r) {
+  MOC_DCHECK(v.poffsets[r + 1] >= v.poffsets[r]);
+  return static_cast<int>(v.poffsets[r + 1] - v.poffsets[r]);
+}
+
 }  // namespace kc
 }  // namespace dev
 }  // namespace moc

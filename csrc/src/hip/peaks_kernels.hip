@@ -52,16 +52,15 @@ __device__ __forceinline__ unsigned long long shfl_u64_or0(unsigned long long v,
 
 __global__ __launch_bounds__(256) void peaks_wave_kernel(PeaksArgs a) {
   const int64_t li = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (li >= a.n_rec) return;  // wave-uniform
+  if (li >= a.view.n_rec) return;  // wave-uniform
   const int lane = threadIdx.x & 63;
-  const int64_t r = a.rec0 + li;
-  const int64_t pb = a.poffsets[r] - a.base;
-  const int C = __builtin_amdgcn_readfirstlane(static_cast<int>(a.poffsets[r + 1] - a.poffsets[r]));
+  const int64_t r = a.view.rec0 + li;
+  const int64_t pb = chunk_first(a.view, r);
+  const int C = __builtin_amdgcn_readfirstlane(chunk_count(a.view, r));
   if (C <= 0 || C > bounds::kPeaksWaveEntries) return;  // wave-uniform: none, or the tile kernel's
   unsigned long long key = 0;  // lanes past the record hold 0, the maximum's identity (a key is never 0)
   if (lane < C) {
-    MOC_DCHECK(pb + lane >= 0 && pb + lane < a.prof_entries);
-    key = final_key(a.prof[pb + lane].score, static_cast<uint32_t>(lane));
+    key = final_key(a.view.prof[pb + lane].score, static_cast<uint32_t>(lane));
   }
   unsigned long long m;
   if (a.radius >= 63) {  // wave-uniform: the window is the record
@@ -91,14 +90,13 @@ __global__ __launch_bounds__(256) void peaks_wave_kernel(PeaksArgs a) {
 __global__ __launch_bounds__(256) void peaks_tile_kernel(PeaksArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
   const int tid = threadIdx.x;
-  const int64_t total = a.n_rec * a.max_tiles;
+  const int64_t total = a.view.n_rec * a.max_tiles;
   for (int64_t w = blockIdx.x; w < total; w += gridDim.x) {  // block-uniform
     const int64_t li = w / a.max_tiles;
     const int t0 = static_cast<int>(w % a.max_tiles) * kTile;
-    const int64_t r = a.rec0 + li;
-    MOC_DCHECK(li >= 0 && li < a.n_rec);
-    const int64_t pb = a.poffsets[r] - a.base;
-    const int C = static_cast<int>(a.poffsets[r + 1] - a.poffsets[r]);
+    const int64_t r = a.view.rec0 + li;
+    const int64_t pb = chunk_first(a.view, r);
+    const int C = chunk_count(a.view, r);
     if (C <= bounds::kPeaksWaveEntries || t0 >= C) continue;  // block-uniform: the wave kernel's, or no such tile
     const int R = min(a.radius, C - 1);  // beyond C - 1 the window is the record either way
     const int Tn = min(kTile, C - t0);
@@ -113,8 +111,7 @@ __global__ __launch_bounds__(256) void peaks_tile_kernel(PeaksArgs a) {
       if (x < E) {
         const int o = lo + x;
         if (o >= 0 && o < C) {
-          MOC_DCHECK(pb + o >= 0 && pb + o < a.prof_entries);
-          own[q] = final_key(a.prof[pb + o].score, static_cast<uint32_t>(o));
+          own[q] = final_key(a.view.prof[pb + o].score, static_cast<uint32_t>(o));
         }
         keys[x] = own[q];
       }
@@ -144,26 +141,22 @@ __global__ __launch_bounds__(256) void peaks_tile_kernel(PeaksArgs a) {
       MOC_DCHECK(j + W - P >= 0 && j + W - P < E);
       const unsigned long long m = max_u64(keys[j], keys[j + W - P]);
       const int o = t0 + j;
-      MOC_DCHECK(pb + o >= 0 && pb + o < a.prof_entries);
-      a.peak[pb + o] = m == final_key(a.prof[pb + o].score, static_cast<uint32_t>(o)) ? 1 : 0;
+      a.peak[pb + o] = m == final_key(a.view.prof[pb + o].score, static_cast<uint32_t>(o)) ? 1 : 0;
     }
     __syncthreads();  // the next tile's stores come after these reads
   }
 }
 
 // topk_select_kernel over the peaks: an entry that is no peak has key 0, which no round picks.
-__global__ __launch_bounds__(256) void topk_select_peaks_kernel(const ProfileEntry* __restrict__ prof,
-                                                                const uint8_t* __restrict__ peak,
-                                                                const int64_t* __restrict__ poffsets, int64_t rec0,
-                                                                int64_t n_rec, int64_t base, int K,
+__global__ __launch_bounds__(256) void topk_select_peaks_kernel(ChunkView v, const uint8_t* __restrict__ peak, int K,
                                                                 Result* __restrict__ out) {
   const int64_t li = static_cast<int64_t>(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (li >= n_rec) return;
+  if (li >= v.n_rec) return;
   const int lane = threadIdx.x & 63;
-  const int64_t r = rec0 + li;
-  const ProfileEntry* e = prof + (poffsets[r] - base);
-  const uint8_t* pk = peak + (poffsets[r] - base);
-  const int C = __builtin_amdgcn_readfirstlane(static_cast<int>(poffsets[r + 1] - poffsets[r]));
+  const int64_t r = v.rec0 + li;
+  const ProfileEntry* __restrict__ e = v.prof + chunk_first(v, r);
+  const uint8_t* pk = peak + chunk_first(v, r);
+  const int C = __builtin_amdgcn_readfirstlane(chunk_count(v, r));
   auto key_at = [&](int o) { return pk[o] ? final_key(e[o].score, static_cast<uint32_t>(o)) : 0ull; };
   if (C <= 64) {
     // a lane per entry: the number of larger keys is a peak's row; rows #peaks .. K-1 are padding
@@ -214,19 +207,18 @@ __global__ __launch_bounds__(256) void topk_select_peaks_kernel(const ProfileEnt
 // hits_count_kernel over the peaks
 __global__ __launch_bounds__(256) void hits_count_peaks_kernel(HitsArgs ha, const uint8_t* __restrict__ peak) {
   const int64_t li = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (li >= ha.n_rec) return;  // wave-uniform
+  if (li >= ha.view.n_rec) return;  // wave-uniform
   const int lane = threadIdx.x & 63;
-  const int64_t r = ha.rec0 + li;
-  const int64_t pb = ha.poffsets[r] - ha.base;
-  const int C = __builtin_amdgcn_readfirstlane(static_cast<int>(ha.poffsets[r + 1] - ha.poffsets[r]));
+  const int64_t r = ha.view.rec0 + li;
+  const int64_t pb = chunk_first(ha.view, r);
+  const int C = __builtin_amdgcn_readfirstlane(chunk_count(ha.view, r));
   const int t = ha.thresholds ? ha.thresholds[r] : ha.min_score;
   int count = 0;  // C < 2^30
   for (int o0 = 0; o0 < C; o0 += 64) {  // wave-uniform: every lane reaches the ballot
     const int o = o0 + lane;
     bool hit = false;
     if (o < C) {
-      MOC_DCHECK(pb + o >= 0 && pb + o < ha.prof_entries);
-      hit = peak[pb + o] != 0 && ha.prof[pb + o].score >= t;
+      hit = peak[pb + o] != 0 && ha.view.prof[pb + o].score >= t;
     }
     count += __popcll(__builtin_amdgcn_ballot_w64(hit));
   }
@@ -239,13 +231,13 @@ __global__ __launch_bounds__(256) void hits_count_peaks_kernel(HitsArgs ha, cons
 // hits_compact_kernel over the peaks
 __global__ __launch_bounds__(256) void hits_compact_peaks_kernel(HitsArgs ha, const uint8_t* __restrict__ peak) {
   const int64_t li = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (li >= ha.n_rec) return;  // wave-uniform
+  if (li >= ha.view.n_rec) return;  // wave-uniform
   const int lane = threadIdx.x & 63;
-  const int64_t r = ha.rec0 + li;
+  const int64_t r = ha.view.rec0 + li;
   const int64_t out0 = ha.hoffsets[r], out1 = ha.hoffsets[r + 1];
   if (out0 >= ha.cap || out1 == out0) return;  // wave-uniform: nothing of this record lands below cap
-  const int64_t pb = ha.poffsets[r] - ha.base;
-  const int C = __builtin_amdgcn_readfirstlane(static_cast<int>(ha.poffsets[r + 1] - ha.poffsets[r]));
+  const int64_t pb = chunk_first(ha.view, r);
+  const int C = __builtin_amdgcn_readfirstlane(chunk_count(ha.view, r));
   const int t = ha.thresholds ? ha.thresholds[r] : ha.min_score;
   int base = 0;  // hits of the passes before this one (wave-uniform)
   for (int o0 = 0; o0 < C; o0 += 64) {  // wave-uniform: every lane reaches the ballot
@@ -253,8 +245,7 @@ __global__ __launch_bounds__(256) void hits_compact_peaks_kernel(HitsArgs ha, co
     ProfileEntry e{0, 0};
     bool hit = false;
     if (o < C) {
-      MOC_DCHECK(pb + o >= 0 && pb + o < ha.prof_entries);
-      e = ha.prof[pb + o];
+      e = ha.view.prof[pb + o];
       hit = peak[pb + o] != 0 && e.score >= t;
     }
     const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
@@ -276,30 +267,29 @@ void preload_peaks_kernels() {
 }
 
 void launch_peaks(const PeaksArgs& a, hipStream_t stream) {
-  if (a.n_rec <= 0 || a.radius <= 0) return;
+  if (a.view.n_rec <= 0 || a.radius <= 0) return;
   if (a.any_short) {
-    const unsigned blocks = static_cast<unsigned>((a.n_rec + kWavesPerBlock - 1) / kWavesPerBlock);
+    const unsigned blocks = static_cast<unsigned>((a.view.n_rec + kWavesPerBlock - 1) / kWavesPerBlock);
     hipLaunchKernelGGL(peaks_wave_kernel, dim3(blocks), dim3(kBlock), 0, stream, a);
   }
   if (a.max_tiles > 0) {
-    const int64_t total = a.n_rec * a.max_tiles;
+    const int64_t total = a.view.n_rec * a.max_tiles;
     const int64_t blocks = std::min<int64_t>(total, static_cast<int64_t>(std::max(a.num_cus, 1)) * 64);
     hipLaunchKernelGGL(peaks_tile_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock),
                        sizeof(unsigned long long) * static_cast<size_t>(a.lds_keys), stream, a);
   }
 }
 
-void launch_topk_select_peaks(const ProfileArgs& pa, const uint8_t* peak, int64_t n_rec, int K, Result* out,
-                              hipStream_t stream) {
-  if (n_rec <= 0) return;
-  const int64_t blocks = (n_rec + 3) / 4;
-  hipLaunchKernelGGL(topk_select_peaks_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, pa.prof,
-                     peak, pa.poffsets, pa.rec0, n_rec, pa.base, K, out);
+void launch_topk_select_peaks(const ChunkView& view, const uint8_t* peak, int K, Result* out, hipStream_t stream) {
+  if (view.n_rec <= 0) return;
+  const int64_t blocks = (view.n_rec + 3) / 4;
+  hipLaunchKernelGGL(topk_select_peaks_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, view, peak,
+                     K, out);
 }
 
 void launch_hits_peaks(const HitsArgs& ha, const uint8_t* peak, hipStream_t stream) {
-  if (ha.n_rec <= 0) return;
-  const unsigned wave_blocks = static_cast<unsigned>((ha.n_rec + kWavesPerBlock - 1) / kWavesPerBlock);
+  if (ha.view.n_rec <= 0) return;
+  const unsigned wave_blocks = static_cast<unsigned>((ha.view.n_rec + kWavesPerBlock - 1) / kWavesPerBlock);
   hipLaunchKernelGGL(hits_count_peaks_kernel, dim3(wave_blocks), dim3(kBlock), 0, stream, ha, peak);
   launch_hits_scan(ha, stream);
   if (ha.cap > 0 && ha.rows)

@@ -50,12 +50,12 @@ __global__ __launch_bounds__(256) void offset_profile_kernel(ProblemView pv, Bat
   const int end_li = __builtin_amdgcn_readfirstlane(we.li), end_t = __builtin_amdgcn_readfirstlane(we.t);
   while (li < end_li || (li == end_li && t < end_t)) {  // wave-uniform
     // ---- one record of the chunk: its first letters stay in a register across the run's tiles of it
-    const int64_t r = pa.rec0 + li;
+    const int64_t r = pa.view.rec0 + li;
     MOC_DCHECK(r >= 0 && r < bv.n);
     const uint8_t* rec = bv.codes + (bv.offsets[r] - bv.offsets[0]);
     const int L2 = __builtin_amdgcn_readfirstlane(static_cast<int>(bv.offsets[r + 1] - bv.offsets[r]));
-    const int64_t pbase = pa.poffsets[r] - pa.base;                                      // the record's first entry
-    const int C = __builtin_amdgcn_readfirstlane(static_cast<int>(pa.poffsets[r + 1] - pa.poffsets[r]));
+    const int64_t pbase = chunk_first(pa.view, r);
+    const int C = __builtin_amdgcn_readfirstlane(chunk_count(pa.view, r));
     const int steps = L2 <= L1 ? L2 : 0;
     const int need = L2 <= L1 ? L1 - L2 + 1 : 1;
     const int ntiles = (need + kSpan - 1) / kSpan;
@@ -118,9 +118,7 @@ __global__ __launch_bounds__(256) void offset_profile_kernel(ProblemView pv, Bat
         if (lane < kTileOffsets && o < C) {  // C = 0 for L2 > L1; o < C makes score(o, 0) a candidate
           ProfileEntry e{P[u], 0};
           if (o < last && L2 >= 2 && bd[u] + Pn > e.score) e = ProfileEntry{bd[u] + Pn, bk[u]};
-          const int64_t at = pbase + o;
-          MOC_DCHECK(at >= 0 && at < pa.prof_entries);
-          pa.prof[at] = e;
+          pa.prof[pbase + o] = e;
         }
       }
     }
@@ -133,15 +131,13 @@ __global__ __launch_bounds__(256) void offset_profile_kernel(ProblemView pv, Bat
 // round j's winner -> out[r * K + j] = (score, o, k of that offset); rounds past the record's C entries pad
 // with no_candidate(). A lane keeps its first four keys in registers (C <= 256 reads the profile once). Records
 // with C <= 64 take no rounds: a lane per entry ranks its key against the others (same rows).
-__global__ __launch_bounds__(256) void topk_select_kernel(const ProfileEntry* __restrict__ prof,
-                                                          const int64_t* __restrict__ poffsets, int64_t rec0,
-                                                          int64_t n_rec, int64_t base, int K, Result* __restrict__ out) {
+__global__ __launch_bounds__(256) void topk_select_kernel(ChunkView v, int K, Result* __restrict__ out) {
   const int64_t li = static_cast<int64_t>(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (li >= n_rec) return;
+  if (li >= v.n_rec) return;
   const int lane = threadIdx.x & 63;
-  const int64_t r = rec0 + li;
-  const ProfileEntry* e = prof + (poffsets[r] - base);
-  const int C = __builtin_amdgcn_readfirstlane(static_cast<int>(poffsets[r + 1] - poffsets[r]));
+  const int64_t r = v.rec0 + li;
+  const ProfileEntry* __restrict__ e = v.prof + chunk_first(v, r);
+  const int C = __builtin_amdgcn_readfirstlane(chunk_count(v, r));
   auto key_at = [&](int o) {
     return final_key(e[o].score, static_cast<uint32_t>(o));  // never 0: o < 2^31
   };
@@ -223,11 +219,10 @@ void launch_offset_profile(const ProblemView& pv, const BatchView& bv, const Pro
   }
 }
 
-void launch_topk_select(const ProfileArgs& pa, int64_t n_rec, int K, Result* out, hipStream_t stream) {
-  if (n_rec <= 0) return;
-  const int64_t blocks = (n_rec + 3) / 4;
-  hipLaunchKernelGGL(topk_select_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, pa.prof,
-                     pa.poffsets, pa.rec0, n_rec, pa.base, K, out);
+void launch_topk_select(const ChunkView& view, int K, Result* out, hipStream_t stream) {
+  if (view.n_rec <= 0) return;
+  const int64_t blocks = (view.n_rec + 3) / 4;
+  hipLaunchKernelGGL(topk_select_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, view, K, out);
 }
 
 }  // namespace dev

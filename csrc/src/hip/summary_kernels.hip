@@ -53,17 +53,16 @@ __device__ __forceinline__ int summary_bin_dev(int score, int lo, int width, int
 
 __global__ __launch_bounds__(256) void profile_summary_kernel(SummaryArgs sa) {
   const int64_t li = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (li >= sa.n_rec) return;  // wave-uniform
+  if (li >= sa.view.n_rec) return;  // wave-uniform
   const int lane = threadIdx.x & 63;
-  const int64_t r = sa.rec0 + li;
-  const int64_t pb = sa.poffsets[r] - sa.base;
-  const int C = __builtin_amdgcn_readfirstlane(static_cast<int>(sa.poffsets[r + 1] - sa.poffsets[r]));  // C < 2^30
+  const int64_t r = sa.view.rec0 + li;
+  const int64_t pb = chunk_first(sa.view, r);
+  const int C = __builtin_amdgcn_readfirstlane(chunk_count(sa.view, r));  // C < 2^30
   long long sum = 0, sumsq = 0;
   int mn = INT32_MAX;
   unsigned long long key = 0ull;  // 0: no entry (a real key is never 0: o < 2^31)
   for (int o = lane; o < C; o += 64) {
-    MOC_DCHECK(pb + o >= 0 && pb + o < sa.prof_entries);
-    const long long s = sa.prof[pb + o].score;
+    const long long s = sa.view.prof[pb + o].score;
     sum += s;
     sumsq += s * s;
     mn = min(mn, static_cast<int>(s));
@@ -79,13 +78,11 @@ __global__ __launch_bounds__(256) void profile_summary_kernel(SummaryArgs sa) {
     if (key != 0ull) {
       const int o = static_cast<int>(0xffffffffu - static_cast<uint32_t>(key));
       MOC_DCHECK(o >= 0 && o < C);
-      MOC_DCHECK(pb + o >= 0 && pb + o < sa.prof_entries);
-      const ProfileEntry e = sa.prof[pb + o];
+      const ProfileEntry e = sa.view.prof[pb + o];
       mx = e.score;
       bn = o;
       bk = e.k;
     }
-    MOC_DCHECK(r >= 0 && r < sa.n_total);
     long long* row = reinterpret_cast<long long*>(sa.summary) + r * kCols;
     row[0] = C;
     row[1] = sum;
@@ -102,25 +99,23 @@ __global__ __launch_bounds__(256) void summary_hist_kernel(SummaryArgs sa) {
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int64_t li = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + w;
-  const bool active = li < sa.n_rec;  // wave-uniform; an idle wave still reaches both barriers
+  const bool active = li < sa.view.n_rec;  // wave-uniform; an idle wave still reaches both barriers
   const int bins = sa.bins;
   MOC_DCHECK(bins >= 1 && bins <= bounds::kSummaryMaxBins);
   for (int b = lane; b < bins; b += 64) cnt[w][b] = 0;
   __syncthreads();
-  const int64_t r = sa.rec0 + li;
+  const int64_t r = sa.view.rec0 + li;
   if (active) {
-    const int64_t pb = sa.poffsets[r] - sa.base;
-    const int C = static_cast<int>(sa.poffsets[r + 1] - sa.poffsets[r]);
+    const int64_t pb = chunk_first(sa.view, r);
+    const int C = chunk_count(sa.view, r);
     for (int o = lane; o < C; o += 64) {
-      MOC_DCHECK(pb + o >= 0 && pb + o < sa.prof_entries);
-      const int b = summary_bin_dev(sa.prof[pb + o].score, sa.lo, sa.width, bins);
+      const int b = summary_bin_dev(sa.view.prof[pb + o].score, sa.lo, sa.width, bins);
       MOC_DCHECK(b >= 0 && b < bins);
       atomicAdd(&cnt[w][b], 1);  // LDS add: 64 lanes on one bin serialise and stay exact
     }
   }
   __syncthreads();
   if (active) {
-    MOC_DCHECK(r >= 0 && r < sa.n_total);
     int32_t* row = sa.hist + r * bins;
     for (int b = lane; b < bins; b += 64) row[b] = cnt[w][b];
   }
@@ -132,8 +127,8 @@ void preload_summary_kernels() {
 }
 
 void launch_summary(const SummaryArgs& sa, hipStream_t stream) {
-  if (sa.n_rec <= 0) return;
-  const unsigned wave_blocks = static_cast<unsigned>((sa.n_rec + kWavesPerBlock - 1) / kWavesPerBlock);
+  if (sa.view.n_rec <= 0) return;
+  const unsigned wave_blocks = static_cast<unsigned>((sa.view.n_rec + kWavesPerBlock - 1) / kWavesPerBlock);
   hipLaunchKernelGGL(profile_summary_kernel, dim3(wave_blocks), dim3(kBlock), 0, stream, sa);
   if (sa.bins > 0 && sa.hist) hipLaunchKernelGGL(summary_hist_kernel, dim3(wave_blocks), dim3(kBlock), 0, stream, sa);
 }

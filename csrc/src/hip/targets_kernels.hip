@@ -64,13 +64,13 @@ __global__ __launch_bounds__(256) void targets_select_kernel(TargetsArgs ta, Pro
   if (active) {
     const int64_t li = pair / ta.T;
     t = static_cast<int>(pair - li * ta.T);
-    r = ta.rec0 + li;
-    MOC_DCHECK(li >= 0 && li < ta.n_rec && r >= 0 && r < bv.n && t >= 0 && t < ta.T);
+    r = ta.view.rec0 + li;
+    MOC_DCHECK(li >= 0 && li < ta.view.n_rec && r >= 0 && r < bv.n && t >= 0 && t < ta.T);
     rec = bv.codes + (bv.offsets[r] - bv.offsets[0]);
     L2 = static_cast<int>(bv.offsets[r + 1] - bv.offsets[r]);
     b = ta.starts[t];
     len = static_cast<int>(ta.starts[t + 1] - b);
-    pb = ta.poffsets[r] - ta.base;
+    pb = chunk_first(ta.view, r);
     MOC_DCHECK(b >= 0 && len >= 1 && b + len <= L1);
   }
   const bool fits = active && L2 >= 1 && L2 <= len && L2 <= L1;
@@ -78,8 +78,8 @@ __global__ __launch_bounds__(256) void targets_select_kernel(TargetsArgs ta, Pro
   unsigned long long key = 0ull;          // 0: no entry (a real key is never 0: o < 2^31)
   for (int o = sub; o < slice; o += G) {
     const int64_t at = pb + b + o;
-    MOC_DCHECK(at >= 0 && at < ta.prof_entries && at < ta.poffsets[r + 1] - ta.base);
-    key = max_u64(key, final_key(ta.prof[at].score, static_cast<uint32_t>(o)));
+    MOC_DCHECK(b + o < chunk_count(ta.view, r));  // the slice lies inside the record's entries
+    key = max_u64(key, final_key(ta.view.prof[at].score, static_cast<uint32_t>(o)));
   }
   const bool boundary = fits && (pv.semantics == static_cast<int>(Semantics::Spec) || slice == 0);
   int bsum = 0;
@@ -101,12 +101,10 @@ __global__ __launch_bounds__(256) void targets_select_kernel(TargetsArgs ta, Pro
       const int o = static_cast<int>(0xffffffffu - static_cast<uint32_t>(key));
       MOC_DCHECK(o >= 0 && o < slice);
       const int64_t at = pb + b + o;
-      MOC_DCHECK(at >= 0 && at < ta.prof_entries);
-      const ProfileEntry e = ta.prof[at];
+      const ProfileEntry e = ta.view.prof[at];
       row = Result{e.score, o, e.k};
     }
     if (boundary && (key == 0ull || bsum > row.score)) row = Result{bsum, slice, 0};
-    MOC_DCHECK(r >= 0 && r < ta.n_total);
     ta.out[r * ta.T + t] = row;
   }
 }
@@ -120,7 +118,7 @@ namespace {
 template <int G>
 void launch_targets_g(const TargetsArgs& ta, const ProblemView& pv, const BatchView& bv, hipStream_t stream) {
   constexpr int64_t kGroupsPerBlock = kBlock / G;
-  const int64_t n_pairs = ta.n_rec * ta.T;
+  const int64_t n_pairs = ta.view.n_rec * ta.T;
   for (int64_t pair0 = 0; pair0 < n_pairs;) {
     const int64_t blocks = std::min<int64_t>((n_pairs - pair0 + kGroupsPerBlock - 1) / kGroupsPerBlock, kMaxBlocksPerLaunch);
     hipLaunchKernelGGL((targets_select_kernel<G>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, ta, pv,
@@ -131,7 +129,7 @@ void launch_targets_g(const TargetsArgs& ta, const ProblemView& pv, const BatchV
 }  // namespace
 
 void launch_targets(const TargetsArgs& ta, const ProblemView& pv, const BatchView& bv, hipStream_t stream) {
-  if (ta.n_rec <= 0 || ta.T <= 0) return;
+  if (ta.view.n_rec <= 0 || ta.T <= 0) return;
   switch (ta.group) {
     case 4: launch_targets_g<4>(ta, pv, bv, stream); break;
     case 16: launch_targets_g<16>(ta, pv, bv, stream); break;

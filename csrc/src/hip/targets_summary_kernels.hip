@@ -101,13 +101,13 @@ __device__ __forceinline__ Pair pair_of(const TargetsArgs& ta, const ProblemView
   if (p.active) {
     const int64_t li = pair / ta.T;
     p.t = static_cast<int>(pair - li * ta.T);
-    p.r = ta.rec0 + li;
-    MOC_DCHECK(li >= 0 && li < ta.n_rec && p.r >= 0 && p.r < bv.n && p.t >= 0 && p.t < ta.T);
+    p.r = ta.view.rec0 + li;
+    MOC_DCHECK(li >= 0 && li < ta.view.n_rec && p.r >= 0 && p.r < bv.n && p.t >= 0 && p.t < ta.T);
     p.rec = bv.codes + (bv.offsets[p.r] - bv.offsets[0]);
     p.L2 = static_cast<int>(bv.offsets[p.r + 1] - bv.offsets[p.r]);
     p.b = ta.starts[p.t];
     len = static_cast<int>(ta.starts[p.t + 1] - p.b);
-    p.pb = ta.poffsets[p.r] - ta.base;
+    p.pb = chunk_first(ta.view, p.r);
     MOC_DCHECK(p.b >= 0 && len >= 1 && p.b + len <= pv.L1);
   }
   p.fits = p.active && p.L2 >= 1 && p.L2 <= len && p.L2 <= pv.L1;
@@ -147,8 +147,8 @@ __global__ __launch_bounds__(256) void targets_summary_kernel(TargetsSummaryArgs
   unsigned long long key = 0ull;  // 0: no entry (a real key is never 0: o < 2^31)
   for (int o = sub; o < p.slice; o += G) {
     const int64_t at = p.pb + p.b + o;
-    MOC_DCHECK(at >= 0 && at < ta.prof_entries && at < ta.poffsets[p.r + 1] - ta.base);
-    const int sc = ta.prof[at].score;
+    MOC_DCHECK(p.b + o < chunk_count(ta.view, p.r));  // the slice lies inside the record's entries
+    const int sc = ta.view.prof[at].score;
     const long long s = sc;
     sum += s;
     sumsq += s * s;
@@ -168,8 +168,7 @@ __global__ __launch_bounds__(256) void targets_summary_kernel(TargetsSummaryArgs
       const int o = static_cast<int>(0xffffffffu - static_cast<uint32_t>(key));
       MOC_DCHECK(o >= 0 && o < p.slice);
       const int64_t at = p.pb + p.b + o;
-      MOC_DCHECK(at >= 0 && at < ta.prof_entries);
-      const ProfileEntry e = ta.prof[at];
+      const ProfileEntry e = ta.view.prof[at];
       mx = e.score;
       bn = o;
       bk = e.k;
@@ -186,7 +185,6 @@ __global__ __launch_bounds__(256) void targets_summary_kernel(TargetsSummaryArgs
         bk = 0;
       }
     }
-    MOC_DCHECK(p.r >= 0 && p.r < ta.n_total);
     long long* row = reinterpret_cast<long long*>(sa.summary) + (p.r * ta.T + p.t) * kCols;
     row[0] = count;
     row[1] = sum;
@@ -217,8 +215,8 @@ __global__ __launch_bounds__(256) void targets_hist_kernel(TargetsSummaryArgs sa
   __syncthreads();
   for (int o = sub; o < p.slice; o += G) {
     const int64_t at = p.pb + p.b + o;
-    MOC_DCHECK(at >= 0 && at < ta.prof_entries && at < ta.poffsets[p.r + 1] - ta.base);
-    const int b = targets_bin_dev(ta.prof[at].score, sa.lo, sa.width, bins);
+    MOC_DCHECK(p.b + o < chunk_count(ta.view, p.r));  // the slice lies inside the record's entries
+    const int b = targets_bin_dev(ta.view.prof[at].score, sa.lo, sa.width, bins);
     MOC_DCHECK(b >= 0 && b < bins);
     atomicAdd(&mine[b], 1);  // LDS add: lanes on one bin serialise and stay exact
   }
@@ -231,7 +229,6 @@ __global__ __launch_bounds__(256) void targets_hist_kernel(TargetsSummaryArgs sa
   }
   __syncthreads();
   if (p.active) {
-    MOC_DCHECK(p.r >= 0 && p.r < ta.n_total);
     int32_t* row = sa.hist + (p.r * ta.T + p.t) * bins;
     for (int b = sub; b < bins; b += G) row[b] = mine[b];
   }
@@ -246,7 +243,7 @@ namespace {
 template <int G>
 void launch_summary_g(const TargetsSummaryArgs& sa, const ProblemView& pv, const BatchView& bv, hipStream_t stream) {
   constexpr int64_t kGroupsPerBlock = kBlock / G;
-  const int64_t n_pairs = sa.ta.n_rec * sa.ta.T;
+  const int64_t n_pairs = sa.ta.view.n_rec * sa.ta.T;
   for (int64_t pair0 = 0; pair0 < n_pairs;) {
     const int64_t blocks = std::min<int64_t>((n_pairs - pair0 + kGroupsPerBlock - 1) / kGroupsPerBlock, kMaxBlocksPerLaunch);
     hipLaunchKernelGGL((targets_summary_kernel<G>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, sa, pv,
@@ -258,7 +255,7 @@ void launch_summary_g(const TargetsSummaryArgs& sa, const ProblemView& pv, const
 template <int G, int MAXB>
 void launch_hist_g(const TargetsSummaryArgs& sa, const ProblemView& pv, const BatchView& bv, hipStream_t stream) {
   constexpr int64_t kGroupsPerBlock = kBlock / G;
-  const int64_t n_pairs = sa.ta.n_rec * sa.ta.T;
+  const int64_t n_pairs = sa.ta.view.n_rec * sa.ta.T;
   for (int64_t pair0 = 0; pair0 < n_pairs;) {
     const int64_t blocks = std::min<int64_t>((n_pairs - pair0 + kGroupsPerBlock - 1) / kGroupsPerBlock, kMaxBlocksPerLaunch);
     hipLaunchKernelGGL((targets_hist_kernel<G, MAXB>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, sa,
@@ -269,7 +266,7 @@ void launch_hist_g(const TargetsSummaryArgs& sa, const ProblemView& pv, const Ba
 }  // namespace
 
 void launch_targets_summary(const TargetsSummaryArgs& sa, const ProblemView& pv, const BatchView& bv, hipStream_t stream) {
-  if (sa.ta.n_rec <= 0 || sa.ta.T <= 0) return;
+  if (sa.ta.view.n_rec <= 0 || sa.ta.T <= 0) return;
   switch (sa.ta.group) {
     case 4: launch_summary_g<4>(sa, pv, bv, stream); break;
     case 16: launch_summary_g<16>(sa, pv, bv, stream); break;

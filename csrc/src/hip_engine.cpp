@@ -930,12 +930,15 @@ void HipEngine::finalize_keys_device(const uint8_t* d_codes, const int64_t* d_of
   MOC_HIP_CHECK(hipGetLastError());
 }
 
-// Host batch -> slot 0's pooled device buffers on the compute stream, its d_out grown to out_bytes. Returns the
-// offsets rebased to 0, as uploaded: the device base pointer is the buffer itself (record i at d_codes +
-// rebased[i]).
-std::vector<int64_t> HipEngine::upload_batch(const uint8_t* codes, const int64_t* offsets, int64_t n, size_t out_bytes) {
+HipEngine::Placed HipEngine::place_host(const uint8_t* codes, const int64_t* offsets, int64_t n, size_t out_bytes) {
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  Placed p;
+  if (n <= 0) return p;
+  p.wall.start();
   Slot& s = *slots_[0];
-  std::vector<int64_t> rebased(static_cast<size_t>(n) + 1);
+  std::vector<int64_t>& rebased = host_offsets_;
+  rebased.resize(static_cast<size_t>(n) + 1);
   for (int64_t i = 0; i <= n; ++i) rebased[i] = offsets[i] - offsets[0];
   const size_t cbytes = static_cast<size_t>(rebased[n]);
   ensure(s.d_codes, s.d_codes_cap, std::max<size_t>(cbytes, 16) + 32);
@@ -943,44 +946,49 @@ std::vector<int64_t> HipEngine::upload_batch(const uint8_t* codes, const int64_t
   ensure(s.d_out, s.d_out_cap, out_bytes);
   if (cbytes) copy_h2d(s.d_codes, codes + offsets[0], cbytes, s_compute_);
   MOC_HIP_CHECK(hipMemcpyAsync(s.d_offsets, rebased.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s_compute_));
-  return rebased;
-}
-
-// upload_batch's buffers as a placed batch: rebased[n] letter bytes and n + 1 offsets went up.
-HipEngine::Placed HipEngine::placed_upload(const std::vector<int64_t>& rebased, int64_t n) const {
-  const Slot& s = *slots_[0];
-  return Placed{static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(), n,
-                rebased[n] + static_cast<int64_t>(sizeof(int64_t)) * (n + 1), 0};
+  p.d_codes = static_cast<const uint8_t*>(s.d_codes);
+  p.d_offsets = static_cast<const int64_t*>(s.d_offsets);
+  p.h_offsets = rebased.data();
+  p.n = n;
+  p.h2d_bytes = rebased[n] + static_cast<int64_t>(sizeof(int64_t)) * (n + 1);
+  return p;
 }
 
 // Stats of a synchronous call over a placed batch, once it is complete.
-void HipEngine::host_call_stats(Stopwatch& wall, double kernel_ms, const Placed& p, size_t d2h_bytes) {
+void HipEngine::host_call_stats(Placed& p, double kernel_ms, size_t d2h_bytes) {
   stats_.kernel_ms = kernel_ms;
   stats_.h2d_bytes = p.h2d_bytes;
   stats_.d2h_bytes = static_cast<int64_t>(d2h_bytes);
   stats_.kernels |= p.kernels;
-  wall.stop();
-  stats_.total_ms = wall.total_ms();
+  p.wall.stop();
+  stats_.total_ms = p.wall.total_ms();
+}
+
+void HipEngine::finish_placed(Placed& p, std::initializer_list<OutSegment> segments) {
+  const char* d = static_cast<const char*>(slots_[0]->d_out);
+  size_t at = 0;
+  for (const OutSegment& g : segments) {
+    if (g.bytes) copy_d2h(g.host, d + at, g.bytes, s_compute_);
+    at += g.bytes;
+  }
+  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+  host_call_stats(p, device_kernel_ms(), at);
 }
 
 void HipEngine::search_keys(const uint8_t* codes, const int64_t* offsets, int64_t n, int part, int parts,
                             uint64_t* keys) {
-  finish_wire();
-  MOC_HIP_CHECK(hipSetDevice(device_));
-  if (n <= 0) return;
-  Stopwatch wall;
-  wall.start();
+  Placed p = place_host(codes, offsets, n, sizeof(uint64_t) * static_cast<size_t>(std::max<int64_t>(n, 0)));
+  if (p.n <= 0) return;
   Slot& s = *slots_[0];
-  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, sizeof(uint64_t) * static_cast<size_t>(n));
   MOC_HIP_CHECK(hipEventRecord(ev_a_, s_compute_));
-  search_keys_device(static_cast<const uint8_t*>(s.d_codes), static_cast<const int64_t*>(s.d_offsets), rebased.data(),
-                     n, part, parts, static_cast<unsigned long long*>(s.d_out), s_compute_);
+  search_keys_device(p.d_codes, p.d_offsets, p.h_offsets, n, part, parts, static_cast<unsigned long long*>(s.d_out),
+                     s_compute_);
   MOC_HIP_CHECK(hipEventRecord(ev_b_, s_compute_));
   copy_d2h(keys, s.d_out, sizeof(uint64_t) * n, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
   float ms = 0;
   MOC_HIP_CHECK(hipEventElapsedTime(&ms, ev_a_, ev_b_));
-  host_call_stats(wall, ms, placed_upload(rebased, n), sizeof(uint64_t) * n);
+  host_call_stats(p, ms, sizeof(uint64_t) * n);
 }
 
 // ---- per-offset score profile and top-K alignments ------------------------------------------------------
@@ -1006,232 +1014,208 @@ double HipEngine::topk_select_ms() {
   return total;
 }
 
-// K == 0: the whole batch's profile -> d_dst (ProfileEntry, one chunk). K >= 1: top-K rows -> d_dst (Result
-// [n, K]), chunk by chunk through the bounded scratch. hits (with K == 0, d_dst unused): the same chunks, each
-// followed by count, prefix sum and compaction into the call's buffers. summary (likewise, without hits or a
-// radius): the same chunks, each followed by the summary and histogram kernels. targets (likewise): the same chunks,
-// each followed by the targets select kernel over the chunk's (record, target) pairs — or, with targets->summary, by
-// the per-target summary and histogram kernels over the same pairs. Plan buffer: poffsets (n + 1)
-// | every chunk's wave starts | the targets call's starts (T + 1; when the caller gave no device copy).
+namespace {
+// Output bytes of the host forms in slot 0's d_out: used for the allocation and for the copy back (n <= 0: 0)
+size_t rows_bytes(int64_t n, int64_t per_record) {
+  return n > 0 ? sizeof(Result) * static_cast<size_t>(n) * static_cast<size_t>(per_record) : 0;
+}
+size_t summary_bytes(int64_t rows) { return rows > 0 ? sizeof(int64_t) * kSummaryCols * static_cast<size_t>(rows) : 0; }
+size_t hist_bytes(int64_t rows, int32_t bins) {
+  return rows > 0 ? sizeof(int32_t) * static_cast<size_t>(bins) * static_cast<size_t>(rows) : 0;
+}
+size_t hits_index_bytes(int64_t n) { return n > 0 ? sizeof(int64_t) * static_cast<size_t>(n + 1) : 0; }
+size_t thresholds_bytes(int64_t n) { return n > 0 ? sizeof(int32_t) * static_cast<size_t>(n) : 0; }
+
+void check_topk_k(int K) {
+  if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+}
+// the device forms' buffer checks of the two summaries, after the call's own checks
+void check_summary_buffers(int64_t n, const void* d_summary, int32_t bins, const void* d_hist) {
+  if (n > 0 && !d_summary) throw Error("summary: no summary buffer");
+  if (n > 0 && bins > 0 && !d_hist) throw Error("summary: bins > 0 need a hist buffer");
+}
+void require_host_batch(const WireBatch& b) {
+  if (b.device) throw Error("the *_wire host forms take host batches; a device-resident one goes through decode_wire_device");
+}
+// A host wire batch's dense offsets (empty for n <= 0) for the summary checks, which need the lengths before
+// anything is launched
+std::vector<int64_t> wire_check_offsets(const WireBatch& b) {
+  validate_wire(b);
+  require_host_batch(b);
+  std::vector<int64_t> dense;
+  if (b.n > 0) {
+    dense.resize(static_cast<size_t>(b.n) + 1);
+    wire_dense_offsets(b, dense.data());
+  }
+  return dense;
+}
+}  // namespace
+
+// One profile-family call on `stream`: the chunks of plan::plan_profile, each the profile kernel into the bounded
+// scratch (a Profile call: its single chunk straight into call.d_dst), the peaks kernel when the call has a radius,
+// then the kind's consumer over the chunk's dev::ChunkView. Plan buffer: plan::ProfilePlan's layout.
 void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
-                            int K, void* d_dst, hipStream_t stream, const HitsCall* hits, int64_t radius,
-                            const SummaryCall* summary, const TargetsCall* targets) {
+                            const ProfileCall& call, hipStream_t stream) {
+  // what each kind is called in a trace and which stats().kernels bits it sets beside the profile kernel's 16
+  struct KindFacts {
+    const char* trace;
+    int32_t kernels;
+  };
+  static constexpr KindFacts kFacts[] = {
+      {"moc.solve_profile_device", 16},        {"moc.solve_topk_device", 16},
+      {"moc.solve_hits_device", 16 | 64},      {"moc.solve_summary_device", 16 | 512},
+      {"moc.solve_targets_device", 16 | 1024}, {"moc.solve_targets_summary_device", 16 | 2048},
+  };
+  const ProfileKind kind = call.kind;
+  const KindFacts& facts = kFacts[static_cast<int>(kind)];
   if (!have_problem_) throw Error("HipEngine: profile / top-K before set_problem");
-  if (K < 0 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
-  check_peaks_radius(radius);
+  if (kind == ProfileKind::TopK) check_topk_k(call.K);
+  check_peaks_radius(call.radius);
   finish_wire();
   MOC_HIP_CHECK(hipSetDevice(device_));
   ev_select_used_ = 0;
   if (n <= 0) return;
-  if (n >= (int64_t{1} << 31) - 1) throw Error("profile / top-K: more than 2^31 - 2 records in one call");
   if (!stream) stream = s_compute_;
-  TraceRange tr(targets && targets->summary ? "moc.solve_targets_summary_device"
-                : targets ? "moc.solve_targets_device"
-                : summary ? "moc.solve_summary_device"
-                : hits  ? "moc.solve_hits_device"
-                : K     ? "moc.solve_topk_device"
-                        : "moc.solve_profile_device");
-  const bool chunked = K || hits || summary || targets;  // through the bounded scratch
-  const bool peaks = chunked && radius > 0;  // the distinct forms: a byte of peak marks beside every scratch entry
+  const bool chunked = kind != ProfileKind::Profile;  // through the bounded scratch
+  const bool peaks = chunked && call.radius > 0;  // the distinct forms: a byte of peak marks beside every scratch entry
+  const bool targets = kind == ProfileKind::Targets || kind == ProfileKind::TargetsSummary;
   const int64_t entry_bytes = static_cast<int64_t>(sizeof(ProfileEntry)) + (peaks ? 1 : 0);
-  std::vector<int64_t> poff(static_cast<size_t>(n) + 1);
-  profile_offsets(h_offsets, n, poff.data());
-  int64_t sum_l2 = 0, max_l2 = 0, cells = 0, max_need = 1;
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t L2 = h_offsets[i + 1] - h_offsets[i];
-    sum_l2 += L2;
-    max_l2 = std::max(max_l2, L2);
-    max_need = std::max(max_need, dev::lanes_needed(cfg_.L1, L2));
-    cells += record_cells(cfg_.L1, L2);
-  }
-  if (cfg_.L1 >= (int64_t{1} << 30) || max_l2 >= (int64_t{1} << 30))
-    throw Error("Seq1 / Seq2 lengths beyond 2^30 exceed the device engine's offset range");
-  // sub-tiles per wave tile, as the LUT tile kernel picks them, narrowed to the batch's widest offset range
-  const int u = plan::profile_u(cfg_, sum_l2, n, max_need);
-  // chunks of consecutive records: the whole batch for a profile, bounded scratch for top-K, hits and the summary
-  struct Chunk {
-    int64_t r0, r1;
-    size_t starts_at, n_starts;
-  };
-  std::vector<Chunk> chunks;
-  const int64_t cap_entries = std::max<int64_t>(1, opt_.profile_scratch_bytes / entry_bytes);
-  for (int64_t r0 = 0; r0 < n;) {
-    int64_t r1 = r0 + 1;
-    if (!chunked)
-      r1 = n;
-    else
-      while (r1 < n && poff[r1 + 1] - poff[r0] <= cap_entries) ++r1;
-    chunks.push_back(Chunk{r0, r1, 0, 0});
-    r0 = r1;
-  }
-  std::vector<dev::WaveStart> starts;
-  int64_t max_entries = 0, max_records = 0;
-  for (Chunk& c : chunks) {
-    const std::vector<dev::WaveStart> runs = plan::profile_runs(cfg_, h_offsets + c.r0, c.r1 - c.r0, u);
-    c.starts_at = starts.size();
-    c.n_starts = runs.size();
-    starts.insert(starts.end(), runs.begin(), runs.end());
-    max_entries = std::max(max_entries, poff[c.r1] - poff[c.r0]);
-    max_records = std::max(max_records, c.r1 - c.r0);
-  }
-  const size_t poff_bytes = sizeof(int64_t) * poff.size();
-  const size_t starts_at = poff_bytes + sizeof(dev::WaveStart) * starts.size();  // 8-byte aligned: both parts are
-  const size_t tstarts_bytes = targets && !targets->d_starts ? sizeof(int64_t) * (static_cast<size_t>(targets->T) + 1) : 0;
-  const size_t plan_bytes = starts_at + tstarts_bytes;
+  const TargetsCall& tc = call.targets;
+  // throws for a batch past the record or length limits, before the trace range opens and anything is queued
+  const plan::ProfilePlan pp =
+      plan::plan_profile(cfg_, sem_, h_offsets, n, chunked, entry_bytes, opt_.profile_scratch_bytes, peaks ? call.radius : 0,
+                         targets ? tc.h_starts : nullptr, targets ? tc.T : 0, targets && !tc.d_starts);
+  TraceRange tr(facts.trace);
   MOC_HIP_CHECK(hipEventSynchronize(ev_plan_));  // previous call's plan buffers are free again
-  ensure(d_plan_, d_plan_cap_, plan_bytes);
-  ensure_host(h_plan_, h_plan_cap_, plan_bytes);
+  ensure(d_plan_, d_plan_cap_, pp.bytes);
+  ensure_host(h_plan_, h_plan_cap_, pp.bytes);
   // scratch: the largest chunk's profile entries | its peak marks (distinct forms)
-  const size_t scratch_entries = static_cast<size_t>(std::max<int64_t>(max_entries, 1));
+  const size_t scratch_entries = static_cast<size_t>(std::max<int64_t>(pp.max_entries, 1));
   if (chunked) ensure(d_prof_scratch_, d_prof_scratch_cap_, static_cast<size_t>(entry_bytes) * scratch_entries);
   uint8_t* d_peak = peaks ? static_cast<uint8_t*>(d_prof_scratch_) + sizeof(ProfileEntry) * scratch_entries : nullptr;
-  if (hits)
+  if (kind == ProfileKind::Hits)
     ensure(d_hits_sums_, d_hits_sums_cap_,
-           sizeof(int64_t) * static_cast<size_t>((max_records + bounds::kHitsScanBlockRecords - 1) / bounds::kHitsScanBlockRecords));
-  std::memcpy(h_plan_, poff.data(), poff_bytes);
-  std::memcpy(static_cast<char*>(h_plan_) + poff_bytes, starts.data(), sizeof(dev::WaveStart) * starts.size());
-  if (tstarts_bytes) std::memcpy(static_cast<char*>(h_plan_) + starts_at, targets->h_starts, tstarts_bytes);
-  int64_t max_target = 0;  // the longest target: with a chunk's shortest record, its longest slice
-  if (targets)
-    for (int64_t t = 0; t < targets->T; ++t) max_target = std::max(max_target, targets->h_starts[t + 1] - targets->h_starts[t]);
-  upload_staged(d_plan_, h_plan_, plan_bytes, stream);
-  dev::ProblemView pv = problem_view(max_l2);
+           sizeof(int64_t) * static_cast<size_t>((pp.max_records + bounds::kHitsScanBlockRecords - 1) / bounds::kHitsScanBlockRecords));
+  char* h_plan = static_cast<char*>(h_plan_);
+  std::memcpy(h_plan, pp.poff.data(), pp.starts_off);
+  std::memcpy(h_plan + pp.starts_off, pp.starts.data(), pp.targets_off - pp.starts_off);
+  if (pp.bytes > pp.targets_off) std::memcpy(h_plan + pp.targets_off, tc.h_starts, pp.bytes - pp.targets_off);
+  upload_staged(d_plan_, h_plan_, pp.bytes, stream);
+  const char* d_plan = static_cast<const char*>(d_plan_);
+  const int64_t* d_tstarts = tc.d_starts ? tc.d_starts : reinterpret_cast<const int64_t*>(d_plan + pp.targets_off);
+  dev::ProblemView pv = problem_view(pp.max_l2);
   pv.prof16 = nullptr;  // the LUT sweep: exact int32 for any weights
   pv.mfma_sweep = 0;
   const dev::BatchView bv{d_codes + h_offsets[0], d_offsets, n};
   ensure_device_events();
   if (chunked && profile_timing_)
-    while (ev_select_.size() < 2 * chunks.size()) {
+    while (ev_select_.size() < 2 * pp.chunks.size()) {
       hipEvent_t e = nullptr;
       MOC_HIP_CHECK(hipEventCreate(&e));
       ev_select_.push_back(e);
     }
   MOC_HIP_CHECK(hipEventRecord(ev_d0_, stream));
-  for (const Chunk& c : chunks) {
+  for (const plan::ProfileChunk& c : pp.chunks) {
     dev::ProfileArgs pa;
-    pa.starts = reinterpret_cast<const dev::WaveStart*>(static_cast<const char*>(d_plan_) + poff_bytes) + c.starts_at;
+    pa.starts = reinterpret_cast<const dev::WaveStart*>(d_plan + pp.starts_off) + c.starts_at;
     pa.n_waves = static_cast<int64_t>(c.n_starts) - 1;
-    pa.u = u;
-    pa.rec0 = c.r0;
-    pa.poffsets = static_cast<const int64_t*>(d_plan_);
-    pa.base = chunked ? poff[c.r0] : 0;
-    pa.prof = chunked ? static_cast<ProfileEntry*>(d_prof_scratch_) : static_cast<ProfileEntry*>(d_dst);
-    pa.prof_entries = chunked ? poff[c.r1] - poff[c.r0] : poff[n];
+    pa.u = pp.u;
+    pa.prof = static_cast<ProfileEntry*>(chunked ? d_prof_scratch_ : call.d_dst);
+    dev::ChunkView& view = pa.view;
+    view.prof = pa.prof;
+    view.poffsets = reinterpret_cast<const int64_t*>(d_plan);
+    view.base = pp.poff[c.r0];  // 0 for a Profile call: its one chunk starts the batch
+    view.prof_entries = c.entries;
+    view.rec0 = c.r0;
+    view.n_rec = c.r1 - c.r0;
+    view.n_total = n;
     dev::launch_offset_profile(pv, bv, pa, stream);
-    if (chunked) {
-      if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
-      if (peaks) {
-        dev::PeaksArgs ka;
-        ka.prof = pa.prof;
-        ka.poffsets = pa.poffsets;
-        ka.base = pa.base;
-        ka.prof_entries = pa.prof_entries;
-        ka.rec0 = c.r0;
-        ka.n_rec = c.r1 - c.r0;
-        ka.radius = static_cast<int32_t>(radius);
-        ka.num_cus = cfg_.num_cus;
-        ka.peak = d_peak;
-        int64_t max_c = 0;
-        for (int64_t r = c.r0; r < c.r1; ++r) {
-          const int64_t C = poff[r + 1] - poff[r];
-          if (C >= 1 && C <= bounds::kPeaksWaveEntries) ka.any_short = 1;
-          max_c = std::max(max_c, C);
-        }
-        if (max_c > bounds::kPeaksWaveEntries) {
-          ka.max_tiles = static_cast<int32_t>((max_c + bounds::kPeaksTile - 1) / bounds::kPeaksTile);
-          ka.lds_keys = static_cast<int32_t>(std::min<int64_t>(bounds::kPeaksTile, max_c) + 2 * std::min<int64_t>(radius, max_c - 1));
-        }
-        dev::launch_peaks(ka, stream);
-      }
-      if (targets) {
-        dev::TargetsArgs ta;
-        ta.prof = pa.prof;
-        ta.poffsets = pa.poffsets;
-        ta.base = pa.base;
-        ta.prof_entries = pa.prof_entries;
-        ta.rec0 = c.r0;
-        ta.n_rec = c.r1 - c.r0;
-        ta.n_total = n;
-        ta.starts = targets->d_starts ? targets->d_starts
-                                      : reinterpret_cast<const int64_t*>(static_cast<const char*>(d_plan_) + starts_at);
-        ta.T = static_cast<int32_t>(targets->T);
-        int64_t min_l2 = INT64_MAX;
-        for (int64_t r = c.r0; r < c.r1; ++r) min_l2 = std::min(min_l2, h_offsets[r + 1] - h_offsets[r]);
-        ta.group = targets_group_ ? targets_group_ : bounds::targets_group(std::max<int64_t>(max_target - min_l2, 0));
-        ta.out = targets->d_out;
-        if (const SummaryCall* ts = targets->summary) {
-          dev::TargetsSummaryArgs tsa;
-          tsa.ta = ta;
-          tsa.summary = ts->d_summary;
-          tsa.hist = ts->d_hist;
-          tsa.bins = ts->d_hist ? ts->bins : 0;
-          tsa.lo = ts->lo;
-          tsa.width = ts->width;
-          dev::launch_targets_summary(tsa, pv, bv, stream);
-        } else {
-          dev::launch_targets(ta, pv, bv, stream);
-        }
-      } else if (summary) {
-        dev::SummaryArgs sa;
-        sa.prof = pa.prof;
-        sa.poffsets = pa.poffsets;
-        sa.base = pa.base;
-        sa.prof_entries = pa.prof_entries;
-        sa.rec0 = c.r0;
-        sa.n_rec = c.r1 - c.r0;
-        sa.n_total = n;
-        sa.summary = summary->d_summary;
-        sa.hist = summary->d_hist;
-        sa.bins = summary->d_hist ? summary->bins : 0;
-        sa.lo = summary->lo;
-        sa.width = summary->width;
-        dev::launch_summary(sa, stream);
-      } else if (hits) {
+    if (!chunked) continue;
+    if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
+    if (peaks) {
+      dev::PeaksArgs ka;
+      ka.view = view;
+      ka.radius = static_cast<int32_t>(call.radius);
+      ka.any_short = c.any_short;
+      ka.max_tiles = c.max_tiles;
+      ka.lds_keys = c.lds_keys;
+      ka.num_cus = cfg_.num_cus;
+      ka.peak = d_peak;
+      dev::launch_peaks(ka, stream);
+    }
+    dev::TargetsSummaryArgs tsa;  // the two targets kinds: tsa.ta alone, or all of it
+    if (targets) {
+      tsa.ta.view = view;
+      tsa.ta.starts = d_tstarts;
+      tsa.ta.T = static_cast<int32_t>(tc.T);
+      tsa.ta.group = targets_group_ ? targets_group_ : bounds::targets_group(std::max<int64_t>(pp.max_target - c.min_l2, 0));
+      tsa.ta.out = tc.d_out;
+    }
+    switch (kind) {
+      case ProfileKind::Profile: break;
+      case ProfileKind::TopK:
+        if (peaks)
+          dev::launch_topk_select_peaks(view, d_peak, call.K, static_cast<Result*>(call.d_dst), stream);
+        else
+          dev::launch_topk_select(view, call.K, static_cast<Result*>(call.d_dst), stream);
+        break;
+      case ProfileKind::Hits: {
         dev::HitsArgs ha;
-        ha.prof = pa.prof;
-        ha.poffsets = pa.poffsets;
-        ha.base = pa.base;
-        ha.prof_entries = pa.prof_entries;
-        ha.rec0 = c.r0;
-        ha.n_rec = c.r1 - c.r0;
-        ha.thresholds = hits->d_thresholds;
-        ha.min_score = hits->min_score;
-        ha.hoffsets = hits->d_hoffsets;
+        ha.view = view;
+        ha.thresholds = call.hits.d_thresholds;
+        ha.min_score = call.hits.min_score;
+        ha.hoffsets = call.hits.d_hoffsets;
         ha.sums = static_cast<int64_t*>(d_hits_sums_);
-        ha.rows = hits->d_rows;
-        ha.cap = hits->cap;
+        ha.rows = call.hits.d_rows;
+        ha.cap = call.hits.cap;
         if (peaks)
           dev::launch_hits_peaks(ha, d_peak, stream);
         else
           dev::launch_hits(ha, stream);
-      } else if (peaks) {
-        dev::launch_topk_select_peaks(pa, d_peak, c.r1 - c.r0, K, static_cast<Result*>(d_dst), stream);
-      } else {
-        dev::launch_topk_select(pa, c.r1 - c.r0, K, static_cast<Result*>(d_dst), stream);
+        break;
       }
-      if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
+      case ProfileKind::Summary: {
+        dev::SummaryArgs sa;
+        sa.view = view;
+        sa.summary = call.summary.d_summary;
+        sa.hist = call.summary.d_hist;
+        sa.bins = call.summary.d_hist ? call.summary.bins : 0;
+        sa.lo = call.summary.lo;
+        sa.width = call.summary.width;
+        dev::launch_summary(sa, stream);
+        break;
+      }
+      case ProfileKind::Targets: dev::launch_targets(tsa.ta, pv, bv, stream); break;
+      case ProfileKind::TargetsSummary:
+        tsa.summary = call.summary.d_summary;
+        tsa.hist = call.summary.d_hist;
+        tsa.bins = call.summary.d_hist ? call.summary.bins : 0;
+        tsa.lo = call.summary.lo;
+        tsa.width = call.summary.width;
+        dev::launch_targets_summary(tsa, pv, bv, stream);
+        break;
     }
+    if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
   }
   MOC_HIP_CHECK(hipGetLastError());
   MOC_HIP_CHECK(hipEventRecord(ev_d1_, stream));
   MOC_HIP_CHECK(hipEventRecord(ev_plan_, stream));
   stats_ = EngineStats{};
-  stats_.cells = cells;
+  stats_.cells = pp.cells;
   stats_.records = n;
-  stats_.chunks = static_cast<int64_t>(chunks.size());
-  stats_.kernels = (hits ? 16 | 64 : 16) | (peaks ? 256 : 0) | (summary ? 512 : 0) |
-                   (targets ? (targets->summary ? 2048 : 1024) : 0);
+  stats_.chunks = static_cast<int64_t>(pp.chunks.size());
+  stats_.kernels = facts.kernels | (peaks ? 256 : 0);
 }
 
 void HipEngine::solve_profile_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
                                      int64_t n, ProfileEntry* d_prof, hipStream_t stream) {
-  run_profile(d_codes, d_offsets, h_offsets, n, 0, d_prof, stream);
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::Profile, d_prof}, stream);
 }
 
 void HipEngine::solve_topk_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
                                   int64_t n, int K, Result* d_out, hipStream_t stream, int64_t radius) {
-  if (K < 1) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
-  run_profile(d_codes, d_offsets, h_offsets, n, K, d_out, stream, nullptr, radius);
+  if (K < 1) check_topk_k(K);  // before the problem check; a K past the range after it (run_profile)
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::TopK, d_out, K, radius}, stream);
 }
 
 void HipEngine::solve_profile(const uint8_t* codes, const int64_t* offsets, int64_t n, ProfileEntry* prof_out,
@@ -1240,44 +1224,28 @@ void HipEngine::solve_profile(const uint8_t* codes, const int64_t* offsets, int6
   MOC_HIP_CHECK(hipSetDevice(device_));
   profile_offsets(offsets, std::max<int64_t>(n, 0), poffsets_out);
   if (n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const size_t pbytes = sizeof(ProfileEntry) * static_cast<size_t>(poffsets_out[n]);
-  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, std::max<size_t>(pbytes, 8));
-  profile_placed(placed_upload(rebased, n), prof_out, poffsets_out, wall);
+  Placed p = place_host(codes, offsets, n, std::max<size_t>(sizeof(ProfileEntry) * static_cast<size_t>(poffsets_out[n]), 8));
+  profile_placed(p, prof_out, poffsets_out);
 }
 
-// The host forms' second halves: the batch is on the device (p) and slot 0's d_out holds the call's output bytes.
-void HipEngine::profile_placed(const Placed& p, ProfileEntry* prof_out, const int64_t* poffsets, Stopwatch& wall) {
-  Slot& s = *slots_[0];
-  const size_t pbytes = sizeof(ProfileEntry) * static_cast<size_t>(poffsets[p.n]);
-  run_profile(p.d_codes, p.d_offsets, p.h_offsets, p.n, 0, s.d_out, s_compute_);
-  if (pbytes) copy_d2h(prof_out, s.d_out, pbytes, s_compute_);
-  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  host_call_stats(wall, device_kernel_ms(), p, pbytes);
+// The host forms' bodies: the batch is on the device (p) and slot 0's d_out holds the call's output bytes, the
+// segments finish_placed copies back in their order.
+void HipEngine::profile_placed(Placed& p, ProfileEntry* prof_out, const int64_t* poffsets) {
+  solve_profile_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, static_cast<ProfileEntry*>(slots_[0]->d_out), s_compute_);
+  finish_placed(p, {{prof_out, sizeof(ProfileEntry) * static_cast<size_t>(poffsets[p.n])}});
 }
 
 void HipEngine::solve_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, Result* out,
                            int64_t radius) {
-  if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  check_topk_k(K);
   check_peaks_radius(radius);
-  finish_wire();
-  MOC_HIP_CHECK(hipSetDevice(device_));
-  if (n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const std::vector<int64_t> rebased =
-      upload_batch(codes, offsets, n, sizeof(Result) * static_cast<size_t>(n) * static_cast<size_t>(K));
-  topk_placed(placed_upload(rebased, n), K, out, wall, radius);
+  Placed p = place_host(codes, offsets, n, rows_bytes(n, K));
+  if (p.n > 0) topk_placed(p, K, out, radius);
 }
 
-void HipEngine::topk_placed(const Placed& p, int K, Result* out, Stopwatch& wall, int64_t radius) {
-  Slot& s = *slots_[0];
-  const size_t obytes = sizeof(Result) * static_cast<size_t>(p.n) * static_cast<size_t>(K);
-  run_profile(p.d_codes, p.d_offsets, p.h_offsets, p.n, K, s.d_out, s_compute_, nullptr, radius);
-  copy_d2h(out, s.d_out, obytes, s_compute_);
-  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  host_call_stats(wall, device_kernel_ms(), p, obytes);
+void HipEngine::topk_placed(Placed& p, int K, Result* out, int64_t radius) {
+  solve_topk_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, K, static_cast<Result*>(slots_[0]->d_out), s_compute_, radius);
+  finish_placed(p, {{out, rows_bytes(p.n, K)}});
 }
 
 // ---- threshold hits -------------------------------------------------------------------------------------
@@ -1296,7 +1264,7 @@ void HipEngine::solve_hits_device(const uint8_t* d_codes, const int64_t* d_offse
     return;
   }
   const HitsCall hc{min_score, d_thresholds, d_hoffsets, d_rows, d_rows ? cap : 0};
-  run_profile(d_codes, d_offsets, h_offsets, n, 0, nullptr, stream, &hc, radius);
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::Hits, nullptr, 0, radius, hc}, stream);
 }
 
 void HipEngine::solve_hits(const uint8_t* codes, const int64_t* offsets, int64_t n, int32_t min_score,
@@ -1309,21 +1277,16 @@ void HipEngine::solve_hits(const uint8_t* codes, const int64_t* offsets, int64_t
   rows_out.clear();
   hits_passes_ = 0;
   hoffsets_out[0] = 0;
-  if (n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const std::vector<int64_t> rebased =
-      upload_batch(codes, offsets, n, sizeof(int64_t) * static_cast<size_t>(n + 1) + sizeof(int32_t) * static_cast<size_t>(n));
-  hits_placed(placed_upload(rebased, n), min_score, thresholds, hoffsets_out, rows_out, max_rows_hint, wall, radius);
+  Placed p = place_host(codes, offsets, n, hits_index_bytes(n) + thresholds_bytes(n));
+  if (p.n > 0) hits_placed(p, min_score, thresholds, hoffsets_out, rows_out, max_rows_hint, radius);
 }
 
-void HipEngine::hits_placed(const Placed& p, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
-                            std::vector<Result>& rows_out, int64_t max_rows_hint, Stopwatch& wall, int64_t radius) {
-  Slot& s = *slots_[0];
+// d_out: hoffsets (n + 1) | thresholds (n); the rows have a buffer of their own, which the second pass may grow
+void HipEngine::hits_placed(Placed& p, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
+                            std::vector<Result>& rows_out, int64_t max_rows_hint, int64_t radius) {
   const int64_t n = p.n;
-  // d_out: hoffsets (n + 1) | thresholds (n); the rows have a buffer of their own, which the second pass may grow
-  const size_t hbytes = sizeof(int64_t) * static_cast<size_t>(n + 1), tbytes = sizeof(int32_t) * static_cast<size_t>(n);
-  char* d = static_cast<char*>(s.d_out);
+  const size_t hbytes = hits_index_bytes(n), tbytes = thresholds_bytes(n);
+  char* d = static_cast<char*>(slots_[0]->d_out);
   if (thresholds) copy_h2d(d + hbytes, thresholds, tbytes, s_compute_);
   int64_t cap = std::max<int64_t>(max_rows_hint < 0 ? 4 * n : max_rows_hint, 1);
   double kernel_ms = 0;
@@ -1347,7 +1310,7 @@ void HipEngine::hits_placed(const Placed& p, int32_t min_score, const int32_t* t
     copy_d2h(rows_out.data(), d_hits_rows_, rbytes, s_compute_);
     MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
   }
-  host_call_stats(wall, kernel_ms, p, hbytes * static_cast<size_t>(hits_passes_) + rbytes);
+  host_call_stats(p, kernel_ms, hbytes * static_cast<size_t>(hits_passes_) + rbytes);
   if (thresholds) stats_.h2d_bytes += static_cast<int64_t>(tbytes);
 }
 
@@ -1367,40 +1330,26 @@ void HipEngine::solve_summary_device(const uint8_t* d_codes, const int64_t* d_of
                                      int64_t n, int64_t* d_summary, int32_t* d_hist, int32_t bins, int32_t lo,
                                      int32_t width, hipStream_t stream) {
   check_summary(h_offsets, std::max<int64_t>(n, 0), bins, width);  // before any launch or change of state
-  if (n > 0 && !d_summary) throw Error("summary: no summary buffer");
-  if (n > 0 && bins > 0 && !d_hist) throw Error("summary: bins > 0 need a hist buffer");
+  check_summary_buffers(n, d_summary, bins, d_hist);
   const SummaryCall sc{d_summary, bins > 0 ? d_hist : nullptr, bins, lo, width};
-  run_profile(d_codes, d_offsets, h_offsets, n, 0, nullptr, stream, nullptr, 0, &sc);  // n <= 0: launches nothing
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::Summary, nullptr, 0, 0, {}, sc}, stream);  // n <= 0: launches nothing
 }
 
 void HipEngine::solve_summary(const uint8_t* codes, const int64_t* offsets, int64_t n, int64_t* summary_out,
                               int32_t* hist_out, int32_t bins, int32_t lo, int32_t width) {
   check_summary(offsets, std::max<int64_t>(n, 0), bins, width);
   if (n > 0 && bins > 0 && !hist_out) throw Error("summary: bins > 0 need a hist buffer");
-  finish_wire();
-  MOC_HIP_CHECK(hipSetDevice(device_));
-  if (n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const size_t un = static_cast<size_t>(n);
-  const std::vector<int64_t> rebased =
-      upload_batch(codes, offsets, n, sizeof(int64_t) * kSummaryCols * un + sizeof(int32_t) * static_cast<size_t>(bins) * un);
-  summary_placed(placed_upload(rebased, n), summary_out, hist_out, bins, lo, width, wall);
+  Placed p = place_host(codes, offsets, n, summary_bytes(n) + hist_bytes(n, bins));
+  if (p.n > 0) summary_placed(p, summary_out, hist_out, bins, lo, width);
 }
 
 // d_out: summary (7 n int64) | hist (n * bins int32)
-void HipEngine::summary_placed(const Placed& p, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo,
-                               int32_t width, Stopwatch& wall) {
-  Slot& s = *slots_[0];
-  const size_t un = static_cast<size_t>(p.n);
-  const size_t sbytes = sizeof(int64_t) * kSummaryCols * un, hbytes = sizeof(int32_t) * static_cast<size_t>(bins) * un;
-  char* d = static_cast<char*>(s.d_out);
+void HipEngine::summary_placed(Placed& p, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo, int32_t width) {
+  const size_t sbytes = summary_bytes(p.n), hbytes = hist_bytes(p.n, bins);
+  char* d = static_cast<char*>(slots_[0]->d_out);
   solve_summary_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, reinterpret_cast<int64_t*>(d),
                        reinterpret_cast<int32_t*>(d + sbytes), bins, lo, width, s_compute_);
-  copy_d2h(summary_out, d, sbytes, s_compute_);
-  if (hbytes) copy_d2h(hist_out, d + sbytes, hbytes, s_compute_);
-  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  host_call_stats(wall, device_kernel_ms(), p, sbytes + hbytes);
+  finish_placed(p, {{summary_out, sbytes}, {hist_out, hbytes}});
 }
 
 // ---- multi-target search --------------------------------------------------------------------------------
@@ -1415,31 +1364,21 @@ void HipEngine::solve_targets_device(const uint8_t* d_codes, const int64_t* d_of
   check_targets_call(h_starts, T);  // before any launch or change of state
   if (n > 0 && !d_out) throw Error("targets: no rows buffer");
   const TargetsCall tc{d_starts, h_starts, T, d_out};
-  run_profile(d_codes, d_offsets, h_offsets, n, 0, nullptr, stream, nullptr, 0, nullptr, &tc);  // n <= 0: no launch
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::Targets, nullptr, 0, 0, {}, {}, tc}, stream);  // n <= 0: no launch
 }
 
 void HipEngine::solve_targets(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T,
                               Result* out) {
   check_targets_call(starts, T);
-  finish_wire();
-  MOC_HIP_CHECK(hipSetDevice(device_));
-  if (n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const std::vector<int64_t> rebased =
-      upload_batch(codes, offsets, n, sizeof(Result) * static_cast<size_t>(n) * static_cast<size_t>(T));
-  targets_placed(placed_upload(rebased, n), starts, T, out, wall);
+  Placed p = place_host(codes, offsets, n, rows_bytes(n, T));
+  if (p.n > 0) targets_placed(p, starts, T, out);
 }
 
 // d_out: rows (n * T Result); starts travel with the plan buffer
-void HipEngine::targets_placed(const Placed& p, const int64_t* starts, int64_t T, Result* out, Stopwatch& wall) {
-  Slot& s = *slots_[0];
-  const size_t obytes = sizeof(Result) * static_cast<size_t>(p.n) * static_cast<size_t>(T);
-  solve_targets_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, static_cast<Result*>(s.d_out),
+void HipEngine::targets_placed(Placed& p, const int64_t* starts, int64_t T, Result* out) {
+  solve_targets_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, static_cast<Result*>(slots_[0]->d_out),
                        s_compute_);
-  copy_d2h(out, s.d_out, obytes, s_compute_);
-  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  host_call_stats(wall, device_kernel_ms(), p, obytes);
+  finish_placed(p, {{out, rows_bytes(p.n, T)}});
   stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1);
 }
 
@@ -1457,11 +1396,10 @@ void HipEngine::solve_targets_summary_device(const uint8_t* d_codes, const int64
                                              int64_t* d_summary, int32_t* d_hist, int32_t bins, int32_t lo,
                                              int32_t width, hipStream_t stream) {
   check_targets_summary(h_offsets, std::max<int64_t>(n, 0), h_starts, T, bins, width);  // before any launch or change of state
-  if (n > 0 && !d_summary) throw Error("summary: no summary buffer");
-  if (n > 0 && bins > 0 && !d_hist) throw Error("summary: bins > 0 need a hist buffer");
+  check_summary_buffers(n, d_summary, bins, d_hist);
   const SummaryCall sc{d_summary, bins > 0 ? d_hist : nullptr, bins, lo, width};
-  const TargetsCall tc{d_starts, h_starts, T, nullptr, &sc};
-  run_profile(d_codes, d_offsets, h_offsets, n, 0, nullptr, stream, nullptr, 0, nullptr, &tc);  // n <= 0: no launch
+  const TargetsCall tc{d_starts, h_starts, T, nullptr};
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::TargetsSummary, nullptr, 0, 0, {}, sc, tc}, stream);  // n <= 0: no launch
 }
 
 void HipEngine::solve_targets_summary(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
@@ -1469,30 +1407,18 @@ void HipEngine::solve_targets_summary(const uint8_t* codes, const int64_t* offse
                                       int32_t width) {
   check_targets_summary(offsets, std::max<int64_t>(n, 0), starts, T, bins, width);
   if (n > 0 && bins > 0 && !hist_out) throw Error("summary: bins > 0 need a hist buffer");
-  finish_wire();
-  MOC_HIP_CHECK(hipSetDevice(device_));
-  if (n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const size_t pairs = static_cast<size_t>(n) * static_cast<size_t>(T);
-  const std::vector<int64_t> rebased =
-      upload_batch(codes, offsets, n, sizeof(int64_t) * kSummaryCols * pairs + sizeof(int32_t) * static_cast<size_t>(bins) * pairs);
-  targets_summary_placed(placed_upload(rebased, n), starts, T, summary_out, hist_out, bins, lo, width, wall);
+  Placed p = place_host(codes, offsets, n, summary_bytes(n * T) + hist_bytes(n * T, bins));
+  if (p.n > 0) targets_summary_placed(p, starts, T, summary_out, hist_out, bins, lo, width);
 }
 
 // d_out: summary (7 n T int64) | hist (n T bins int32); starts travel with the plan buffer
-void HipEngine::targets_summary_placed(const Placed& p, const int64_t* starts, int64_t T, int64_t* summary_out,
-                                       int32_t* hist_out, int32_t bins, int32_t lo, int32_t width, Stopwatch& wall) {
-  Slot& s = *slots_[0];
-  const size_t pairs = static_cast<size_t>(p.n) * static_cast<size_t>(T);
-  const size_t sbytes = sizeof(int64_t) * kSummaryCols * pairs, hbytes = sizeof(int32_t) * static_cast<size_t>(bins) * pairs;
-  char* d = static_cast<char*>(s.d_out);
+void HipEngine::targets_summary_placed(Placed& p, const int64_t* starts, int64_t T, int64_t* summary_out,
+                                       int32_t* hist_out, int32_t bins, int32_t lo, int32_t width) {
+  const size_t sbytes = summary_bytes(p.n * T), hbytes = hist_bytes(p.n * T, bins);
+  char* d = static_cast<char*>(slots_[0]->d_out);
   solve_targets_summary_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, reinterpret_cast<int64_t*>(d),
                                reinterpret_cast<int32_t*>(d + sbytes), bins, lo, width, s_compute_);
-  copy_d2h(summary_out, d, sbytes, s_compute_);
-  if (hbytes) copy_d2h(hist_out, d + sbytes, hbytes, s_compute_);
-  MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  host_call_stats(wall, device_kernel_ms(), p, sbytes + hbytes);
+  finish_placed(p, {{summary_out, sbytes}, {hist_out, hbytes}});
   stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1);
 }
 
@@ -1548,13 +1474,8 @@ void HipEngine::report_device(const uint8_t* d_codes, const int64_t* d_offsets, 
 void HipEngine::report(const uint8_t* codes, const int64_t* offsets, int64_t n, int K, const Result* rows,
                        int32_t* counts, uint8_t* marks) {
   if (K < 1 || K > kMaxTopK) throw Error("report: K must be in 1.." + std::to_string(kMaxTopK));
-  finish_wire();
-  MOC_HIP_CHECK(hipSetDevice(device_));
-  if (n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const std::vector<int64_t> rebased = upload_batch(codes, offsets, n, report_out_bytes(n, K, marks ? offsets[n] - offsets[0] : 0));
-  report_placed(placed_upload(rebased, n), K, rows, counts, marks, wall);
+  Placed p = place_host(codes, offsets, n, n > 0 ? report_out_bytes(n, K, marks ? offsets[n] - offsets[0] : 0) : 0);
+  if (p.n > 0) report_placed(p, K, rows, counts, marks);
 }
 
 // d_out of a host report: counts (16-byte aligned at the start) | rows | marker bytes (K * letters, 0 without marks)
@@ -1563,20 +1484,19 @@ size_t HipEngine::report_out_bytes(int64_t n, int K, int64_t mark_letters) {
   return 16 * n_rows + sizeof(Result) * n_rows + std::max<size_t>(static_cast<size_t>(K) * static_cast<size_t>(mark_letters), 16);
 }
 
-void HipEngine::report_placed(const Placed& p, int K, const Result* rows, int32_t* counts, uint8_t* marks, Stopwatch& wall) {
-  Slot& s = *slots_[0];
+void HipEngine::report_placed(Placed& p, int K, const Result* rows, int32_t* counts, uint8_t* marks) {
   const int64_t n = p.n;
   const size_t n_rows = static_cast<size_t>(n) * static_cast<size_t>(K);
   const size_t cbytes = 16 * n_rows, rbytes = sizeof(Result) * n_rows;
   const size_t mbytes = marks ? static_cast<size_t>(K) * static_cast<size_t>(p.h_offsets[n] - p.h_offsets[0]) : 0;
-  char* d = static_cast<char*>(s.d_out);
+  char* d = static_cast<char*>(slots_[0]->d_out);
   copy_h2d(d + cbytes, rows, rbytes, s_compute_);
   report_device(p.d_codes, p.d_offsets, p.h_offsets, n, K, reinterpret_cast<const Result*>(d + cbytes),
                 reinterpret_cast<int32_t*>(d), marks ? reinterpret_cast<uint8_t*>(d + cbytes + rbytes) : nullptr, s_compute_);
   copy_d2h(counts, d, cbytes, s_compute_);
   if (mbytes) copy_d2h(marks, d + cbytes + rbytes, mbytes, s_compute_);
   MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
-  host_call_stats(wall, device_kernel_ms(), p, cbytes + mbytes);
+  host_call_stats(p, device_kernel_ms(), cbytes + mbytes);
   stats_.h2d_bytes += static_cast<int64_t>(rbytes);
 }
 
@@ -1708,13 +1628,22 @@ HipEngine::DecodedWire HipEngine::decode_wire_device(const WireBatch& b, const W
   return dw;
 }
 
-// A host wire batch on the device for a host form, slot 0's d_out grown to out_bytes.
 HipEngine::Placed HipEngine::place_wire(const WireBatch& b, size_t out_bytes) {
-  if (b.device) throw Error("the *_wire host forms take host batches; a device-resident one goes through decode_wire_device");
+  validate_wire(b);
+  Placed p;
+  if (b.n <= 0) return p;
+  p.wall.start();
+  require_host_batch(b);
   const DecodedWire dw = decode_wire_device(b, nullptr, s_compute_);
   Slot& s = *slots_[0];
   ensure(s.d_out, s.d_out_cap, out_bytes);
-  return Placed{dw.d_codes, dw.d_offsets, dw.h_offsets, dw.n, wire_h2d_, wire_kernels_};
+  p.d_codes = dw.d_codes;
+  p.d_offsets = dw.d_offsets;
+  p.h_offsets = dw.h_offsets;
+  p.n = dw.n;
+  p.h2d_bytes = wire_h2d_;
+  p.kernels = wire_kernels_;
+  return p;
 }
 
 void HipEngine::wire_profile_offsets(const WireBatch& b, int64_t* poffsets) const {
@@ -1727,20 +1656,15 @@ void HipEngine::wire_profile_offsets(const WireBatch& b, int64_t* poffsets) cons
 void HipEngine::solve_profile_wire(const WireBatch& b, ProfileEntry* prof_out, int64_t* poffsets_out) {
   wire_profile_offsets(b, poffsets_out);
   if (b.n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const size_t pbytes = sizeof(ProfileEntry) * static_cast<size_t>(poffsets_out[b.n]);
-  profile_placed(place_wire(b, std::max<size_t>(pbytes, 8)), prof_out, poffsets_out, wall);
+  Placed p = place_wire(b, std::max<size_t>(sizeof(ProfileEntry) * static_cast<size_t>(poffsets_out[b.n]), 8));
+  profile_placed(p, prof_out, poffsets_out);
 }
 
 void HipEngine::solve_topk_wire(const WireBatch& b, int K, Result* out, int64_t radius) {
-  if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  check_topk_k(K);
   check_peaks_radius(radius);
-  validate_wire(b);
-  if (b.n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  topk_placed(place_wire(b, sizeof(Result) * static_cast<size_t>(b.n) * static_cast<size_t>(K)), K, out, wall, radius);
+  Placed p = place_wire(b, rows_bytes(b.n, K));
+  if (p.n > 0) topk_placed(p, K, out, radius);
 }
 
 void HipEngine::solve_hits_wire(const WireBatch& b, int32_t min_score, const int32_t* thresholds, int64_t* hoffsets_out,
@@ -1752,78 +1676,46 @@ void HipEngine::solve_hits_wire(const WireBatch& b, int32_t min_score, const int
   rows_out.clear();
   hits_passes_ = 0;
   hoffsets_out[0] = 0;
-  if (b.n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const size_t n = static_cast<size_t>(b.n);
-  hits_placed(place_wire(b, sizeof(int64_t) * (n + 1) + sizeof(int32_t) * n), min_score, thresholds, hoffsets_out, rows_out,
-              max_rows_hint, wall, radius);
+  Placed p = place_wire(b, hits_index_bytes(b.n) + thresholds_bytes(b.n));
+  if (p.n > 0) hits_placed(p, min_score, thresholds, hoffsets_out, rows_out, max_rows_hint, radius);
 }
 
 void HipEngine::solve_summary_wire(const WireBatch& b, int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo,
                                    int32_t width) {
   if (!have_problem_) throw Error("HipEngine: summary before set_problem");
-  validate_wire(b);
-  if (b.device) throw Error("the *_wire host forms take host batches; a device-resident one goes through decode_wire_device");
-  if (b.n > 0) {  // the bound needs the lengths: the host's dense offsets of the batch, before anything is launched
-    std::vector<int64_t> dense(static_cast<size_t>(b.n) + 1);
-    wire_dense_offsets(b, dense.data());
-    check_summary(dense.data(), b.n, bins, width);
-  } else {
-    check_summary(nullptr, 0, bins, width);
-  }
+  check_summary(wire_check_offsets(b).data(), std::max<int64_t>(b.n, 0), bins, width);
   if (b.n > 0 && bins > 0 && !hist_out) throw Error("summary: bins > 0 need a hist buffer");
   finish_wire();
-  if (b.n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const size_t n = static_cast<size_t>(b.n);
-  summary_placed(place_wire(b, sizeof(int64_t) * kSummaryCols * n + sizeof(int32_t) * static_cast<size_t>(bins) * n),
-                 summary_out, hist_out, bins, lo, width, wall);
+  Placed p = place_wire(b, summary_bytes(b.n) + hist_bytes(b.n, bins));
+  if (p.n > 0) summary_placed(p, summary_out, hist_out, bins, lo, width);
 }
 
 void HipEngine::solve_targets_wire(const WireBatch& b, const int64_t* starts, int64_t T, Result* out) {
   check_targets_call(starts, T);
   validate_wire(b);
-  if (b.device) throw Error("the *_wire host forms take host batches; a device-resident one goes through decode_wire_device");
+  require_host_batch(b);
   finish_wire();
-  if (b.n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  targets_placed(place_wire(b, sizeof(Result) * static_cast<size_t>(b.n) * static_cast<size_t>(T)), starts, T, out, wall);
+  Placed p = place_wire(b, rows_bytes(b.n, T));
+  if (p.n > 0) targets_placed(p, starts, T, out);
 }
 
 void HipEngine::solve_targets_summary_wire(const WireBatch& b, const int64_t* starts, int64_t T, int64_t* summary_out,
                                            int32_t* hist_out, int32_t bins, int32_t lo, int32_t width) {
   check_targets_call(starts, T);
-  validate_wire(b);
-  if (b.device) throw Error("the *_wire host forms take host batches; a device-resident one goes through decode_wire_device");
-  if (b.n > 0) {  // the bound needs the lengths: the host's dense offsets of the batch, before anything is launched
-    std::vector<int64_t> dense(static_cast<size_t>(b.n) + 1);
-    wire_dense_offsets(b, dense.data());
-    check_targets_summary(dense.data(), b.n, starts, T, bins, width);
-  } else {
-    check_targets_summary(nullptr, 0, starts, T, bins, width);
-  }
+  check_targets_summary(wire_check_offsets(b).data(), std::max<int64_t>(b.n, 0), starts, T, bins, width);
   if (b.n > 0 && bins > 0 && !hist_out) throw Error("summary: bins > 0 need a hist buffer");
   finish_wire();
-  if (b.n <= 0) return;
-  Stopwatch wall;
-  wall.start();
-  const size_t pairs = static_cast<size_t>(b.n) * static_cast<size_t>(T);
-  targets_summary_placed(place_wire(b, sizeof(int64_t) * kSummaryCols * pairs + sizeof(int32_t) * static_cast<size_t>(bins) * pairs),
-                         starts, T, summary_out, hist_out, bins, lo, width, wall);
+  Placed p = place_wire(b, summary_bytes(b.n * T) + hist_bytes(b.n * T, bins));
+  if (p.n > 0) targets_summary_placed(p, starts, T, summary_out, hist_out, bins, lo, width);
 }
 
 void HipEngine::report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks) {
   if (K < 1 || K > kMaxTopK) throw Error("report: K must be in 1.." + std::to_string(kMaxTopK));
-  validate_wire(b);
-  if (b.n <= 0) return;
-  Stopwatch wall;
-  wall.start();
   // the marker bytes need the letter count before the decode: the batch's own first and end offsets
-  const int64_t letters = b.end_letter() - b.first_letter();
-  report_placed(place_wire(b, report_out_bytes(b.n, K, marks ? std::max<int64_t>(letters, 0) : 0)), K, rows, counts, marks, wall);
+  validate_wire(b);
+  const int64_t letters = b.n > 0 ? b.end_letter() - b.first_letter() : 0;
+  Placed p = place_wire(b, b.n > 0 ? report_out_bytes(b.n, K, marks ? std::max<int64_t>(letters, 0) : 0) : 0);
+  if (p.n > 0) report_placed(p, K, rows, counts, marks);
 }
 
 }  // namespace moc

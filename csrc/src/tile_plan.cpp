@@ -6,6 +6,7 @@
 #include <queue>
 #include <string>
 
+#include "moc/cpu_engine.hpp"
 #include "moc/problem.hpp"
 
 namespace moc {
@@ -404,6 +405,67 @@ std::vector<dev::WaveStart> profile_runs(const Config& c, const int64_t* offsets
   std::vector<int64_t> tcost;
   const int64_t total_tiles = tile_costs(c, offsets, nullptr, n, dev::tile_span(false, u), ntiles, tcost);
   return balanced_runs(ntiles, tcost, total_tiles, 0, 1, static_cast<int64_t>(c.num_cus) * c.tile_waves_per_cu);
+}
+
+ProfilePlan plan_profile(const Config& c, Semantics sem, const int64_t* offsets, int64_t n, bool chunked,
+                         int64_t entry_bytes, int64_t scratch_bytes, int64_t radius, const int64_t* target_starts, int64_t T,
+                         bool upload_targets) {
+  if (n >= (int64_t{1} << 31) - 1) throw Error("profile / top-K: more than 2^31 - 2 records in one call");
+  ProfilePlan pp;
+  pp.poff.resize(static_cast<size_t>(n) + 1);
+  pp.poff[0] = 0;
+  int64_t sum_l2 = 0, max_need = 1;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t L2 = offsets[i + 1] - offsets[i];
+    pp.poff[i + 1] = pp.poff[i] + candidate_offsets(c.L1, L2, sem);
+    sum_l2 += L2;
+    pp.max_l2 = std::max(pp.max_l2, L2);
+    max_need = std::max(max_need, dev::lanes_needed(c.L1, L2));
+    pp.cells += record_cells(c.L1, L2);
+  }
+  if (c.L1 >= (int64_t{1} << 30) || pp.max_l2 >= (int64_t{1} << 30))
+    throw Error("Seq1 / Seq2 lengths beyond 2^30 exceed the device engine's offset range");
+  // sub-tiles per wave tile, as the LUT tile kernel picks them, narrowed to the batch's widest offset range
+  pp.u = profile_u(c, sum_l2, n, max_need);
+  const std::vector<int64_t>& poff = pp.poff;
+  const int64_t cap_entries = std::max<int64_t>(1, scratch_bytes / entry_bytes);
+  for (int64_t r0 = 0; r0 < n;) {
+    int64_t r1 = r0 + 1;
+    if (!chunked)
+      r1 = n;
+    else
+      while (r1 < n && poff[r1 + 1] - poff[r0] <= cap_entries) ++r1;
+    ProfileChunk k;
+    k.r0 = r0;
+    k.r1 = r1;
+    k.entries = poff[r1] - poff[r0];
+    const std::vector<dev::WaveStart> runs = profile_runs(c, offsets + r0, r1 - r0, pp.u);
+    k.starts_at = pp.starts.size();
+    k.n_starts = runs.size();
+    pp.starts.insert(pp.starts.end(), runs.begin(), runs.end());
+    k.min_l2 = INT64_MAX;
+    int64_t max_c = 0;  // the chunk's longest profile
+    for (int64_t r = r0; r < r1; ++r) {
+      const int64_t L2 = offsets[r + 1] - offsets[r], C = poff[r + 1] - poff[r];
+      k.min_l2 = std::min(k.min_l2, L2);
+      k.max_l2 = std::max(k.max_l2, L2);
+      if (radius > 0 && C >= 1 && C <= bounds::kPeaksWaveEntries) k.any_short = 1;
+      max_c = std::max(max_c, C);
+    }
+    if (radius > 0 && max_c > bounds::kPeaksWaveEntries) {
+      k.max_tiles = static_cast<int32_t>((max_c + bounds::kPeaksTile - 1) / bounds::kPeaksTile);
+      k.lds_keys = static_cast<int32_t>(std::min<int64_t>(bounds::kPeaksTile, max_c) + 2 * std::min<int64_t>(radius, max_c - 1));
+    }
+    pp.max_entries = std::max(pp.max_entries, k.entries);
+    pp.max_records = std::max(pp.max_records, r1 - r0);
+    pp.chunks.push_back(k);
+    r0 = r1;
+  }
+  for (int64_t t = 0; target_starts && t < T; ++t) pp.max_target = std::max(pp.max_target, target_starts[t + 1] - target_starts[t]);
+  pp.starts_off = sizeof(int64_t) * pp.poff.size();
+  pp.targets_off = pp.starts_off + sizeof(dev::WaveStart) * pp.starts.size();  // 8-byte aligned: both parts are
+  pp.bytes = pp.targets_off + (target_starts && upload_targets ? sizeof(int64_t) * (static_cast<size_t>(T) + 1) : 0);
+  return pp;
 }
 
 ReportPlan plan_report(const int64_t* offsets, int64_t n, int K) {

@@ -1931,6 +1931,181 @@ void test_tile_plan_digests() {
   }
 }
 
+// ---- the profile family's chunk planner (plan::plan_profile) --------------------------------------------
+namespace {
+struct ProfilePlanCase {
+  const char* name;
+  PlanProblem p;
+  int cus;
+  Semantics sem;
+  std::vector<int64_t> off;
+  bool chunked;
+  int64_t entry_bytes, scratch_bytes, radius;
+  std::vector<int64_t> tstarts;  // empty: no targets
+  bool upload_targets;
+  uint64_t want;
+};
+
+std::vector<int64_t> offsets_of(std::initializer_list<int64_t> lengths) {
+  std::vector<int64_t> off{7};  // a chunk of a bigger batch: plans read differences only
+  for (int64_t L2 : lengths) off.push_back(off.back() + L2);
+  return off;
+}
+
+// Every Seq1 below has 400 letters under the reference semantics unless the case says otherwise: a record of L2 <
+// 400 letters has 400 - L2 entries, one of 400 has 1, a longer one none.
+std::vector<ProfilePlanCase> profile_plan_cases() {
+  const Semantics ref = Semantics::Reference, spec = Semantics::Spec;
+  const std::vector<int64_t> five = offsets_of({300, 300, 300, 300, 300});  // 100 entries each
+  return {
+      // unchunked: one chunk whatever the budget
+      {"unchunked", kLut400, 256, ref, plan_batch(10, 40, 1, 420, 400), false, 8, 8, 0, {}, false, 0xfa9934525466a1d2ull},
+      // a budget of exactly one record's entries; one entry short of two records; exactly two records
+      {"one_record", kLut400, 256, ref, five, true, 8, 8 * 100, 0, {}, false, 0x17d9684d3ecce6bfull},
+      {"short_of_two", kLut400, 256, ref, five, true, 8, 8 * 199, 0, {}, false, 0x17d9684d3ecce6bfull},
+      {"two_records", kLut400, 256, ref, five, true, 8, 8 * 200, 0, {}, false, 0xa6eac03de1ef4576ull},
+      // 10, 390, 5, 20 entries under a budget of 50: the second record gets a chunk alone
+      {"over_budget", kLut400, 8, ref, offsets_of({390, 10, 395, 380}), true, 8, 8 * 50, 0, {}, false, 0x63abc98497a46288ull},
+      // 0, 50, 0, 40, 0, 0 | 30, 0 entries under a budget of 100: records without candidates at a chunk's start,
+      // middle and end
+      {"zero_entries", kLut400, 256, ref, offsets_of({403, 350, 403, 360, 403, 403, 370, 403}), true, 8, 8 * 100, 0, {}, false,
+       0xa80edb7cca84d59dull},
+      // peak marks beside the entries: a chunk whose longest profile has kPeaksWaveEntries entries (64, 20) and one
+      // with one more (65, 10); then a radius past the profile (clamped to its length) and the spec semantics' extra entry
+      {"peaks_64_65", kLut400, 256, ref, offsets_of({336, 380, 335, 390}), true, 9, 9 * 100, 3, {}, false, 0x292490bd97a19c11ull},
+      {"peaks_radius_max", kLut400, 256, spec, offsets_of({336, 380, 335, 390}), true, 9, 9 * 100, 2048, {}, false,
+       0xcf110f0c2066d480ull},
+      // targets of 100, 150 and 150 letters: every record is longer than the longest target (the group input clamps
+      // to 0); then slices of up to 130 entries, the starts already on the device
+      {"targets_clamped", kLut400, 256, ref, offsets_of({200, 180, 160}), true, 8, 8 * 700, 0, {0, 100, 250, 400}, true,
+       0x2b7d9528c527e5b2ull},
+      {"targets_slices", kLut400, 8, spec, offsets_of({20, 100, 140, 60}), true, 8, 8 * 400, 0, {0, 100, 250, 400}, false,
+       0x54048abff964691full},
+      // seeded batches through small budgets: mixed lengths, one CU, a tile16-capable Seq1 (the profile stays on the LUT)
+      {"random_400", kLut400, 8, spec, plan_batch(11, 200, 1, 420, 400), true, 8, 4096, 0, {}, false, 0x8a03619396f847a6ull},
+      {"random_400_peaks", kLut400, 1, ref, plan_batch(12, 90, 1, 399), true, 9, 9 * 700, 2, {}, false, 0x017e831d40639eb3ull},
+      {"random_1489", kWhole1489, 256, ref, plan_batch(13, 33, 1300, 1489), true, 8, 1 << 10, 0, {}, false, 0x6debc8424f1dd488ull},
+  };
+}
+
+uint64_t profile_plan_digest(const plan::ProfilePlan& pp, const int64_t* off) {
+  uint64_t h = 14695981039346656037ull;
+  h = fnv1a(h, static_cast<int64_t>(pp.poff.size()));
+  for (int64_t v : pp.poff) h = fnv1a(h, v);
+  h = fnv1a(h, pp.u);
+  h = fnv1a(h, static_cast<int64_t>(pp.chunks.size()));
+  for (const plan::ProfileChunk& k : pp.chunks) {
+    int64_t min_l2 = INT64_MAX;
+    for (int64_t r = k.r0; r < k.r1; ++r) min_l2 = std::min(min_l2, off[r + 1] - off[r]);
+    for (int64_t v : {k.r0, k.r1, static_cast<int64_t>(k.starts_at), static_cast<int64_t>(k.n_starts), int64_t{k.any_short},
+                      int64_t{k.max_tiles}, int64_t{k.lds_keys}, std::max<int64_t>(pp.max_target - k.min_l2, 0)})
+      h = fnv1a(h, v);
+    CHECK(k.min_l2 == min_l2);
+  }
+  h = runs_digest(h, pp.starts);
+  for (size_t v : {pp.starts_off, pp.targets_off, pp.bytes}) h = fnv1a(h, static_cast<int64_t>(v));
+  return h;
+}
+}  // namespace
+
+// The refactor that moved the chunk planning out of HipEngine::run_profile must not change a plan: digests (FNV-1a
+// over poff, u, every chunk's r0, r1, starts_at, n_starts, any_short, max_tiles, lds_keys and its targets group
+// input max(max_target - min_l2, 0), the starts and the three plan-buffer offsets) recorded from commit f39dbf6's
+// HipEngine::run_profile, its planning lines compiled verbatim in a scratch harness and fed these same inputs. The
+// shape of every plan is checked directly as well.
+void test_plan_profile() {
+  int at = 0;
+  for (const ProfilePlanCase& k : profile_plan_cases()) {
+    const plan::Config c = with(plan_problem(k.p), k.cus);
+    const int64_t n = static_cast<int64_t>(k.off.size()) - 1, T = static_cast<int64_t>(k.tstarts.size()) - 1;
+    const int64_t* off = k.off.data();
+    const plan::ProfilePlan pp = plan::plan_profile(c, k.sem, off, n, k.chunked, k.entry_bytes, k.scratch_bytes, k.radius,
+                                                    k.tstarts.empty() ? nullptr : k.tstarts.data(), std::max<int64_t>(T, 0),
+                                                    k.upload_targets);
+    const uint64_t got = profile_plan_digest(pp, off);
+    CHECK(got == k.want);
+    if (got != k.want) std::fprintf(stderr, "  plan_profile digest %d (%s): 0x%016llxull\n", at, k.name, static_cast<unsigned long long>(got));
+    ++at;
+    // ---- shape
+    CHECK(static_cast<int64_t>(pp.poff.size()) == n + 1 && pp.poff[0] == 0);
+    int64_t cells = 0, max_l2 = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      CHECK(pp.poff[i + 1] - pp.poff[i] == candidate_offsets(c.L1, off[i + 1] - off[i], k.sem));
+      cells += record_cells(c.L1, off[i + 1] - off[i]);
+      max_l2 = std::max(max_l2, off[i + 1] - off[i]);
+    }
+    CHECK(pp.cells == cells && pp.max_l2 == max_l2);
+    const int64_t budget = std::max<int64_t>(1, k.scratch_bytes / k.entry_bytes);
+    if (!k.chunked) CHECK(pp.chunks.size() == 1);
+    int64_t next = 0, max_entries = 0, max_records = 0;
+    size_t next_start = 0;
+    for (const plan::ProfileChunk& ch : pp.chunks) {
+      CHECK(ch.r0 == next && ch.r1 > ch.r0 && ch.r1 <= n);  // the chunks tile [0, n) in order
+      next = ch.r1;
+      CHECK(ch.entries == pp.poff[ch.r1] - pp.poff[ch.r0]);
+      if (k.chunked && ch.r1 - ch.r0 > 1) CHECK(ch.entries <= budget);
+      // greedy: the next record would not have fitted
+      if (k.chunked && ch.r1 < n) CHECK(pp.poff[ch.r1 + 1] - pp.poff[ch.r0] > budget);
+      max_entries = std::max(max_entries, ch.entries);
+      max_records = std::max(max_records, ch.r1 - ch.r0);
+      CHECK(ch.starts_at == next_start && ch.n_starts >= 2 && ch.starts_at + ch.n_starts <= pp.starts.size());
+      next_start = ch.starts_at + ch.n_starts;
+      // the profile kernel walks a chunk's runs like the LUT tile kernel walks a batch's
+      const std::vector<dev::WaveStart> s(pp.starts.begin() + static_cast<int64_t>(ch.starts_at),
+                                          pp.starts.begin() + static_cast<int64_t>(ch.starts_at + ch.n_starts));
+      plan::TilePlan tp;
+      tp.u = pp.u;
+      check_plan_shape(c, off + ch.r0, nullptr, ch.r1 - ch.r0, tp, s);
+      Tiles seen = walk_plan(c, off + ch.r0, nullptr, ch.r1 - ch.r0, tp, s);
+      std::sort(seen.begin(), seen.end());
+      CHECK(seen == plan_tiles(c, off + ch.r0, nullptr, ch.r1 - ch.r0, tp));
+      if (k.radius <= 0) CHECK(ch.any_short == 0 && ch.max_tiles == 0 && ch.lds_keys == 0);
+      CHECK(ch.lds_keys <= bounds::kPeaksTile + 2 * bounds::kPeaksMaxRadius);
+    }
+    CHECK(next == n && next_start == pp.starts.size());
+    CHECK(pp.max_entries == max_entries && pp.max_records == max_records);
+    CHECK(pp.starts_off == 8 * pp.poff.size() && pp.targets_off == pp.starts_off + sizeof(dev::WaveStart) * pp.starts.size());
+    CHECK(pp.bytes == pp.targets_off + (k.upload_targets ? 8 * k.tstarts.size() : 0));
+  }
+  // the cases' own edges, read off the plans
+  auto plan_of = [&](const char* name) {
+    for (const ProfilePlanCase& k : profile_plan_cases())
+      if (!std::strcmp(k.name, name))
+        return plan::plan_profile(with(plan_problem(k.p), k.cus), k.sem, k.off.data(), static_cast<int64_t>(k.off.size()) - 1,
+                                  k.chunked, k.entry_bytes, k.scratch_bytes, k.radius, k.tstarts.empty() ? nullptr : k.tstarts.data(),
+                                  std::max<int64_t>(static_cast<int64_t>(k.tstarts.size()) - 1, 0), k.upload_targets);
+    CHECK(false);
+    return plan::ProfilePlan{};
+  };
+  CHECK(plan_of("one_record").chunks.size() == 5 && plan_of("short_of_two").chunks.size() == 5);
+  CHECK(plan_of("two_records").chunks.size() == 3 && plan_of("two_records").max_records == 2);
+  {
+    const plan::ProfilePlan pp = plan_of("over_budget");
+    CHECK(pp.chunks.size() == 3 && pp.chunks[1].r0 == 1 && pp.chunks[1].r1 == 2 && pp.chunks[1].entries == 390 && pp.max_entries == 390);
+  }
+  {
+    const plan::ProfilePlan pp = plan_of("zero_entries");
+    CHECK(pp.chunks.size() == 2 && pp.chunks[0].r1 == 6 && pp.chunks[0].entries == 90 && pp.chunks[1].entries == 30);
+  }
+  {
+    const plan::ProfilePlan pp = plan_of("peaks_64_65");
+    CHECK(pp.chunks.size() == 2);
+    CHECK(pp.chunks[0].any_short == 1 && pp.chunks[0].max_tiles == 0 && pp.chunks[0].lds_keys == 0);  // 64 entries: the wave kernel's
+    CHECK(pp.chunks[1].any_short == 1 && pp.chunks[1].max_tiles == 1 && pp.chunks[1].lds_keys == 65 + 2 * 3);
+  }
+  {
+    const plan::ProfilePlan pp = plan_of("targets_clamped");
+    CHECK(pp.max_target == 150 && pp.chunks.size() == 1 && pp.chunks[0].min_l2 == 160);
+    CHECK(bounds::targets_group(std::max<int64_t>(pp.max_target - pp.chunks[0].min_l2, 0)) == bounds::targets_group(0));
+  }
+  // the limits throw from the planner, with the engine's texts
+  const plan::Config& c = plan_problem(kLut400);
+  CHECK(throws([&] { plan::plan_profile(c, Semantics::Reference, nullptr, (int64_t{1} << 31) - 1, true, 8, 64, 0); },
+               "more than 2^31 - 2 records"));
+  const int64_t huge[] = {0, int64_t{1} << 30};
+  CHECK(throws([&] { plan::plan_profile(c, Semantics::Reference, huge, 1, true, 8, 64, 0); }, "beyond 2^30"));
+}
+
 int main(int argc, char** argv) {
   const std::vector<std::pair<const char*, std::function<void()>>> tests = {
       {"score_table", test_score_table}, {"parser", test_parser},     {"stream_reader", test_stream_reader},
@@ -1945,7 +2120,8 @@ int main(int argc, char** argv) {
       {"tile16_key32_replay", test_tile16_key32_replay}, {"tile16_i16_replay", test_tile16_i16_replay},
       {"profile16_lds_bytes", test_profile16_lds_bytes}, {"watchdog", test_watchdog},
       {"tile_plan_cases", test_tile_plan_cases}, {"tile_plan_digests", test_tile_plan_digests},
-      {"plan_chunk_threaded", test_plan_chunk_threaded}, {"plan_layout", test_plan_layout}};
+      {"plan_chunk_threaded", test_plan_chunk_threaded}, {"plan_layout", test_plan_layout},
+      {"plan_profile", test_plan_profile}};
   for (const auto& t : tests) {
     if (argc > 1 && !std::strstr(t.first, argv[1])) continue;  // test_core NAME: only the tests named *NAME*
     const int before = g_failed;
