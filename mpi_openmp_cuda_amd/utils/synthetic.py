@@ -98,7 +98,8 @@ def make_planted(L1: int, L2: int, weights, positions=None, seed: int = 0):
     0 .. L1 - L2), on a Seq1 without equal neighbours: a chosen offset is the winner. Returns (problem,
     positions). With W1 > 0 the expected result of record i is (W1 * L2, p_i, 0) under either semantics for
     p_i <= L1 - L2 - 1; for p_i = L1 - L2 under the spec semantics only (the reference semantics never try
-    that offset: an oracle decides the record)."""
+    that offset: an oracle decides the record). The winner's k is always 0 here: make_planted_k,
+    make_planted_k_ties and make_extreme_mutants plant a mutation point."""
     if not 0 < L2 <= L1:
         raise ValueError("need 0 < L2 <= L1")
     rng = np.random.default_rng(seed)
@@ -215,3 +216,145 @@ def make_extreme(L1: int, l2_min: int, l2_max: int, weights, copies: int = 1, se
     np.cumsum(lengths, out=offsets[1:])
     codes = np.concatenate([recs[i] for i in order]) if len(order) else np.zeros(0, np.uint8)
     return Problem(Weights.of(weights), s1, codes, offsets)
+
+
+# ---- planted mutation points ---------------------------------------------------------------------------
+# B J O U X Z: in no conservation group (models/scoring.py), so against any other letter they score -W4
+NEUTRAL = tuple(ord(c) - 64 for c in "BJOUXZ")
+K_FAMILIES = ("k", "inside", "own", "shadow", "extreme")
+
+
+def _skipped(seq1: np.ndarray, p: int, L2: int, k: int) -> np.ndarray:
+    """Seq1[p : p + k] ++ Seq1[p + k + 1 : p + L2 + 1]: L2 letters of Seq1 from p with the letter at p + k skipped."""
+    return np.concatenate([seq1[p:p + k], seq1[p + k + 1:p + L2 + 1]]).astype(np.uint8)
+
+
+def _neutral(rng, seq1: np.ndarray, q: int) -> int:
+    """A neutral letter that differs from Seq1[q] and Seq1[q + 1], the two letters a record letter meets on the
+    diagonals p and p + 1: it scores -W4 on both, so its step adds 0 to the diagonal difference D."""
+    right = int(seq1[q + 1]) if q + 1 < seq1.shape[0] else 0
+    free = [c for c in NEUTRAL if c != int(seq1[q]) and c != right]
+    return int(free[int(rng.integers(0, len(free)))])
+
+
+def _check_k_case(L1: int, p: int, L2: int, k: int):
+    if not (L2 >= 2 and 1 <= k <= L2 - 1 and 0 <= p and p + L2 + 1 <= L1):
+        raise ValueError(f"case (p={p}, L2={L2}, k={k}) on L1={L1}: need L2 >= 2, 1 <= k <= L2 - 1, p + L2 + 1 <= L1")
+
+
+def make_planted_k(L1: int, cases, weights, seed: int = 0):
+    """A problem with one record per (p, L2, k) in ``cases`` (1 <= k <= L2 - 1, p + L2 + 1 <= L1; lengths may
+    differ) on a Seq1 without equal neighbours: the record is Seq1[p : p + L2 + 1] with the letter at p + k
+    skipped, so its letters before k match on diagonal p and the rest on diagonal p + 1, and the mutant k at offset
+    p is the only candidate with the full score. The expected row is (W1 * L2, p, k) under either semantics
+    (planted_k_expected). Returns (problem, cases as an int64 [n, 3] array)."""
+    rng = np.random.default_rng(seed)
+    seq1 = seq_no_equal_neighbours(rng, L1)
+    cases = np.asarray(cases, dtype=np.int64).reshape(-1, 3)
+    for p, L2, k in cases:
+        _check_k_case(L1, int(p), int(L2), int(k))
+    return _records(weights, seq1, [_skipped(seq1, int(p), int(L2), int(k)) for p, L2, k in cases]), cases
+
+
+def make_planted_k_ties(L1: int, family: str, cases, weights, seed: int = 0):
+    """Ties that the mutation point's tie-break decides (first k with the largest diagonal difference D; k = 0
+    wins a tie with D(L2); the smaller offset wins). One record per case; returns (problem, cases as int64 rows).
+
+    ``inside``: (p, L2, j, k), 1 <= j < k: make_planted_k's record with its letters j .. k - 1 replaced by neutral
+      ones (_neutral), so every k' in j .. k reaches the same score: the row is
+      (W1 (L2 - (k - j)) - W4 (k - j), p, j).
+    ``own``: (p, L2, k): Seq1[p : p + k] and then L2 - k neutral letters: D(k') = D(L2) for every k' >= k, the
+      un-mutated candidate wins: (W1 k - W4 (L2 - k), p, 0) — while the prefix is long enough to beat chance
+      elsewhere, so k >= max(5, L2 / 2) is required.
+    ``shadow``: (p, L2), p >= 1: Seq1[p - 1] is set to Seq1[p] (the only equal neighbours; the case is refused if
+      Seq1[p - 2] or Seq1[p + 1] equals them) and the record is Seq1[p : p + L2]: (p - 1, k = 1) and (p, 0) both
+      score W1 L2 and the smaller offset wins: (W1 L2, p - 1, 1). p = L1 - L2 is allowed: the reference semantics
+      never try that offset, but they try its shadow."""
+    if family not in ("inside", "own", "shadow"):
+        raise ValueError(f"unknown tie family {family!r}")
+    rng = np.random.default_rng(seed)
+    seq1 = seq_no_equal_neighbours(rng, L1)
+    width = {"inside": 4, "own": 3, "shadow": 2}[family]
+    cases = np.asarray(cases, dtype=np.int64).reshape(-1, width)
+    recs = []
+    if family == "inside":
+        for p, L2, j, k in (tuple(int(v) for v in c) for c in cases):
+            _check_k_case(L1, p, L2, k)
+            if not 1 <= j < k:
+                raise ValueError(f"case (p={p}, L2={L2}, j={j}, k={k}): need 1 <= j < k")
+            r = _skipped(seq1, p, L2, k)
+            for i in range(j, k):
+                r[i] = _neutral(rng, seq1, p + i)
+            recs.append(r)
+    elif family == "own":
+        for p, L2, k in (tuple(int(v) for v in c) for c in cases):
+            _check_k_case(L1, p, L2, k)
+            if k < max(5, (L2 + 1) // 2):
+                raise ValueError(f"case (p={p}, L2={L2}, k={k}): the matching prefix needs k >= max(5, L2 / 2)")
+            r = seq1[p:p + L2].copy()
+            for i in range(k, L2):
+                r[i] = _neutral(rng, seq1, p + i)
+            recs.append(r)
+    else:
+        for p, L2 in (tuple(int(v) for v in c) for c in cases):
+            if not (L2 >= 2 and 1 <= p and p + L2 <= L1):
+                raise ValueError(f"case (p={p}, L2={L2}) on L1={L1}: need L2 >= 2, p >= 1 and p + L2 <= L1")
+            seq1[p - 1] = seq1[p]
+        for p, L2 in (tuple(int(v) for v in c) for c in cases):
+            if seq1[p - 1] != seq1[p] or (p >= 2 and seq1[p - 2] == seq1[p]) or seq1[p + 1] == seq1[p]:
+                raise ValueError(f"case (p={p}, L2={L2}): a third equal letter next to Seq1[{p - 1}] == Seq1[{p}]")
+            recs.append(seq1[p:p + L2].copy())
+        equal = np.nonzero(seq1[1:] == seq1[:-1])[0] + 1
+        assert sorted(equal.tolist()) == sorted({int(p) for p, _ in cases}), "shadow ties: stray equal neighbours"
+    return _records(weights, seq1, recs), cases
+
+
+def make_extreme_mutants(L1: int, l2_min: int, l2_max: int, weights, copies: int = 1, seed: int = 0):
+    """make_extreme's Seq1 "AZAZ..." with records that are pieces of it with one letter skipped (make_planted_k's
+    construction) at p in {0, 1, 5} and k in {1, 2, L2 / 2, L2 - 2, L2 - 1}, for the lengths make_extreme uses,
+    shuffled ``copies`` times. Every letter matches on the mutant's path and, Seq1 having period 2, at offset
+    p mod 2 already: the row is (W1 L2, p mod 2, k). With W1 = W4 = W the winner's D(k) = 2 W k: at k = L2 - 1 one
+    step under the 2 W L2 the kernels' bounds are set by, in a key whose k field holds its smallest value. A length
+    no skipped piece fits (L2 + 1 > L1) gets the exact piece at 0 (k = 0), so that the batch keeps make_extreme's
+    length range and with it the kernel form. Returns (problem, cases as int64 rows (p, L2, k) in record order)."""
+    rng = np.random.default_rng(seed)
+    s1 = np.where(np.arange(L1) % 2 == 0, A, Z).astype(np.uint8)
+    recs, rows = [], []
+    for L2 in sorted({l2_min, l2_max, (l2_min + l2_max) // 2, max(l2_min, l2_max - 1)}):
+        ks = sorted({k for k in (1, 2, L2 // 2, L2 - 2, L2 - 1) if 1 <= k <= L2 - 1})
+        fits = [(p, k) for p in (0, 1, 5) for k in ks if p + L2 + 1 <= L1]
+        for p, k in fits:
+            recs.append(_skipped(s1, p, L2, k))
+            rows.append((p, L2, k))
+        if not fits:
+            if not 0 < L2 <= L1:
+                raise ValueError(f"records of {L2} letters do not fit a Seq1 of {L1}")
+            recs.append(s1[:L2].copy())
+            rows.append((0, L2, 0))
+    order = np.concatenate([rng.permutation(len(recs)) for _ in range(copies)])
+    return _records(weights, s1, [recs[i] for i in order]), np.array([rows[i] for i in order], dtype=np.int64)
+
+
+def planted_k_expected(problem: Problem, cases, family: str = "k") -> np.ndarray:
+    """The int32 (score, n, k) rows the constructions above claim, under either semantics: ``family`` is "k"
+    (make_planted_k), "inside" / "own" / "shadow" (make_planted_k_ties) or "extreme" (make_extreme_mutants)."""
+    if family not in K_FAMILIES:
+        raise ValueError(f"unknown family {family!r}")
+    w1, _, _, w4 = problem.weights.as_list()
+    c = np.asarray(cases, dtype=np.int64)
+    c = c.reshape(-1, {"inside": 4, "shadow": 2}.get(family, 3))
+    if c.shape[0] != problem.n:
+        raise ValueError("one case per record")
+    p, L2 = c[:, 0], c[:, 1]
+    if family == "k":
+        rows = (w1 * L2, p, c[:, 2])
+    elif family == "inside":
+        span = c[:, 3] - c[:, 2]
+        rows = (w1 * (L2 - span) - w4 * span, p, c[:, 2])
+    elif family == "own":
+        rows = (w1 * c[:, 2] - w4 * (L2 - c[:, 2]), p, np.zeros_like(p))
+    elif family == "shadow":
+        rows = (w1 * L2, p - 1, np.ones_like(p))
+    else:
+        rows = (w1 * L2, p % 2, c[:, 2])
+    return np.stack(rows, axis=1).astype(np.int32)

@@ -2,15 +2,16 @@
 unique best one, or two chosen offsets tie, so that an engine dropping one offset is caught at that offset
 and not with the odds of a random problem. CPU tier: the builders against the pure-Python prefix oracle, then
 the CPU engine (the GPU tier's oracle) at every offset around its vector widths, and its context-parallel
-keys over more parts than a record has tiles."""
+keys over more parts than a record has tiles. Every winner planted by those two builders has k = 0; make_planted_k
+plants the mutation point too (here against the oracle; tests/test_planted_k.py has the rest)."""
 import numpy as np
 import pytest
 
 from mpi_openmp_cuda_amd import Semantics, decode_keys, search_cpu, search_keys_cpu
 from mpi_openmp_cuda_amd.models.reference import prefix_oracle, solve_problem
 from mpi_openmp_cuda_amd.ops.align import as_triples
-from mpi_openmp_cuda_amd.utils.synthetic import (differing, make_planted, make_planted_ties, planted_expected,
-                                                 seq_no_equal_neighbours)
+from mpi_openmp_cuda_amd.utils.synthetic import (differing, make_planted, make_planted_k, make_planted_ties,
+                                                 planted_expected, planted_k_expected, seq_no_equal_neighbours)
 
 W = (10, 2, 3, 4)
 SEMS = [Semantics.REFERENCE, Semantics.SPEC]
@@ -124,3 +125,24 @@ def test_cpu_keys_combine_over_parts(L1, L2, parts, sem):
     got = as_triples(decode_keys(keys, prob))
     want = planted_expected(prob, pos, sem)
     assert np.array_equal(got, want), differing(got, want, pos)
+
+
+# every winner above has k = 0. make_planted_k skips one letter of the Seq1 segment, so (p, k) wins: every p and k
+@pytest.mark.parametrize("w", [W, (200, 10, 10, 10), (300, 300, 1, 1)], ids=["w", "w_i16", "w_dpp"])
+@pytest.mark.parametrize("L1,L2", [(71, 8), (72, 40), (90, 33), (120, 70), (40, 2), (40, 3)])
+def test_planted_k_matches_prefix_oracle(L1, L2, w):
+    cases = [(p, L2, k) for p in range(L1 - L2) for k in range(1, L2)]
+    # (two letters find a rival elsewhere by chance in most Seq1s: a seed whose Seq1 holds none)
+    prob, cases = make_planted_k(L1, cases, w, seed=6 if L2 == 2 else L1 + L2)
+    assert prob.n == (L1 - L2) * (L2 - 1) and (prob.seq1[1:] != prob.seq1[:-1]).all()
+    want = planted_k_expected(prob, cases)
+    assert np.array_equal(want, np.stack([np.full(prob.n, w[0] * L2), cases[:, 0], cases[:, 2]], axis=1))
+    assert (want[:, 2] >= 1).all()
+    for sem in SEMS:
+        oracle = solve_problem(prob, sem, oracle=prefix_oracle)
+        assert np.array_equal(oracle, want), differing(oracle, want, cases[:, 0])
+        for threads in (1, 3):
+            got = as_triples(search_cpu(prob, sem, threads=threads))
+            assert np.array_equal(got, want), differing(got, want, cases[:, 0])
+    with pytest.raises(ValueError):
+        make_planted_k(L1, [(L1 - L2, L2, 1)], w)  # the final offset has no letter behind it to skip to
