@@ -358,3 +358,181 @@ def planted_k_expected(problem: Problem, cases, family: str = "k") -> np.ndarray
     else:
         rows = (w1 * L2, p % 2, c[:, 2])
     return np.stack(rows, axis=1).astype(np.int32)
+
+
+# ---- wire-decoder cases ---------------------------------------------------------------------------------
+# Inputs for the decoders of the wire formats (docs/WIRE_FORMATS.md): P33 fields on every digit carry and at every
+# bit phase, every base-6 octet, every narrow length field, as problems whose result rows read the decoded letters
+# and lengths back (tests/decoder_cases.py holds the case lists, tests/test_decoder_cases.py proves the claims).
+P33_P = 26 ** 4          # a P33 field x = A * 26^4 + B: the device decoders split it there
+P33_TOP = 26 ** 7 - 1    # the largest field: seven letters 'Z'
+OCTETS = 6 ** 8          # base-6 octet values
+OCTET_SLICE = 6 ** 7     # octets that share a top digit
+
+
+def p33_boundary_fields() -> np.ndarray:
+    """The uint64 P33 field values on a digit carry, 41 230 of them: q P - 1 and q P for q = 1 .. 26^3 - 1 (every
+    carry into digits 4..6); A P + 676 m - 1 and A P + 676 m for m = 1..675 and A in {0, 8788, 26^3 - 1} (every carry
+    into digits 2..3, at the smallest, a middle and the largest upper half); v, 676 v and P v for v = 0..675 (every
+    digit pair at each of the three pair positions); 0 and 26^7 - 1."""
+    q = np.arange(1, 26 ** 3, dtype=np.uint64) * np.uint64(P33_P)
+    parts = [np.stack([q - np.uint64(1), q], axis=1).reshape(-1)]
+    m = np.arange(1, 676, dtype=np.uint64) * np.uint64(676)
+    for a in (0, 8788, 26 ** 3 - 1):
+        at = np.uint64(a * P33_P) + m
+        parts.append(np.stack([at - np.uint64(1), at], axis=1).reshape(-1))
+    v = np.arange(676, dtype=np.uint64)
+    parts.append(np.stack([v, v * np.uint64(676), v * np.uint64(P33_P)], axis=1).reshape(-1))
+    parts.append(np.array([0, P33_TOP], dtype=np.uint64))
+    return np.concatenate(parts)
+
+
+def p33_phase_fields() -> np.ndarray:
+    """2 x 32 runs of 64 consecutive uint64 fields (4096 fields): 26^7 - 1 at field f of its run and 0 everywhere else,
+    for f = 0..31, then the inverse, 0 at field f and 26^7 - 1 everywhere else. A run is 64 fields, so field f of a
+    run lies at bit phase 33 f mod 32 = f: the largest and the smallest field at each of the 32 phases beside the
+    opposite fill, where a mask or shift that leaks shows."""
+    runs = np.zeros((2, 32, 64), dtype=np.uint64)
+    runs[1] = P33_TOP
+    f = np.arange(32)
+    runs[0, f, f] = P33_TOP
+    runs[1, f, f] = 0
+    return runs.reshape(-1)
+
+
+def p33_field_letters(fields) -> np.ndarray:
+    """The uint8 letter codes of P33 fields, seven per field: digit j of the field's value in base 26, plus 1, digit 0
+    first."""
+    x = np.asarray(fields, dtype=np.uint64)
+    if x.size and int(x.max()) > P33_TOP:
+        raise ValueError("a P33 field is below 26^7")
+    digits = (x[:, None] // (np.uint64(26) ** np.arange(7, dtype=np.uint64))[None, :]) % np.uint64(26)
+    return (digits + np.uint64(1)).astype(np.uint8).reshape(-1)
+
+
+READOUT_WEIGHTS = (1, 0, 0, 0)
+
+
+def make_letter_readout(letters):
+    """One-letter records that read a decoded letter stream back: Seq1 = "AB...ZA" (27 letters: the second 'A' gives
+    the reference semantics, which never try the last offset, an offset for 'Z'), weights (1, 0, 0, 0), record i the
+    single letter ``letters[i]``. Its only matching offset below 26 is letters[i] - 1 ('A' also matches at 26, the
+    smaller offset wins) and a record of one letter has no mutant, so the row is (1, letters[i] - 1, 0) under either
+    semantics. All lengths are 1: base 6 above base 1. Returns (problem, rows)."""
+    letters = np.ascontiguousarray(letters, dtype=np.uint8)
+    if letters.size and (letters.min() < 1 or letters.max() > 26):
+        raise ValueError("letter codes are 1..26")
+    seq1 = np.concatenate([np.arange(1, 27), [1]]).astype(np.uint8)
+    n = letters.shape[0]
+    prob = Problem(Weights.of(READOUT_WEIGHTS), seq1, letters, np.arange(n + 1, dtype=np.int64))
+    rows = np.stack([np.ones(n, np.int64), letters.astype(np.int64) - 1, np.zeros(n, np.int64)], axis=1)
+    return prob, rows.astype(np.int32)
+
+
+def octet_digits(values) -> np.ndarray:
+    """The 8 base-6 digits of every octet value, digit 0 first: int64 [n, 8]."""
+    v = np.asarray(values, dtype=np.int64)
+    return (v[:, None] // (6 ** np.arange(8, dtype=np.int64))[None, :]) % 6
+
+
+def _copies(weights, seq1: np.ndarray, lengths: np.ndarray, starts: np.ndarray) -> Problem:
+    """Record i = ``lengths[i]`` letters of Seq1 (read cyclically) from ``starts[i]``."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    offsets = np.zeros(lengths.shape[0] + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    within = np.arange(int(offsets[-1]), dtype=np.int64) - np.repeat(offsets[:-1], lengths)
+    at = np.repeat(np.asarray(starts, dtype=np.int64), lengths) + within
+    return Problem(Weights.of(weights), seq1, seq1[at % seq1.shape[0]], offsets)
+
+
+OCTET_WEIGHTS = (3, 1, 2, 4)
+
+
+def make_length_copies(lengths, seed=0):
+    """One record per entry of ``lengths`` (each at most 25) that reads its own length back: Seq1 is the 26 distinct
+    letters "AB...Z", record i a copy of Seq1[p_i : p_i + L_i] with a seeded p_i <= 25 - L_i, weights (3, 1, 2, 4). No
+    other offset and no mutant matches every letter, and p_i + L_i < 26 is an offset both semantics try, so the row is
+    (3 L_i, p_i, 0) — a wrong length breaks the score, and every later start of its tile with it. Returns (problem,
+    rows)."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    if lengths.size and (lengths.min() < 1 or lengths.max() > 25):
+        raise ValueError("lengths of 1..25")
+    p = np.random.default_rng(seed).integers(0, 26 - lengths)  # 0 .. 25 - L
+    prob = _copies(OCTET_WEIGHTS, np.arange(1, 27, dtype=np.uint8), lengths, p)
+    rows = np.stack([OCTET_WEIGHTS[0] * lengths, p, np.zeros_like(p)], axis=1).astype(np.int32)
+    return prob, rows
+
+
+def make_octet_copies(top: int, rot: int = 0, base: int = 1, seed: int = 0):
+    """Every base-6 octet with top digit ``top`` as record lengths: ``base`` + digit j, j = 0..7, of every value in
+    [top 6^7, (top + 1) 6^7), after 8 ``rot`` records of ``base`` letters (``rot`` whole zero octets: with three
+    octets to an 8-byte word, rot = 0, 1, 2 put every value at each of the three positions of a word), as
+    make_length_copies' records: the row is (3 L_i, p_i, 0). 2 239 488 + 8 rot records. Returns (problem, rows)."""
+    if not (0 <= top <= 5 and rot >= 0 and 1 <= base and base + 5 <= 25):
+        raise ValueError("need 0 <= top <= 5, rot >= 0 and 1 <= base <= 20")
+    values = np.arange(top * OCTET_SLICE, (top + 1) * OCTET_SLICE, dtype=np.int64)
+    lengths = np.concatenate([np.full(8 * rot, base, np.int64), base + octet_digits(values).reshape(-1)])
+    return make_length_copies(lengths, [seed, top, rot, base])
+
+
+def make_octet_tail(values, tail: int, base: int = 1, seed: int = 0):
+    """A batch that ends inside an octet: ``base`` + digit of every octet of ``values`` but only the first ``tail``
+    (1..7) digits of the last one, as make_length_copies' records. The kernels that take four lengths per load decode
+    the records after the last whole four one at a time. Returns (problem, rows)."""
+    if not 1 <= tail <= 7:
+        raise ValueError("tail: 1..7 records of the last octet")
+    lengths = base + octet_digits(values).reshape(-1)
+    return make_length_copies(lengths[:lengths.shape[0] - 8 + tail], [seed, tail, base])
+
+
+NARROW_PERIOD = {3: 8, 4: 2, 8: 4}  # records per byte pattern (3-bit), per byte (4-bit), per 4-record load (8-bit)
+
+
+def narrow_exhaustive_lengths(bits: int, base: int, top: int = None) -> np.ndarray:
+    """Record lengths holding every value of a ``bits``-bit length field (3-bit: 0..7, 4-bit: 0..15 above ``base``;
+    8-bit: the lengths 1 .. ``top``, default 128, ``base`` ignored) at every index residue that places the field
+    differently (index mod 8 for 3-bit fields, mod 2 for nibbles, mod 4 for the bytes a thread loads four at a time),
+    once between neighbours of the smallest value and once between neighbours of the largest: one group of
+    ``NARROW_PERIOD[bits]`` records per (fill, value, residue), all of the fill but the record at the residue."""
+    if bits not in NARROW_PERIOD:
+        raise ValueError("bits: 3, 4 or 8")
+    period = NARROW_PERIOD[bits]
+    values = np.arange(1, (128 if top is None else int(top)) + 1) if bits == 8 else int(base) + np.arange(1 << bits)
+    groups = []
+    for fill in (values[0], values[-1]):
+        g = np.full((values.shape[0], period, period), fill, dtype=np.int64)  # [value, residue, record of the group]
+        r = np.arange(period)
+        g[:, r, r] = values[:, None]
+        groups.append(g.reshape(-1))
+    return np.concatenate(groups)
+
+
+def make_narrow_exhaustive(bits: int, L1: int, base: int = 5, top: int = None, weights=(3, 1, 2, 4), seed: int = 0):
+    """narrow_exhaustive_lengths as a problem: Seq1 of ``L1`` random letters without equal neighbours, record i a copy
+    of the window of Seq1 from a seeded start (read cyclically where the record is longer than what follows it). The
+    reference is the CPU engine. Returns the problem."""
+    lengths = narrow_exhaustive_lengths(bits, base, top)
+    rng = np.random.default_rng([seed, bits, L1])
+    seq1 = seq_no_equal_neighbours(rng, L1)
+    return _copies(weights, seq1, lengths, rng.integers(0, L1, lengths.shape[0]))
+
+
+def short_octets() -> np.ndarray:
+    """The octet values whose upper or lower half (v = 1296 h + l) is at an end of its range: h in {0, 1295} with
+    every l, l in {0, 1295} with every h — 5 180 values, where the quotient by 6^4 that splits an octet is 0 or
+    largest, or steps with the smallest or largest remainder."""
+    ends, every = np.array([0, 1295], dtype=np.int64), np.arange(1296, dtype=np.int64)
+    v = np.concatenate([(ends[:, None] * 1296 + every[None, :]).reshape(-1),
+                        (every[:, None] * 1296 + ends[None, :]).reshape(-1)])
+    return np.unique(v)
+
+
+def make_short_octets(L1: int = 200, base: int = 150, weights=(3, 2, 1, 4), seed: int = 0) -> Problem:
+    """short_octets as record lengths ``base`` + digit (150..155) of random letters against a random Seq1 of ``L1``
+    (200): the lane-per-offset short kernel's regime with base-6 lengths. The reference is the CPU engine."""
+    lengths = base + octet_digits(short_octets()).reshape(-1)
+    rng = np.random.default_rng([seed, L1, base])
+    seq1 = rng.integers(1, 27, size=L1, dtype=np.uint8)
+    offsets = np.zeros(lengths.shape[0] + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    return Problem(Weights.of(weights), seq1, rng.integers(1, 27, size=int(offsets[-1]), dtype=np.uint8), offsets)

@@ -40,23 +40,23 @@ def random_lengths(n: int, form: str, seed: int) -> np.ndarray:
     return lengths
 
 
-def forced_slice(lengths, letters, letter_format: str, form: str, alloc=private_alloc) -> WireSlice:
+def forced_slice(lengths, letters, letter_format: str, form: str, alloc=private_alloc, base: int = 5) -> WireSlice:
     """A WireSlice whose lengths are re-encoded in ``form`` whatever range they span (WireSlice itself picks the
-    narrowest form, base 6 for every batch of one record): the lengths lie in 5..10, which every form holds above
-    base 5 (8-bit: base 0)."""
+    narrowest form, base 6 for every batch of one record): by default the lengths lie in 5..10, which every form holds
+    above ``base`` 5 (8-bit: base 0)."""
     ws = WireSlice(lengths, letters, letter_format, alloc=alloc)
     bits = _BITS[form]
     if form == "none":
         ws.len_bits, ws.len_base, ws.lengths = 0, 0, None
         return ws
     n = ws.n
-    ws.len_bits, ws.len_base = bits, (0 if bits == 8 else 5)
+    ws.len_bits, ws.len_base = bits, (0 if bits == 8 else base)
     if bits == LEN_BASE6:
-        ws.lengths = pack_lengths6(lengths, 5, out=alloc("lengths6", np.uint8, lengths6_bytes(n)))
+        ws.lengths = pack_lengths6(lengths, base, out=alloc("lengths6", np.uint8, lengths6_bytes(n)))
     elif bits == 3:
-        ws.lengths = pack_lengths3(lengths, 5, out=alloc("lengths3", np.uint8, lengths3_bytes(n)))
+        ws.lengths = pack_lengths3(lengths, base, out=alloc("lengths3", np.uint8, lengths3_bytes(n)))
     elif bits == 4:
-        ws.lengths = pack_lengths4(lengths, 5, out=alloc("lengths4", np.uint8, (n + 1) // 2))
+        ws.lengths = pack_lengths4(lengths, base, out=alloc("lengths4", np.uint8, (n + 1) // 2))
     else:
         ws.lengths = alloc("lengths", np.uint8, n)
         ws.lengths[:] = lengths
