@@ -466,6 +466,7 @@ class GpuRankImpl final : public GpuRank {
     g.kernel_ms = st.kernel_ms;
     g.h2d_bytes = st.h2d_bytes;
     g.d2h_bytes = st.d2h_bytes;
+    g.chunks = st.chunks;
     g.kernels = st.kernels;
     g.direct = st.direct;
     g.r2 = st.r2;

@@ -268,6 +268,7 @@ void run_sliced(JobCore& job, BulkParser& parser, int64_t first_index, SharedWin
       eng.kernel_ms += gs.kernel_ms;
       job.h2d_bytes += gs.h2d_bytes;
       job.d2h_bytes += gs.d2h_bytes;
+      job.chunks += gs.chunks;
     } else {
       solve_batch_cpu(eng.table, eng.seq1.data(), L1, cpu_batch, reinterpret_cast<Result*>(res_mine), eng.sem,
                       eng.threads);

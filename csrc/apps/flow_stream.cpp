@@ -458,6 +458,7 @@ void StreamFlow::finish(int s, Done& d) {
     j_.eng.kernel_ms += gs.kernel_ms;
     j_.h2d_bytes += gs.h2d_bytes;
     j_.d2h_bytes += gs.d2h_bytes;
+    j_.chunks += gs.chunks;
     kernel_ms_.push_back(gs.kernel_ms);
     d.launched = false;
     j_.pt.end();

@@ -89,6 +89,7 @@ struct RankEngine {
   Semantics sem = Semantics::Reference;
   int threads = 0;
   double kernel_ms = 0;  // accumulated device time of the search kernels
+  int64_t chunks = 0;    // accumulated chunks of the engine's solves (--timing)
 
   void set_problem(const Weights& w, const std::vector<uint8_t>& s1, Semantics s);
   void solve(const uint8_t* codes, const int64_t* offsets, int64_t n, Result* out);
@@ -118,6 +119,7 @@ struct JobCore {
   int64_t cells = 0, chars = 0, records = 0, batches = 0;
   int64_t first_index = 0;  // global index of the current batch's first record
   int64_t pinned_bytes = 0, h2d_bytes = 0, d2h_bytes = 0;  // this rank (--timing)
+  int64_t chunks = 0;  // chunks of this rank's wire solves (--timing rank_chunks, with eng.chunks)
   // rccl(-emul) transport (--timing): bytes this rank sent over the comm, the root's bytes to each rank and
   // its distribution time (per-peer rate = bytes / time)
   int64_t comm_sent_bytes = 0;

@@ -150,6 +150,7 @@ void RankEngine::solve(const uint8_t* codes, const int64_t* offsets, int64_t n, 
   if (gpu) {
     hip->solve(codes, offsets, n, out);
     kernel_ms += hip->last_kernel_ms();
+    chunks += hip->last_stats().chunks;
     return;
   }
   solve_batch_cpu(table, seq1.data(), static_cast<int64_t>(seq1.size()), copy_slice(codes, offsets, n), out, sem,
@@ -345,11 +346,11 @@ void JobCore::report(const Header& h) {
   }
   // every mode: what each rank page-locked and moved host->device over the job (sliced mode also has
   // its per-rank records and pin times, gathered with its results), and what it sent over the comm
-  int64_t moved[3] = {pinned_bytes, h2d_bytes, comm_sent_bytes};
-  std::vector<int64_t> all_moved(static_cast<size_t>(3 * ctx.size));
+  int64_t moved[4] = {pinned_bytes, h2d_bytes, comm_sent_bytes, chunks + eng.chunks};
+  std::vector<int64_t> all_moved(static_cast<size_t>(4 * ctx.size));
   {
     MPI_Request r;
-    mpi_check(MPI_Igather(moved, 3, MPI_INT64_T, all_moved.data(), 3, MPI_INT64_T, kRoot, ctx.world, &r), "MPI_Igather");
+    mpi_check(MPI_Igather(moved, 4, MPI_INT64_T, all_moved.data(), 4, MPI_INT64_T, kRoot, ctx.world, &r), "MPI_Igather");
     mpi_wait(r, "MPI_Igather (--timing)");
   }
   if (ctx.rank != kRoot || !flags.get_bool("timing", false)) return;
@@ -367,16 +368,21 @@ void JobCore::report(const Header& h) {
   } else {
     std::vector<int64_t> pinned(static_cast<size_t>(ctx.size)), h2d(static_cast<size_t>(ctx.size));
     for (int q = 0; q < ctx.size; ++q) {
-      pinned[q] = all_moved[3 * q];
-      h2d[q] = all_moved[3 * q + 1];
+      pinned[q] = all_moved[4 * q];
+      h2d[q] = all_moved[4 * q + 1];
     }
     per_rank += ", \"rank_pinned_bytes\": " + list(pinned) + ", \"rank_h2d_bytes\": " + list(h2d);
+  }
+  {  // the chunks each rank's engine ran (the staged pipeline's --chunk-records / --chunk-bytes; 0: a CPU rank)
+    std::vector<int64_t> rank_chunks(static_cast<size_t>(ctx.size));
+    for (int q = 0; q < ctx.size; ++q) rank_chunks[q] = all_moved[4 * q + 3];
+    per_rank += ", \"rank_chunks\": " + list(rank_chunks);
   }
   if (device_transport || coll_rccl) {
     // the numbers a first multi-GPU run reads: communicator set-up, bytes each rank put on the comm, and the
     // root's rate to each peer over the distribution (bytes to that rank / the root's distribution time)
     std::vector<int64_t> sent(static_cast<size_t>(ctx.size));
-    for (int q = 0; q < ctx.size; ++q) sent[q] = all_moved[3 * q + 2];
+    for (int q = 0; q < ctx.size; ++q) sent[q] = all_moved[4 * q + 2];
     char buf[96];
     std::snprintf(buf, sizeof buf, "%.3f, \"rccl_comm_wait_ms\": %.3f, \"distribute_ms\": %.3f", mx[2], mx[3],
                   distribute_ms);

@@ -50,6 +50,11 @@ int moc_score_table(const int32_t* weights4, int32_t* lut1024, uint8_t* cls1024)
  * index bits of tile16's 32-bit selection keys (0 = 64-bit keys), [5] 1 if the int16 tile16 profile holds the
  * table. */
 int moc_kernel_bounds(const int32_t* weights4, int64_t L1, int64_t min_l2, int64_t max_l2, int32_t* out6);
+/* ---- the staged pipeline's cut (moc/tile_plan.hpp plan::staged_chunks); no GPU needed ----
+ * The chunks an engine made with these sizes cuts a batch into (0 for a size: the engine's default): their bounds
+ * 0 = b0 < b1 < ... = n into bounds_out (room for n + 1 entries). Returns the number of chunks, -1 on error. */
+int64_t moc_staged_chunks(const int64_t* offsets, int64_t n, int64_t chunk_records, int64_t chunk_bytes,
+                          int64_t* bounds_out);
 /* "src=<source hash> defs=<-D flags of the kernel objects>" (empty defs: the product build) */
 const char* moc_build_info(void);
 
@@ -234,6 +239,11 @@ int moc_cpu_decode_wire(const moc_wire_batch* b, uint8_t* codes_out, int64_t* of
  * buffers of the caller (letter count bytes / n + 1 entries) that receive the decode instead of the engine's. */
 int moc_engine_decode_wire_device(void* e, const moc_wire_batch* b, const moc_wire_batch* host_meta, void* stream,
                                   uint64_t* out3, int64_t* h_offsets_out, uint8_t* d_codes_dst, int64_t* d_offsets_dst);
+/* The search of a host wire batch (moc::HipEngine::solve_wire, what ./final's GPU ranks call): results in `fmt`
+ * (moc_engine_solve_ex) into out; min_l2 / max_l2: the batch's length range (-1: unknown; required with sparse
+ * offsets). Zero-copy when every array is page-locked and the streaming kernel takes the batch, else the staged
+ * pipeline (P33 letters unpacked and sparse offsets expanded on the host first). Synchronous. */
+int moc_engine_solve_wire(void* e, const moc_wire_batch* b, void* out, int fmt, int64_t min_l2, int64_t max_l2);
 /* Profile, top-K, hits and report of a host wire batch: the decode above, then moc_engine_solve_profile /
  * _solve_topk / _solve_hits / _report on the decoded buffers, with their arguments and contracts. Synchronous. */
 int moc_engine_solve_profile_wire(void* e, const moc_wire_batch* b, int64_t* poffsets, moc_profile_entry* prof);

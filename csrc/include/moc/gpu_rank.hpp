@@ -34,6 +34,7 @@ struct GpuRankOptions {
 struct GpuSolveStats {
   double kernel_ms = 0;
   int64_t h2d_bytes = 0, d2h_bytes = 0;
+  int64_t chunks = 0;   // chunks of the staged pipeline (1: a zero-copy solve)
   int32_t kernels = 0;  // bitmask: 1 swipe, 2 short, 4 tiles
   int32_t direct = 0;   // 1: streamed zero-copy / DMA from pinned host memory
   R2Params r2{};        // parameters of R2 results

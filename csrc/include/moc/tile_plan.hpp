@@ -50,6 +50,16 @@ struct ChunkPlan {
 };
 void plan_chunk(const Config& c, const int64_t* offsets, int64_t n, ChunkPlan& cp);
 
+// The staged pipeline's cut (HipEngine::run_staged). End (exclusive) of the chunk that starts at record rb: the
+// longest run rb..re with re - rb <= chunk_records and offsets[re] - offsets[rb] <= chunk_bytes, and at least one
+// record (a record longer than chunk_bytes is a chunk of its own). offsets: n + 1 absolute entries (any first
+// offset); 0 <= rb < n; both limits >= 1.
+int64_t staged_chunk_end(const int64_t* offsets, int64_t n, int64_t rb, int64_t chunk_records, int64_t chunk_bytes);
+// Every chunk of a batch: the bounds 0 = b0 < b1 < ... = n into bounds_out (room for n + 1 entries); returns their
+// count minus one. Stops after n chunks whatever staged_chunk_end answers (a cut that does not advance cannot hang
+// a caller: the last bound is then short of n).
+int64_t staged_chunks(const int64_t* offsets, int64_t n, int64_t chunk_records, int64_t chunk_bytes, int64_t* bounds_out);
+
 struct TilePlan {
   int u = 2;              // sub-tiles per wave tile
   int win_tiles = 0;      // windowed tile16: tiles per window stride

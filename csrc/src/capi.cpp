@@ -19,6 +19,7 @@
 #include "moc/runtime/log.hpp"
 #include "moc/runtime/pinned.hpp"
 #include "moc/score_table.hpp"
+#include "moc/tile_plan.hpp"
 
 static_assert(sizeof(moc_result) == sizeof(moc::Result), "ABI result layout");
 static_assert(sizeof(moc_profile_entry) == sizeof(moc::ProfileEntry), "ABI profile entry layout");
@@ -141,6 +142,20 @@ int moc_kernel_bounds(const int32_t* weights4, int64_t L1, int64_t min_l2, int64
     out6[4] = moc::bounds::tile16_key32_bits(L1, w, searched);
     out6[5] = moc::profile16_i16_fits(t) ? 1 : 0;
   });
+}
+
+int64_t moc_staged_chunks(const int64_t* offsets, int64_t n, int64_t chunk_records, int64_t chunk_bytes,
+                          int64_t* bounds_out) {
+  int64_t chunks = -1;
+  guard([&] {
+    if (n < 0 || chunk_records < 0 || chunk_bytes < 0) throw moc::Error("staged_chunks: negative size");
+    for (int64_t i = 0; i < n; ++i)
+      if (offsets[i + 1] < offsets[i]) throw moc::Error("staged_chunks: offsets must not decrease");
+    const moc::EngineOptions defaults;
+    chunks = moc::plan::staged_chunks(offsets, n, chunk_records > 0 ? chunk_records : defaults.chunk_records,
+                                      chunk_bytes > 0 ? chunk_bytes : defaults.chunk_bytes, bounds_out);
+  });
+  return chunks;
 }
 
 int moc_cpu_solve(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
@@ -647,6 +662,16 @@ int moc_engine_solve_profile_wire(void* e, const moc_wire_batch* w, int64_t* pof
       eng->wire_profile_offsets(b, poffsets);
     else
       eng->solve_profile_wire(b, reinterpret_cast<moc::ProfileEntry*>(prof), poffsets);
+  });
+}
+
+int moc_engine_solve_wire(void* e, const moc_wire_batch* w, void* out, int fmt, int64_t min_l2, int64_t max_l2) {
+  return guard([&] {
+    moc::WireBatch b = wire_batch(w);
+    if (b.device) throw moc::Error("solve_wire: host pointers only (moc_engine_solve_wire_device)");
+    b.min_l2 = min_l2;
+    b.max_l2 = max_l2;
+    static_cast<moc::HipEngine*>(e)->solve_wire(b, out, static_cast<moc::ResultFormat>(fmt));
   });
 }
 

@@ -781,12 +781,7 @@ void HipEngine::run_staged(const uint8_t* codes, const int64_t* offsets, int64_t
   int64_t chunk = 0;
   for (int64_t rb = 0; rb < n; ++chunk) {
     // chunk end: at most chunk_records records and chunk_bytes letters (at least one record)
-    int64_t re = std::min(n, rb + opt_.chunk_records);
-    const int64_t byte_cap = offsets[rb] + opt_.chunk_bytes;
-    if (offsets[re] > byte_cap) {
-      re = std::upper_bound(offsets + rb + 1, offsets + re + 1, byte_cap) - offsets - 1;
-      re = std::max(re, rb + 1);
-    }
+    const int64_t re = plan::staged_chunk_end(offsets, n, rb, opt_.chunk_records, opt_.chunk_bytes);
     const int64_t cn = re - rb;
     Slot& s = *slots_[chunk % 2];
     retire(s);

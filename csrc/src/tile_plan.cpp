@@ -93,6 +93,26 @@ void plan_chunk(const Config& c, const int64_t* offsets, int64_t n, ChunkPlan& c
     throw Error("Seq1 / Seq2 lengths beyond 2^30 exceed the device engine's offset range");
 }
 
+int64_t staged_chunk_end(const int64_t* offsets, int64_t n, int64_t rb, int64_t chunk_records, int64_t chunk_bytes) {
+  int64_t re = chunk_records < n - rb ? rb + chunk_records : n;  // (no sum that a huge limit could overflow)
+  if (offsets[re] - offsets[rb] > chunk_bytes) {
+    const int64_t byte_cap = offsets[rb] + chunk_bytes;
+    re = std::upper_bound(offsets + rb + 1, offsets + re + 1, byte_cap) - offsets - 1;
+    re = std::max(re, rb + 1);
+  }
+  return re;
+}
+
+int64_t staged_chunks(const int64_t* offsets, int64_t n, int64_t chunk_records, int64_t chunk_bytes, int64_t* bounds_out) {
+  int64_t chunks = 0;
+  bounds_out[0] = 0;
+  for (int64_t rb = 0; rb < n && chunks < n; ++chunks) {
+    rb = staged_chunk_end(offsets, n, rb, chunk_records, chunk_bytes);
+    bounds_out[chunks + 1] = rb;
+  }
+  return chunks;
+}
+
 int64_t tile_costs(const Config& c, const int64_t* offsets, const int32_t* long_recs, int64_t n_long, int span,
                    std::vector<int32_t>& ntiles, std::vector<int64_t>& tcost) {
   ntiles.resize(static_cast<size_t>(n_long));

@@ -2106,6 +2106,79 @@ void test_plan_profile() {
   CHECK(throws([&] { plan::plan_profile(c, Semantics::Reference, huge, 1, true, 8, 64, 0); }, "beyond 2^30"));
 }
 
+// ---- the staged pipeline's cut (plan::staged_chunk_end / staged_chunks) ----------------------------------
+// The rule by a plain scan: records while both limits hold, and at least one.
+std::vector<int64_t> staged_model(const std::vector<int64_t>& off, int64_t R, int64_t B) {
+  const int64_t n = static_cast<int64_t>(off.size()) - 1;
+  std::vector<int64_t> b = {0};
+  for (int64_t rb = 0; rb < n;) {
+    int64_t re = rb + 1;
+    while (re < n && re + 1 - rb <= R && off[re + 1] - off[rb] <= B) ++re;
+    b.push_back(re);
+    rb = re;
+  }
+  return b;
+}
+
+void test_staged_chunks() {
+  auto offsets_of = [](const std::vector<int64_t>& lens, int64_t base) {
+    std::vector<int64_t> off = {base};
+    for (int64_t l : lens) off.push_back(off.back() + l);
+    return off;
+  };
+  auto cut = [](const std::vector<int64_t>& off, int64_t R, int64_t B) {
+    const int64_t n = static_cast<int64_t>(off.size()) - 1;
+    std::vector<int64_t> b(static_cast<size_t>(n) + 1, -1);
+    const int64_t chunks = plan::staged_chunks(off.data(), n, R, B, b.data());
+    b.resize(static_cast<size_t>(chunks) + 1);
+    return b;
+  };
+  using V = std::vector<int64_t>;
+  const V tens(12, 10);  // the first j records hold 10 j letters
+  for (const int64_t base : {int64_t{0}, int64_t{12345}, (int64_t{1} << 33) + 7}) {
+    const V off = offsets_of(tens, base);
+    // letters of the first 4 records exactly chunk_bytes, one less, one more
+    CHECK((cut(off, 100, 40) == V{0, 4, 8, 12}));
+    CHECK((cut(off, 100, 39) == V{0, 3, 6, 9, 12}));
+    CHECK((cut(off, 100, 41) == V{0, 4, 8, 12}));
+    // chunk_records of 1, n - 1, n and n + 1
+    CHECK(cut(off, 1, 1 << 20).size() == 13);
+    CHECK((cut(off, 11, 1 << 20) == V{0, 11, 12}));
+    CHECK((cut(off, 12, 1 << 20) == V{0, 12}) && (cut(off, 13, 1 << 20) == V{0, 12}));
+    // both limits in one batch: whichever is reached first
+    CHECK((cut(off, 3, 45) == V{0, 3, 6, 9, 12}) && (cut(off, 5, 25) == V{0, 2, 4, 6, 8, 10, 12}));
+    // chunk_bytes = 1: every record longer than the limit, each a chunk of its own
+    CHECK(cut(off, 100, 1).size() == 13);
+    // a record longer than chunk_bytes first, in the middle and last
+    CHECK((cut(offsets_of({50, 10, 10, 10, 10}, base), 100, 20) == V{0, 1, 3, 5}));
+    CHECK((cut(offsets_of({10, 10, 50, 10, 10}, base), 100, 20) == V{0, 2, 3, 5}));
+    CHECK((cut(offsets_of({10, 10, 10, 50, 10}, base), 100, 20) == V{0, 2, 3, 4, 5}));
+    CHECK((cut(offsets_of({10, 10, 10, 10, 50}, base), 100, 20) == V{0, 2, 4, 5}));
+    CHECK((cut(offsets_of({3000}, base), 100, 20) == V{0, 1}));
+    // limits no sum can hold
+    CHECK((cut(off, INT64_MAX, INT64_MAX) == V{0, 12}));
+  }
+  CHECK((cut({0}, 4, 4) == V{0}));  // no records: no chunk
+  // against the scan, and the rule's properties
+  std::mt19937_64 rng(20);
+  for (int it = 0; it < 400; ++it) {
+    const int64_t n = 1 + static_cast<int64_t>(rng() % 40);
+    V lens;
+    for (int64_t i = 0; i < n; ++i) lens.push_back(1 + static_cast<int64_t>(rng() % (it % 3 ? 12 : 300)));
+    const V off = offsets_of(lens, static_cast<int64_t>(rng() % 100000));
+    const int64_t R = 1 + static_cast<int64_t>(rng() % (n + 2)), B = 1 + static_cast<int64_t>(rng() % 400);
+    const V b = cut(off, R, B);
+    CHECK(b == staged_model(off, R, B));
+    CHECK(b.front() == 0 && b.back() == n);
+    for (size_t c = 0; c + 1 < b.size(); ++c) {
+      CHECK(b[c + 1] > b[c]);
+      CHECK(b[c + 1] - b[c] <= R);
+      CHECK(off[b[c + 1]] - off[b[c]] <= B || b[c + 1] - b[c] == 1);
+      CHECK(plan::staged_chunk_end(off.data(), n, b[c], R, B) == b[c + 1]);
+    }
+  }
+}
+
 int main(int argc, char** argv) {
   const std::vector<std::pair<const char*, std::function<void()>>> tests = {
       {"score_table", test_score_table}, {"parser", test_parser},     {"stream_reader", test_stream_reader},
@@ -2121,7 +2194,7 @@ int main(int argc, char** argv) {
       {"profile16_lds_bytes", test_profile16_lds_bytes}, {"watchdog", test_watchdog},
       {"tile_plan_cases", test_tile_plan_cases}, {"tile_plan_digests", test_tile_plan_digests},
       {"plan_chunk_threaded", test_plan_chunk_threaded}, {"plan_layout", test_plan_layout},
-      {"plan_profile", test_plan_profile}};
+      {"plan_profile", test_plan_profile}, {"staged_chunks", test_staged_chunks}};
   for (const auto& t : tests) {
     if (argc > 1 && !std::strstr(t.first, argv[1])) continue;  // test_core NAME: only the tests named *NAME*
     const int before = g_failed;

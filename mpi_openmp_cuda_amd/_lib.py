@@ -61,6 +61,7 @@ def _decl(lib):
         "moc_format_results": (c_int64, [c_void_p, c_int64, c_int64, c_void_p, c_int64]),
         "moc_score_table": (c_int, [P(c_int32), c_void_p, c_void_p]),
         "moc_kernel_bounds": (c_int, [P(c_int32), c_int64, c_int64, c_int64, c_void_p]),
+        "moc_staged_chunks": (c_int64, [c_void_p, c_int64, c_int64, c_int64, c_void_p]),
         "moc_build_info": (c_char_p, []),
         "moc_packed5_bytes": (c_int64, [c_int64]),
         "moc_pack5": (c_int, [c_void_p, c_int64, c_void_p]),
@@ -104,6 +105,7 @@ def _decl(lib):
         "moc_cpu_decode_wire": (c_int, [P(WireBatch), c_void_p, c_void_p, c_void_p]),
         "moc_engine_decode_wire_device": (c_int, [c_void_p, P(WireBatch), P(WireBatch), c_void_p, c_void_p, c_void_p,
                                                   c_void_p, c_void_p]),
+        "moc_engine_solve_wire": (c_int, [c_void_p, P(WireBatch), c_void_p, c_int, c_int64, c_int64]),
         "moc_engine_solve_profile_wire": (c_int, [c_void_p, P(WireBatch), c_void_p, c_void_p]),
         "moc_engine_solve_topk_wire": (c_int, [c_void_p, P(WireBatch), c_int, c_void_p]),
         "moc_engine_solve_hits_wire": (c_int, [c_void_p, P(WireBatch), c_int32, c_void_p, c_int64, c_void_p, c_void_p,

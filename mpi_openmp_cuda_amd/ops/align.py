@@ -1507,6 +1507,20 @@ class HipSearchEngine:
         del keep
         return dense
 
+    def solve_wire(self, ws, shift: int = 0) -> np.ndarray:
+        """Host wire batch (a :class:`~..parallel.wire.WireSlice` with its results allocated; ``shift`` > 0: through
+        its sparse offsets, as ``./final``'s GPU ranks send their slices) -> the slice's ``results`` in its format
+        (``ws.triples(engine)`` decodes them). Zero-copy when every array is page-locked and the streaming kernel
+        takes the batch; else the staged pipeline, P33 letters unpacked and sparse offsets expanded on the host
+        first. Synchronous."""
+        if ws.results is None:
+            ws.alloc_results(self)
+        b, keep = wire_batch_of(ws, shift)
+        _lib.check(_lib.lib().moc_engine_solve_wire(self._h, ctypes.byref(b), _lib.ptr(ws.results),
+                                                    _format_id(ws.fmt), int(ws.l2_min), int(ws.l2_max)))
+        del keep
+        return ws.results
+
     def solve_profile_wire(self, ws, shift: int = 0):
         """Host wire batch (a :class:`~..parallel.wire.WireSlice`; ``shift`` > 0: through its sparse offsets) ->
         ``(prof, poffsets)`` as :meth:`solve_profile` returns them for the decoded records. The packed letters,
@@ -1619,6 +1633,24 @@ def kernel_bounds(weights, L1: int, min_l2: int, max_l2: int) -> dict:
     swipe = {1: "swipe_kbits", 2: "swipe_rk"}.get(int(out[0]))
     return {"swipe": swipe, "short_pk": bool(out[1]), "key_shift": int(out[2]), "profile16": bool(out[3]),
             "tile16_key_bits": int(out[4]), "profile16_i16": bool(out[5])}
+
+
+def staged_chunks(offsets, chunk_records: int = 0, chunk_bytes: int = 0) -> np.ndarray:
+    """The chunks the staged pipeline of a ``HipSearchEngine(chunk_records=, chunk_bytes=)`` cuts a batch into
+    (csrc/include/moc/tile_plan.hpp staged_chunk_end), no GPU needed: int64 bounds ``0 = b0 < b1 < ... = n``, chunk c
+    holding records ``[b[c], b[c + 1])``. A chunk is the longest run of at most ``chunk_records`` records and
+    ``chunk_bytes`` letters, and at least one record; 0 for a size means the engine's default. ``offsets`` as
+    :meth:`HipSearchEngine.solve` takes them (absolute, any first offset)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = offsets.shape[0] - 1
+    if n < 0:
+        raise ValueError("offsets needs at least one entry")
+    bounds = np.zeros(n + 1, np.int64)
+    chunks = int(_lib.lib().moc_staged_chunks(_lib.ptr(offsets), n, int(chunk_records), int(chunk_bytes),
+                                              _lib.ptr(bounds)))
+    if chunks < 0:
+        raise _lib.NativeError(_lib.lib().moc_last_error().decode(errors="replace"))
+    return bounds[:chunks + 1].copy()
 
 
 def search_hip(problem: Problem, semantics=Semantics.REFERENCE, device: Optional[int] = None,
