@@ -361,6 +361,43 @@ int moc_engine_solve_targets_summary_wire(void* e, const moc_wire_batch* b, cons
                                           int32_t bins, int32_t lo, int32_t width, int64_t* summary, int32_t* hist);
 /* device time (ms) of the last per-target summary call's summary + histogram launches (MOC_PROFILE_TIMING=1; else 0) */
 int moc_engine_targets_summary_ms(void* e, double* ms);
+/* ---- per-target top-K and threshold hits (moc/cpu_engine.hpp targets_topk_batch_cpu / targets_hits_batch_cpu) ----
+ * Seq1 is a catalog delimited by starts as above; pair p = i * T + t is record i against target t alone, every n
+ * relative to the target's start.
+ * Top-K, 1 <= K <= 64: rows [n * T * K], pair-major: the pair's min(K, entries) best placements in better() order,
+ * then (INT32_MIN, 0, 0) rows. K = 1 is moc_cpu_targets.
+ * Hits: thresholds NULL (min_score for every pair) or int32 [n * T], pair-major. toffsets: int64 [n * T + 1], always
+ * complete and exact; pair p's hits, ascending in n, are rows[toffsets[p] .. toffsets[p + 1]); a row is written iff its
+ * flat index is < cap, nothing at or past rows + cap is touched, cap = 0 (rows may be NULL) counts only — the
+ * contract of moc_cpu_hits. The engine's host forms are optimistic as moc_engine_solve_hits is (max_rows_hint < 0:
+ * n * T; moc_engine_hits_passes, moc_engine_hits_rows); the device forms queue on `stream` with no sync
+ * (d_thresholds: device int32 [n * T] or NULL; d_starts / h_starts as moc_engine_solve_targets_device).
+ * Errors, all reported before any work: the target set's ("targets:"), then K ("top-K:") or the buffers ("hits:").
+ * moc_engine_targets_ms gives the device time of the new launches. */
+int moc_cpu_targets_topk(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                         const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics, int threads,
+                         int K, moc_result* rows);
+int moc_cpu_targets_hits(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                         const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics, int threads,
+                         int32_t min_score, const int32_t* thresholds, int64_t* toffsets, moc_result* rows, int64_t cap);
+int moc_engine_solve_targets_topk(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
+                                  int64_t T, int K, moc_result* rows);
+int moc_engine_solve_targets_topk_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                         const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
+                                         const int64_t* h_starts, int64_t T, int K, moc_result* d_rows, void* stream);
+int moc_engine_solve_targets_topk_wire(void* e, const moc_wire_batch* b, const int64_t* starts, int64_t T, int K,
+                                       moc_result* rows);
+int moc_engine_solve_targets_hits(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
+                                  int64_t T, int32_t min_score, const int32_t* thresholds, int64_t max_rows_hint,
+                                  int64_t* toffsets, moc_result* rows, int64_t cap);
+int moc_engine_solve_targets_hits_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                         const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
+                                         const int64_t* h_starts, int64_t T, int32_t min_score,
+                                         const int32_t* d_thresholds, int64_t* d_toffsets, moc_result* d_rows, int64_t cap,
+                                         void* stream);
+int moc_engine_solve_targets_hits_wire(void* e, const moc_wire_batch* b, const int64_t* starts, int64_t T,
+                                       int32_t min_score, const int32_t* thresholds, int64_t max_rows_hint,
+                                       int64_t* toffsets, moc_result* rows, int64_t cap);
 /* stats: kernel_ms, total_ms, h2d_bytes, d2h_bytes, chunks, cells, records, direct, format, kernels,
  * r2 smin, r2 kw, r2 j, forms (moc::bounds::FormBits of the last solve) */
 int moc_engine_stats(void* e, double* out14);

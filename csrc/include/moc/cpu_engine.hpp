@@ -174,6 +174,24 @@ void targets_summary_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L
                                const int64_t* starts, int64_t T, int64_t* summary, int32_t* hist, int32_t bins,
                                int32_t lo, int32_t width, Semantics sem, int num_threads = 0);
 
+// ---- per-target top-K and threshold hits: the rows of every (record, target) pair's target profile
+// Terms and the target profile as above; pair (i, t) has C_{i,t} = bounds::targets_pair_count(len, L2, spec)
+// entries, the boundary entry (k = 0, local offset len - L2, summed from the letters) the last of them.
+// Top-K, 1 <= K <= kMaxTopK: out[((i * T + t) * K) ..) = the pair's min(K, C_{i,t}) best entries in better() order
+// (higher score, then smaller local offset) as (score, n local to the target, that entry's k), then no_candidate()
+// rows. It is topk_batch_cpu run on target t alone, row for row; K = 1 is targets_batch_cpu.
+// Hits: pair p = i * T + t has the threshold thresholds[p] (int32 [n * T], pair-major), or min_score for every pair
+// when thresholds is null; its hits are the entries of its target profile with score >= threshold in ascending local
+// offset — hits_batch_cpu run on target t alone. toffsets (int64 [n * T + 1]) is hits_batch_cpu's index over pairs
+// and the capacity contract is its own: the index always complete and exact, a row written iff its flat index is
+// < cap, nothing at or past rows + cap touched, cap == 0 (rows may be null) counts only. A pair that does not fit
+// has no hits. Errors before any work: check_targets' ("targets: ..."), then the top-K / hits messages.
+void targets_topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                            const int64_t* starts, int64_t T, int K, Result* out, Semantics sem, int num_threads = 0);
+void targets_hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                            const int64_t* starts, int64_t T, int32_t min_score, const int32_t* thresholds,
+                            int64_t* toffsets, Result* rows, int64_t cap, Semantics sem, int num_threads = 0);
+
 // ---- alignment report: the signs under a result row's letter pairs
 // A row is a Result {score, n, k} of record i (L2 letters) against Seq1; rows[i*K .. i*K+K) belong to record i.
 //   empty row   (score == kNoCandidateScore, e.g. top-K padding): counts {0,0,0,0}, marker bytes 0, nothing read

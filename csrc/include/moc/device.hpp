@@ -438,6 +438,29 @@ struct TargetsSummaryArgs {
 // would pass the grid limit).
 void launch_targets_summary(const TargetsSummaryArgs& sa, const ProblemView& pv, const BatchView& bv, hipStream_t stream);
 
+// ---- per-target top-K and threshold hits (targets_rows_kernels.hip; definitions: moc/cpu_engine.hpp
+// targets_topk_batch_cpu / targets_hits_batch_cpu)
+// Top-K: the chunk, pairs and lane groups of TargetsArgs; pair (r, t) stores its K rows at ta.out[(r * T + t) * K ..)
+// (batch-wide record index; every row is stored, the empty row past the pair's entries), 1 <= K <= kMaxTopK. More
+// than one launch when the blocks would pass the grid limit.
+void launch_targets_topk(const TargetsArgs& ta, int K, const ProblemView& pv, const BatchView& bv, hipStream_t stream);
+// Hits: HitsArgs' contract over pairs in place of records (ta.out is not used). toffsets is the batch's int64
+// [n_total * T + 1] hit index: the count kernel leaves pair p's count in toffsets[p + 1] (and 0 in toffsets[0] when the
+// chunk starts the batch), launch_hits_scan turns the chunk's counts into running totals on top of toffsets[rec0 * T]
+// — complete since the previous chunk's scan on the same stream — and the compaction stores pair p's hits, ascending
+// in the local offset, at rows[toffsets[p] ..) below `cap`.
+struct TargetsHitsArgs {
+  TargetsArgs ta;
+  const int32_t* thresholds = nullptr;  // device int32 [n_total * T] (batch-wide pair index), or null: min_score for all
+  int32_t min_score = 0;
+  int64_t* toffsets = nullptr;          // device int64 [n_total * T + 1]
+  int64_t* sums = nullptr;              // scan scratch: ceil(n_rec * T / bounds::kHitsScanBlockRecords) entries
+  Result* rows = nullptr;               // device, `cap` rows; null with cap == 0 counts only
+  int64_t cap = 0;
+};
+// Queues count, scan (one or three launches) and, when cap > 0, the compaction on `stream`.
+void launch_targets_hits(const TargetsHitsArgs& ha, const ProblemView& pv, const BatchView& bv, hipStream_t stream);
+
 // Loads every kernel file's code object onto the current device now (HIP loads them lazily, at the first
 // launch from each file: milliseconds inside the first timed search of a job otherwise).
 void preload_align_kernels();
@@ -454,6 +477,7 @@ void preload_peaks_kernels();
 void preload_summary_kernels();
 void preload_targets_kernels();
 void preload_targets_summary_kernels();
+void preload_targets_rows_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -471,6 +495,7 @@ enum PreloadSet : unsigned {
   kPreloadSummary = 2048,  // summary_kernels.hip: likewise
   kPreloadTargets = 4096,  // targets_kernels.hip: likewise
   kPreloadTargetsSummary = 8192,  // targets_summary_kernels.hip: likewise
+  kPreloadTargetsRows = 16384,    // targets_rows_kernels.hip: likewise
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -487,9 +512,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadSummary) preload_summary_kernels();
   if (set & kPreloadTargets) preload_targets_kernels();
   if (set & kPreloadTargetsSummary) preload_targets_summary_kernels();
+  if (set & kPreloadTargetsRows) preload_targets_rows_kernels();
 }
 // "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
-// profile, report, hits, wire, peaks, summary, targets, targets_summary;
+// profile, report, hits, wire, peaks, summary, targets, targets_summary, targets_rows;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

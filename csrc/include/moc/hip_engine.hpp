@@ -66,7 +66,9 @@ struct EngineStats {
                          // 256 peaks (the peak filter and masked select / hits kernels of a distinct call),
                          // 512 summary (the summary / histogram kernels, next to 16),
                          // 1024 targets (the multi-target select kernel, next to 16),
-                         // 2048 targets_summary (the per-target summary / histogram kernels, next to 16)
+                         // 2048 targets_summary (the per-target summary / histogram kernels, next to 16),
+                         // 4096 targets_topk (the per-target top-K kernel, next to 16),
+                         // 8192 targets_hits (the per-target count / scan / compact kernels, next to 16)
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -217,6 +219,9 @@ class HipEngine {
   // Host form (uploads through the pooled buffers; synchronous; fills stats()).
   void solve_targets(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T,
                      Result* out);
+  // The check every targets call makes first: throws unless a problem is set and (h_starts, T) is a valid target set
+  // over its Seq1; touches nothing.
+  void check_targets_call(const int64_t* h_starts, int64_t T) const;
   // Device time (ms) of the targets select launches of the last targets call; as topk_select_ms().
   double targets_ms() { return topk_select_ms(); }
 
@@ -240,6 +245,38 @@ class HipEngine {
                              int64_t* summary_out, int32_t* hist_out, int32_t bins, int32_t lo, int32_t width);
   // Device time (ms) of the per-target summary (and histogram) launches of the last such call; as topk_select_ms().
   double targets_summary_ms() { return topk_select_ms(); }
+
+  // ---- per-target top-K and threshold hits (definitions: moc/cpu_engine.hpp targets_topk_batch_cpu /
+  // targets_hits_batch_cpu; kernels: csrc/src/hip/targets_rows_kernels.hip): the engine's Seq1 is a catalog as for
+  // solve_targets, and every (record, target) pair gets the K best entries of its target profile — rows [n * T * K],
+  // pair-major, padded with empty rows — or every entry at or above its threshold in ascending local offset, pair p =
+  // i * T + t's rows at rows[toffsets[p] .. toffsets[p + 1]). n is local to the target in both. Limits as
+  // solve_targets. Before anything is launched or any state changes the target set is checked ("targets:" errors),
+  // then K (solve_topk's message) or the hits buffers (solve_hits_device's messages). targets_ms() covers the new
+  // launches.
+  // Device forms: queued on `stream` (0 = engine compute stream) with no sync, in the chunks of solve_targets — per
+  // chunk the profile kernel over the catalog, then the per-target top-K kernel, or count, prefix sum over the
+  // chunk's pairs (hits' own scan launches) and compaction, the lane group chosen as solve_targets chooses it (top-K:
+  // bounds::targets_topk_group, a wave from 257 slice entries on).
+  // d_starts / h_starts as solve_targets_device. d_thresholds: device int32 [n * T] (pair-major), or null for
+  // min_score on every pair. d_toffsets (int64 [n * T + 1]) is always complete and exact; a row is stored iff its
+  // flat index is < cap, and nothing at or past d_rows + cap is touched (cap == 0 with a null d_rows counts only).
+  // An empty batch launches nothing, apart from the 8-byte memset of d_toffsets[0] of the hits form.
+  void solve_targets_topk_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                                 const int64_t* d_starts, const int64_t* h_starts, int64_t T, int K, Result* d_out,
+                                 hipStream_t stream);
+  void solve_targets_hits_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                                 const int64_t* d_starts, const int64_t* h_starts, int64_t T, int32_t min_score,
+                                 const int32_t* d_thresholds, int64_t* d_toffsets, Result* d_rows, int64_t cap,
+                                 hipStream_t stream);
+  // Host forms (upload through the pooled buffers; synchronous; fill stats()). thresholds: host int32 [n * T] or null.
+  // Hits is optimistic as solve_hits is: one pass with room for max(max_rows_hint, 1) rows (hint < 0: n * T), and
+  // exactly one more with toffsets[n * T] rows when that was too few; hits_passes() tells.
+  void solve_targets_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T,
+                          int K, Result* out);
+  void solve_targets_hits(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T,
+                          int32_t min_score, const int32_t* thresholds, int64_t* toffsets_out,
+                          std::vector<Result>& rows_out, int64_t max_rows_hint = -1);
 
   // ---- alignment report (definitions: moc/cpu_engine.hpp report_batch_cpu; kernels:
   // csrc/src/hip/report_kernels.hip): the sign counts and, optionally, the marker bytes of caller-supplied rows.
@@ -290,6 +327,10 @@ class HipEngine {
   void solve_targets_wire(const WireBatch& b, const int64_t* starts, int64_t T, Result* out);
   void solve_targets_summary_wire(const WireBatch& b, const int64_t* starts, int64_t T, int64_t* summary_out,
                                   int32_t* hist_out, int32_t bins, int32_t lo, int32_t width);
+  void solve_targets_topk_wire(const WireBatch& b, const int64_t* starts, int64_t T, int K, Result* out);
+  void solve_targets_hits_wire(const WireBatch& b, const int64_t* starts, int64_t T, int32_t min_score,
+                               const int32_t* thresholds, int64_t* toffsets_out, std::vector<Result>& rows_out,
+                               int64_t max_rows_hint = -1);
   // poffsets[0..n] of a host wire batch (profile_offsets of its decoded lengths; no GPU work)
   void wire_profile_offsets(const WireBatch& b, int64_t* poffsets) const;
 
@@ -375,6 +416,9 @@ class HipEngine {
   void targets_placed(Placed& p, const int64_t* starts, int64_t T, Result* out);
   void targets_summary_placed(Placed& p, const int64_t* starts, int64_t T, int64_t* summary_out, int32_t* hist_out,
                               int32_t bins, int32_t lo, int32_t width);
+  void targets_topk_placed(Placed& p, const int64_t* starts, int64_t T, int K, Result* out);
+  void targets_hits_placed(Placed& p, const int64_t* starts, int64_t T, int32_t min_score, const int32_t* thresholds,
+                           int64_t* toffsets_out, std::vector<Result>& rows_out, int64_t max_rows_hint);
   void report_placed(Placed& p, int K, const Result* rows, int32_t* counts, uint8_t* marks);
   void ensure_device_events();  // ev_d0_ / ev_d1_, made by the first call that records them
   dev::Plan device_plan(void* d_plan, size_t n_starts, bool has_long_recs, int64_t n_long, const plan::TilePlan& tp,
@@ -405,7 +449,7 @@ class HipEngine {
                   bool packed5);
   void solve_wire_impl(const WireBatch& b, void* out, ResultFormat fmt, bool async);
   // ---- the profile family: one run loop over plan::plan_profile's chunks; a ProfileCall names the form
-  enum class ProfileKind { Profile, TopK, Hits, Summary, Targets, TargetsSummary };
+  enum class ProfileKind { Profile, TopK, Hits, Summary, Targets, TargetsSummary, TargetsTopK, TargetsHits };
   struct HitsCall {
     int32_t min_score;
     const int32_t* d_thresholds;
@@ -422,22 +466,21 @@ class HipEngine {
     const int64_t* d_starts;  // device [T + 1], or null: h_starts goes up with the plan buffer
     const int64_t* h_starts;
     int64_t T;
-    Result* d_out;            // Targets only
+    Result* d_out;            // Targets: [n, T]; TargetsTopK: [n, T, K]
   };
   struct ProfileCall {
     ProfileKind kind = ProfileKind::Profile;
     void* d_dst = nullptr;  // Profile: ProfileEntry [poffsets[n]], written in one chunk; TopK: Result [n, K]
-    int K = 0;              // TopK
+    int K = 0;              // TopK, TargetsTopK
     int64_t radius = 0;     // TopK, Hits: > 0 selects among the peaks of that radius only
-    HitsCall hits{};        // Hits
+    HitsCall hits{};        // Hits; TargetsHits: over pairs (d_hoffsets is toffsets, d_thresholds int32 [n * T])
     SummaryCall summary{};  // Summary, TargetsSummary
-    TargetsCall targets{};  // Targets, TargetsSummary
+    TargetsCall targets{};  // Targets, TargetsSummary, TargetsTopK, TargetsHits
   };
   void run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
                    const ProfileCall& call, hipStream_t stream);
-  // These throw unless the call is allowed and touch nothing: T and starts; bins, width and the batch's exactness
-  // bound (bounds::summary_exact); the target set, then the summary's checks over the call's largest target profile.
-  void check_targets_call(const int64_t* h_starts, int64_t T) const;
+  // These throw unless the call is allowed and touch nothing: bins, width and the batch's exactness bound
+  // (bounds::summary_exact); the target set (check_targets_call), then the summary's checks over the call's largest target profile.
   void check_summary(const int64_t* h_offsets, int64_t n, int32_t bins, int32_t width) const;
   void check_targets_summary(const int64_t* h_offsets, int64_t n, const int64_t* h_starts, int64_t T, int32_t bins,
                              int32_t width) const;

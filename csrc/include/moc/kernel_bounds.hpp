@@ -185,6 +185,20 @@ inline int64_t targets_pair_count(int64_t len, int64_t L2, bool spec) {
   return len - L2 + (spec || len == L2 ? 1 : 0);
 }
 
+// ---- per-target top-K and threshold hits (targets_rows_kernels.hip; definitions: moc/cpu_engine.hpp
+// targets_topk_batch_cpu / targets_hits_batch_cpu): the lane groups of the multi-target search. The count and
+// compaction kernels take targets_group's choice (measured crossings: four lanes ahead at slices of 20 entries and
+// behind at 46, sixteen level with a wave at 410 — 1.63 against 1.66 ms — and behind it at 826). The top-K kernel's 16-lane range ends
+// earlier. Measured at K = 4 on input6-shaped records (profiles/targets_rows/README.md): sixteen lanes lead a wave at
+// slices of 202 entries (1.67 against 1.82 ms) and trail it at 410 (2.08 against 1.48), so the crossing lies
+// somewhere in 202 .. 410. kTargetsTopKGroup16MaxSlice = 256 was chosen inside that bracket because it is the number
+// of slice keys a wave holds in registers (four per lane, 4 * 64; the rest is re-read once per round) — a structural
+// reason to prefer that point of the bracket, not a measured crossing. Tuning constants only.
+constexpr int64_t kTargetsTopKGroup16MaxSlice = 256;
+inline int targets_topk_group(int64_t max_slice) {
+  return max_slice <= kTargetsGroup4MaxSlice ? 4 : max_slice <= kTargetsTopKGroup16MaxSlice ? 16 : 64;
+}
+
 // Form bits reported per solve (EngineStats::forms; Python: stats()["forms"]).
 enum FormBits : int32_t {
   kFormSwipeKBits = 1,    // swipe, int16 keys with k bits

@@ -489,6 +489,101 @@ void targets_summary_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L
   });
 }
 
+namespace {
+// Pair (record, target q)'s place in the record's catalog profile: fits, the slice's first catalog offset and
+// entry count, and whether the boundary entry takes part (then its score, summed from the letters).
+struct TargetPair {
+  bool fits = false, boundary = false;
+  int64_t b = 0, slice = 0;
+  int32_t bscore = 0;
+};
+inline TargetPair target_pair(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2,
+                              const int64_t* starts, int64_t q, Semantics sem) {
+  TargetPair p;
+  p.b = starts[q];
+  const int64_t len = starts[q + 1] - p.b;
+  p.fits = L2 >= 1 && L2 <= len && L2 <= L1;
+  if (!p.fits) return p;
+  p.slice = len - L2;  // b + slice <= L1 - L2 <= C
+  p.boundary = sem == Semantics::Spec || p.slice == 0;
+  if (p.boundary) {
+    const uint8_t* a = s1 + p.b + p.slice;
+    for (int64_t l = 0; l < L2; ++l) p.bscore += t.lut[s2[l] * kLutStride + a[l]];
+  }
+  return p;
+}
+}  // namespace
+
+void targets_topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                            const int64_t* starts, int64_t T, int K, Result* out, Semantics sem, int num_threads) {
+  check_targets(starts, T, L1);
+  if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
+    thread_local std::vector<uint64_t> keys;
+    const int64_t L2 = batch.length(i);
+    for (int64_t q = 0; q < T; ++q) {
+      Result* row = out + (i * T + q) * K;
+      const TargetPair p = target_pair(t, s1, L1, batch.record(i), L2, starts, q, sem);
+      keys.clear();
+      for (int64_t o = 0; o < p.slice; ++o) keys.push_back(profile_key(prof[p.b + o], o));
+      if (p.boundary) keys.push_back(profile_key(ProfileEntry{p.bscore, 0}, p.slice));
+      const int64_t m = std::min<int64_t>(K, static_cast<int64_t>(keys.size()));
+      std::partial_sort(keys.begin(), keys.begin() + m, keys.end(), std::greater<uint64_t>());
+      for (int64_t j = 0; j < m; ++j) {
+        const int64_t o = 0xffffffffu - static_cast<uint32_t>(keys[j]);
+        row[j] = o < p.slice ? Result{prof[p.b + o].score, static_cast<int32_t>(o), prof[p.b + o].k}
+                             : Result{p.bscore, static_cast<int32_t>(o), 0};
+      }
+      for (int64_t j = m; j < K; ++j) row[j] = no_candidate();
+    }
+    (void)C;
+  });
+}
+
+void targets_hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                            const int64_t* starts, int64_t T, int32_t min_score, const int32_t* thresholds,
+                            int64_t* toffsets, Result* rows, int64_t cap, Semantics sem, int num_threads) {
+  check_targets(starts, T, L1);
+  if (cap < 0 || (cap > 0 && !rows)) throw Error("hits: cap rows need a rows buffer (cap = 0 counts only)");
+  if (!toffsets) throw Error("hits: no hoffsets buffer");
+  const int64_t n_pairs = batch.size() * T;
+  auto threshold = [&](int64_t pair) { return thresholds ? thresholds[pair] : min_score; };
+  // phase 1: counts into toffsets[pair + 1], then their running totals
+  toffsets[0] = 0;
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
+    const int64_t L2 = batch.length(i);
+    for (int64_t q = 0; q < T; ++q) {
+      const TargetPair p = target_pair(t, s1, L1, batch.record(i), L2, starts, q, sem);
+      const int32_t tp = threshold(i * T + q);
+      int64_t c = 0;
+      for (int64_t o = 0; o < p.slice; ++o) c += prof[p.b + o].score >= tp ? 1 : 0;
+      if (p.boundary && p.bscore >= tp) ++c;
+      toffsets[i * T + q + 1] = c;
+    }
+    (void)C;
+  });
+  for (int64_t pair = 0; pair < n_pairs; ++pair) toffsets[pair + 1] += toffsets[pair];
+  if (cap == 0 || toffsets[n_pairs] == 0) return;
+  // phase 2: fill, every row under the capacity contract
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
+    if (toffsets[i * T] >= cap || toffsets[i * T] == toffsets[(i + 1) * T]) return;
+    const int64_t L2 = batch.length(i);
+    for (int64_t q = 0; q < T; ++q) {
+      int64_t at = toffsets[i * T + q];
+      if (at >= cap) return;
+      if (at == toffsets[i * T + q + 1]) continue;
+      const TargetPair p = target_pair(t, s1, L1, batch.record(i), L2, starts, q, sem);
+      const int32_t tp = threshold(i * T + q);
+      for (int64_t o = 0; o < p.slice && at < cap; ++o) {
+        const ProfileEntry& e = prof[p.b + o];
+        if (e.score >= tp) rows[at++] = Result{e.score, static_cast<int32_t>(o), e.k};
+      }
+      if (p.boundary && p.bscore >= tp && at < cap) rows[at++] = Result{p.bscore, static_cast<int32_t>(p.slice), 0};
+    }
+    (void)C;
+  });
+}
+
 void topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch, int K, Result* out,
                     Semantics sem, int num_threads, int64_t radius) {
   if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));

@@ -112,7 +112,8 @@ int parse_preload_set(const char* s) {
                {"swipe33", kPreloadSwipeP33}, {"tile16", kPreloadTile16}, {"mfma", kPreloadMfma},
                {"profile", kPreloadProfile}, {"report", kPreloadReport}, {"hits", kPreloadHits},
                {"wire", kPreloadWire}, {"peaks", kPreloadPeaks}, {"summary", kPreloadSummary},
-               {"targets", kPreloadTargets}, {"targets_summary", kPreloadTargetsSummary}};
+               {"targets", kPreloadTargets}, {"targets_summary", kPreloadTargetsSummary},
+               {"targets_rows", kPreloadTargetsRows}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -1060,11 +1061,12 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
       {"moc.solve_profile_device", 16},        {"moc.solve_topk_device", 16},
       {"moc.solve_hits_device", 16 | 64},      {"moc.solve_summary_device", 16 | 512},
       {"moc.solve_targets_device", 16 | 1024}, {"moc.solve_targets_summary_device", 16 | 2048},
+      {"moc.solve_targets_topk_device", 16 | 4096}, {"moc.solve_targets_hits_device", 16 | 8192},
   };
   const ProfileKind kind = call.kind;
   const KindFacts& facts = kFacts[static_cast<int>(kind)];
   if (!have_problem_) throw Error("HipEngine: profile / top-K before set_problem");
-  if (kind == ProfileKind::TopK) check_topk_k(call.K);
+  if (kind == ProfileKind::TopK || kind == ProfileKind::TargetsTopK) check_topk_k(call.K);
   check_peaks_radius(call.radius);
   finish_wire();
   MOC_HIP_CHECK(hipSetDevice(device_));
@@ -1073,7 +1075,8 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   if (!stream) stream = s_compute_;
   const bool chunked = kind != ProfileKind::Profile;  // through the bounded scratch
   const bool peaks = chunked && call.radius > 0;  // the distinct forms: a byte of peak marks beside every scratch entry
-  const bool targets = kind == ProfileKind::Targets || kind == ProfileKind::TargetsSummary;
+  const bool targets = kind == ProfileKind::Targets || kind == ProfileKind::TargetsSummary ||
+                       kind == ProfileKind::TargetsTopK || kind == ProfileKind::TargetsHits;
   const int64_t entry_bytes = static_cast<int64_t>(sizeof(ProfileEntry)) + (peaks ? 1 : 0);
   const TargetsCall& tc = call.targets;
   // throws for a batch past the record or length limits, before the trace range opens and anything is queued
@@ -1091,6 +1094,9 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   if (kind == ProfileKind::Hits)
     ensure(d_hits_sums_, d_hits_sums_cap_,
            sizeof(int64_t) * static_cast<size_t>((pp.max_records + bounds::kHitsScanBlockRecords - 1) / bounds::kHitsScanBlockRecords));
+  if (kind == ProfileKind::TargetsHits)  // the same block sums over the chunk's pairs
+    ensure(d_hits_sums_, d_hits_sums_cap_,
+           sizeof(int64_t) * static_cast<size_t>((pp.max_records * tc.T + bounds::kHitsScanBlockRecords - 1) / bounds::kHitsScanBlockRecords));
   char* h_plan = static_cast<char*>(h_plan_);
   std::memcpy(h_plan, pp.poff.data(), pp.starts_off);
   std::memcpy(h_plan + pp.starts_off, pp.starts.data(), pp.targets_off - pp.starts_off);
@@ -1143,7 +1149,10 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
       tsa.ta.view = view;
       tsa.ta.starts = d_tstarts;
       tsa.ta.T = static_cast<int32_t>(tc.T);
-      tsa.ta.group = targets_group_ ? targets_group_ : bounds::targets_group(std::max<int64_t>(pp.max_target - c.min_l2, 0));
+      const int64_t max_slice = std::max<int64_t>(pp.max_target - c.min_l2, 0);
+      tsa.ta.group = targets_group_ ? targets_group_
+                     : kind == ProfileKind::TargetsTopK ? bounds::targets_topk_group(max_slice)
+                                                        : bounds::targets_group(max_slice);
       tsa.ta.out = tc.d_out;
     }
     switch (kind) {
@@ -1189,6 +1198,19 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
         tsa.width = call.summary.width;
         dev::launch_targets_summary(tsa, pv, bv, stream);
         break;
+      case ProfileKind::TargetsTopK: dev::launch_targets_topk(tsa.ta, call.K, pv, bv, stream); break;
+      case ProfileKind::TargetsHits: {
+        dev::TargetsHitsArgs tha;
+        tha.ta = tsa.ta;
+        tha.thresholds = call.hits.d_thresholds;
+        tha.min_score = call.hits.min_score;
+        tha.toffsets = call.hits.d_hoffsets;
+        tha.sums = static_cast<int64_t*>(d_hits_sums_);
+        tha.rows = call.hits.d_rows;
+        tha.cap = call.hits.cap;
+        dev::launch_targets_hits(tha, pv, bv, stream);
+        break;
+      }
     }
     if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
   }
@@ -1415,6 +1437,100 @@ void HipEngine::targets_summary_placed(Placed& p, const int64_t* starts, int64_t
                                reinterpret_cast<int32_t*>(d + sbytes), bins, lo, width, s_compute_);
   finish_placed(p, {{summary_out, sbytes}, {hist_out, hbytes}});
   stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1);
+}
+
+// ---- per-target top-K and threshold hits ----------------------------------------------------------------
+void HipEngine::solve_targets_topk_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                          int64_t n, const int64_t* d_starts, const int64_t* h_starts, int64_t T, int K,
+                                          Result* d_out, hipStream_t stream) {
+  check_targets_call(h_starts, T);  // before any launch or change of state
+  check_topk_k(K);
+  if (n > 0 && !d_out) throw Error("targets: no rows buffer");
+  const TargetsCall tc{d_starts, h_starts, T, d_out};
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::TargetsTopK, nullptr, K, 0, {}, {}, tc}, stream);  // n <= 0: no launch
+}
+
+void HipEngine::solve_targets_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
+                                   int64_t T, int K, Result* out) {
+  check_targets_call(starts, T);
+  check_topk_k(K);
+  Placed p = place_host(codes, offsets, n, rows_bytes(n * T, K));
+  if (p.n > 0) targets_topk_placed(p, starts, T, K, out);
+}
+
+// d_out: rows (n * T * K Result); starts travel with the plan buffer
+void HipEngine::targets_topk_placed(Placed& p, const int64_t* starts, int64_t T, int K, Result* out) {
+  solve_targets_topk_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, K,
+                            static_cast<Result*>(slots_[0]->d_out), s_compute_);
+  finish_placed(p, {{out, rows_bytes(p.n * T, K)}});
+  stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1);
+}
+
+void HipEngine::solve_targets_hits_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                          int64_t n, const int64_t* d_starts, const int64_t* h_starts, int64_t T,
+                                          int32_t min_score, const int32_t* d_thresholds, int64_t* d_toffsets,
+                                          Result* d_rows, int64_t cap, hipStream_t stream) {
+  check_targets_call(h_starts, T);  // before any launch or change of state
+  if (cap < 0 || (cap > 0 && !d_rows)) throw Error("hits: cap rows need a rows buffer (cap = 0 counts only)");
+  if (!d_toffsets) throw Error("hits: no hoffsets buffer");
+  if (n <= 0) {  // no launch: the index of an empty batch is its single 0
+    finish_wire();
+    MOC_HIP_CHECK(hipSetDevice(device_));
+    MOC_HIP_CHECK(hipMemsetAsync(d_toffsets, 0, sizeof(int64_t), stream ? stream : s_compute_));
+    ev_select_used_ = 0;
+    return;
+  }
+  const HitsCall hc{min_score, d_thresholds, d_toffsets, d_rows, d_rows ? cap : 0};
+  const TargetsCall tc{d_starts, h_starts, T, nullptr};
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::TargetsHits, nullptr, 0, 0, hc, {}, tc}, stream);
+}
+
+void HipEngine::solve_targets_hits(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
+                                   int64_t T, int32_t min_score, const int32_t* thresholds, int64_t* toffsets_out,
+                                   std::vector<Result>& rows_out, int64_t max_rows_hint) {
+  check_targets_call(starts, T);
+  finish_wire();
+  MOC_HIP_CHECK(hipSetDevice(device_));
+  rows_out.clear();
+  hits_passes_ = 0;
+  toffsets_out[0] = 0;
+  Placed p = place_host(codes, offsets, n, hits_index_bytes(n * T) + thresholds_bytes(n * T));
+  if (p.n > 0) targets_hits_placed(p, starts, T, min_score, thresholds, toffsets_out, rows_out, max_rows_hint);
+}
+
+// d_out: toffsets (n T + 1) | thresholds (n T); the rows have hits' buffer, which the second pass may grow; starts
+// travel with the plan buffer
+void HipEngine::targets_hits_placed(Placed& p, const int64_t* starts, int64_t T, int32_t min_score,
+                                    const int32_t* thresholds, int64_t* toffsets_out, std::vector<Result>& rows_out,
+                                    int64_t max_rows_hint) {
+  const int64_t pairs = p.n * T;
+  const size_t hbytes = hits_index_bytes(pairs), tbytes = thresholds_bytes(pairs);
+  char* d = static_cast<char*>(slots_[0]->d_out);
+  if (thresholds) copy_h2d(d + hbytes, thresholds, tbytes, s_compute_);
+  int64_t cap = std::max<int64_t>(max_rows_hint < 0 ? pairs : max_rows_hint, 1);
+  double kernel_ms = 0;
+  for (;;) {
+    ensure(d_hits_rows_, d_hits_rows_cap_, sizeof(Result) * static_cast<size_t>(cap));
+    solve_targets_hits_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, min_score,
+                              thresholds ? reinterpret_cast<const int32_t*>(d + hbytes) : nullptr,
+                              reinterpret_cast<int64_t*>(d), static_cast<Result*>(d_hits_rows_), cap, s_compute_);
+    copy_d2h(toffsets_out, d, hbytes, s_compute_);
+    MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+    kernel_ms += device_kernel_ms();
+    ++hits_passes_;
+    if (toffsets_out[pairs] <= cap || hits_passes_ == 2) break;
+    cap = toffsets_out[pairs];  // exact: the second pass fits
+  }
+  const int64_t total = toffsets_out[pairs];
+  if (total > cap) throw Error("hits: the second pass did not fit its own count");
+  rows_out.resize(static_cast<size_t>(total));
+  const size_t rbytes = sizeof(Result) * static_cast<size_t>(total);
+  if (rbytes) {
+    copy_d2h(rows_out.data(), d_hits_rows_, rbytes, s_compute_);
+    MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
+  }
+  host_call_stats(p, kernel_ms, hbytes * static_cast<size_t>(hits_passes_) + rbytes);
+  stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1) + (thresholds ? static_cast<int64_t>(tbytes) : 0);
 }
 
 // ---- alignment report -----------------------------------------------------------------------------------
@@ -1702,6 +1818,30 @@ void HipEngine::solve_targets_summary_wire(const WireBatch& b, const int64_t* st
   finish_wire();
   Placed p = place_wire(b, summary_bytes(b.n * T) + hist_bytes(b.n * T, bins));
   if (p.n > 0) targets_summary_placed(p, starts, T, summary_out, hist_out, bins, lo, width);
+}
+
+void HipEngine::solve_targets_topk_wire(const WireBatch& b, const int64_t* starts, int64_t T, int K, Result* out) {
+  check_targets_call(starts, T);
+  check_topk_k(K);
+  validate_wire(b);
+  require_host_batch(b);
+  finish_wire();
+  Placed p = place_wire(b, rows_bytes(b.n * T, K));
+  if (p.n > 0) targets_topk_placed(p, starts, T, K, out);
+}
+
+void HipEngine::solve_targets_hits_wire(const WireBatch& b, const int64_t* starts, int64_t T, int32_t min_score,
+                                        const int32_t* thresholds, int64_t* toffsets_out, std::vector<Result>& rows_out,
+                                        int64_t max_rows_hint) {
+  check_targets_call(starts, T);
+  validate_wire(b);
+  require_host_batch(b);
+  finish_wire();
+  rows_out.clear();
+  hits_passes_ = 0;
+  toffsets_out[0] = 0;
+  Placed p = place_wire(b, hits_index_bytes(b.n * T) + thresholds_bytes(b.n * T));
+  if (p.n > 0) targets_hits_placed(p, starts, T, min_score, thresholds, toffsets_out, rows_out, max_rows_hint);
 }
 
 void HipEngine::report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks) {

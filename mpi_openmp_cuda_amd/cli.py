@@ -16,7 +16,8 @@ from .models.problem import Problem
 from .models.scoring import Semantics
 from .parallel import dist as D
 from .parallel.search import DistributedSearch
-from .utils.io import (format_hits, format_report, format_summary, format_targets, format_targets_summary, format_topk,
+from .utils.io import (format_hits, format_report, format_summary, format_targets, format_targets_hits,
+                       format_targets_summary, format_targets_topk, format_topk,
                        write_results)
 
 
@@ -81,6 +82,18 @@ def main(argv=None) -> int:
                          "the most standard deviations above the rest of its own profile")
     ap.add_argument("--target-hist", default=None, metavar="LO:WIDTH:BINS",
                     help="with --target-summary: one more line '    hist: c0 c1 ...' per target, the bins of --hist")
+    ap.add_argument("--target-top", type=int, default=None, metavar="K",
+                    help="with --targets: the K (1..64) best placements of the record inside every target; under each "
+                         "'  target t: ...' line (rank 1) print '    top j: score: S, n: N, k: K' for the ranks j >= 2 "
+                         "that exist. Not with --target-summary, --target-min-score or --target-within")
+    ap.add_argument("--target-min-score", type=int, default=None, metavar="T",
+                    help="with --targets: under each '  target t: ...' line print '    hit: score: S, n: N, k: K' for "
+                         "every placement inside that target that scores at least T (an int32; a negative T takes the "
+                         "= form), by ascending n. Not with --target-summary, --target-top or --target-within")
+    ap.add_argument("--target-within", type=int, default=None, metavar="D",
+                    help="with --targets: as --target-min-score with every (record, target) pair's own threshold, that "
+                         "target's best score minus D (D >= 0). Not with --target-summary, --target-top or "
+                         "--target-min-score")
     a = ap.parse_args(argv)
     if not 1 <= a.top <= 64:
         ap.error("--top K: K must be in 1..64")
@@ -123,6 +136,19 @@ def main(argv=None) -> int:
         ap.error("--summary does not combine with --top K > 1, --show-alignment, --min-score or --within")
     if a.min_score is not None and not -2 ** 31 <= a.min_score < 2 ** 31:
         ap.error("--min-score T: T must be an int32")
+    target_rows_flags = [f for f, v in (("--target-top", a.target_top), ("--target-min-score", a.target_min_score),
+                                        ("--target-within", a.target_within)) if v is not None]
+    if target_rows_flags:
+        if a.targets is None:
+            ap.error(f"{target_rows_flags[0]} needs --targets FILE")
+        if len(target_rows_flags) > 1 or a.target_summary:
+            ap.error("--target-top, --target-min-score, --target-within and --target-summary exclude each other")
+        if a.target_top is not None and not 1 <= a.target_top <= 64:
+            ap.error("--target-top K: K must be in 1..64")
+        if a.target_min_score is not None and not -2 ** 31 <= a.target_min_score < 2 ** 31:
+            ap.error("--target-min-score T: T must be an int32")
+        if a.target_within is not None and a.target_within < 0:
+            ap.error("--target-within D: D must be >= 0")
     if a.targets is not None:
         if a.top > 1 or a.show_alignment or want_hits or a.distinct is not None or a.summary or a.hist is not None:
             ap.error("--targets does not combine with --top K > 1, --show-alignment, --min-score, --within, "
@@ -199,9 +225,16 @@ def main(argv=None) -> int:
     summary = None
     target_rows = None
     target_summary = None
+    target_topk = None
+    target_hits = None
     if a.targets is not None:
         try:
-            if a.target_summary:
+            if a.target_top is not None:
+                target_topk = search.run_targets_topk(problem, target_set, a.target_top, Semantics.parse(a.semantics))
+            elif a.target_min_score is not None or a.target_within is not None:
+                target_hits = search.run_targets_hits(problem, target_set, a.target_min_score, a.target_within,
+                                                      Semantics.parse(a.semantics))
+            elif a.target_summary:
                 target_summary = search.run_targets_summary(problem, target_set, *target_hist_args,
                                                             semantics=Semantics.parse(a.semantics))
             else:
@@ -247,6 +280,12 @@ def main(argv=None) -> int:
             sys.stdout.flush()
         elif a.target_summary:
             sys.stdout.write(format_targets_summary(*target_summary))
+            sys.stdout.flush()
+        elif target_topk is not None:
+            sys.stdout.write(format_targets_topk(target_topk[:, 0, 0], target_topk))
+            sys.stdout.flush()
+        elif target_hits is not None:
+            sys.stdout.write(format_targets_hits(target_hits[0][:, 0], *target_hits))
             sys.stdout.flush()
         elif a.targets is not None:
             sys.stdout.write(format_targets(target_rows[:, 0], target_rows))

@@ -621,6 +621,92 @@ def targets_zscore(summary):
     return torch.where(ok, (mx.to(torch.float64) - mean) / sd, torch.full_like(mean, float("nan"))).contiguous()
 
 
+# ---- per-target top-K and threshold hits: the rows of every (record, target) pair's target profile
+def _targets_rows_check(rc):
+    """A native per-target top-K / hits call's status: target-set errors ("targets:"), a K out of range ("top-K:")
+    and buffer errors ("hits:") are ValueErrors, anything else a NativeError."""
+    if rc != 0:
+        msg = _lib.lib().moc_last_error().decode(errors="replace")
+        if msg.startswith(("targets:", "top-K:", "hits:")):
+            raise ValueError(msg)
+        raise _lib.NativeError(msg)
+
+
+def _targets_hits_thresholds(n: int, T: int, min_score, thresholds, within, best_rows):
+    """:func:`_hits_thresholds` over pairs: exactly one of the three -> (scalar int, int32 [n * T] pair-major array or
+    None). ``thresholds``: [n, T], or [n] broadcast over the targets. ``best_rows``: a call returning the
+    multi-target rows [n, T, 3] (``within`` only); a pair's threshold is its own best score minus D."""
+    if sum(x is not None for x in (min_score, thresholds, within)) != 1:
+        raise ValueError("hits: give exactly one of min_score, thresholds, within")
+    if min_score is not None:
+        m = int(min_score)
+        if not _I32.min <= m <= _I32.max:
+            raise ValueError(f"hits: min_score {m} is not an int32")
+        return m, None
+    if thresholds is not None:
+        t = np.asarray(thresholds)
+        if t.shape not in ((n, T), (n,)) or not np.issubdtype(t.dtype, np.integer):
+            raise ValueError(f"hits: thresholds must be {n} x {T} integers (one per pair) or {n} (one per record), "
+                             f"got shape {t.shape}")
+        if t.size and (t.min() < _I32.min or t.max() > _I32.max):
+            raise ValueError("hits: thresholds must fit int32")
+        if t.ndim == 1:
+            t = np.broadcast_to(t[:, None], (n, T))
+        return 0, np.ascontiguousarray(t, dtype=np.int32).reshape(-1)
+    if int(within) < 0:
+        raise ValueError(f"hits: within must be >= 0, got {int(within)}")
+    return 0, within_thresholds(np.asarray(best_rows())[:, :, 0], within)
+
+
+def search_targets_topk_cpu(problem: Problem, targets, K: int, semantics=Semantics.REFERENCE,
+                            threads: int = 0) -> np.ndarray:
+    """Per-target top-K on the CPU engine. ``problem.seq1`` is the catalog and ``targets`` its :class:`TargetSet` (or
+    just the starts). Returns int32 [n, T, K, 3]: ``out[i, t]`` is exactly :func:`search_topk_cpu`'s [K, 3] block of
+    record i against target t alone — the pair's best placements in the order higher score, then smaller n, n
+    relative to the target's start, padded with (INT32_MIN, 0, 0) — so no row straddles two targets. ``K = 1`` is
+    :func:`search_targets_cpu`. ValueError for an invalid target set ("targets: ...", first) and for K outside
+    1..64."""
+    starts = _starts_of(targets, problem.L1)
+    K = _check_k(K)
+    T = starts.shape[0] - 1
+    out = np.zeros((problem.n, T, K, 3), np.int32)
+    _targets_rows_check(_lib.lib().moc_cpu_targets_topk(
+        _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+        _lib.ptr(problem.offsets), problem.n, _lib.ptr(starts), T, int(Semantics.parse(semantics)), int(threads), K,
+        _lib.ptr(out)))
+    return out
+
+
+def search_targets_hits_cpu(problem: Problem, targets, min_score=None, thresholds=None, within=None,
+                            semantics=Semantics.REFERENCE, threads: int = 0):
+    """Per-target threshold hits on the CPU engine: ``(rows, toffsets)``. Pair p = i * T + t's hits are exactly
+    :func:`search_hits_cpu`'s of record i against target t alone under the pair's threshold — int32 rows (score, n
+    relative to the target's start, k), ascending in n, at ``rows[toffsets[p]:toffsets[p + 1]]``; ``toffsets`` is
+    int64 [n * T + 1]. Exactly one of ``min_score`` (one int32 for the call; INT32_MIN selects every pair's whole
+    target profile), ``thresholds`` (int32 [n, T], or [n] broadcast over the targets) and ``within`` (D >= 0: every
+    placement within D of the pair's own best score, from :func:`search_targets_cpu`). A record longer than a target
+    has no hits there. ValueError for an invalid target set ("targets: ...", first) and for malformed thresholds."""
+    sem = Semantics.parse(semantics)
+    starts = _starts_of(targets, problem.L1)
+    T = starts.shape[0] - 1
+    m, t = _targets_hits_thresholds(problem.n, T, min_score, thresholds, within,
+                                    lambda: search_targets_cpu(problem, starts, sem, threads))
+    toffsets = np.zeros(problem.n * T + 1, np.int64)
+
+    def call(rows, cap):
+        _targets_rows_check(_lib.lib().moc_cpu_targets_hits(
+            _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+            _lib.ptr(problem.offsets), problem.n, _lib.ptr(starts), T, int(sem), int(threads), m, _lib.ptr(t),
+            _lib.ptr(toffsets), _lib.ptr(rows), cap))
+
+    call(None, 0)  # counts
+    total = int(toffsets[-1])
+    rows = np.zeros((total, 3), np.int32)
+    if total:
+        call(rows, total)
+    return rows, toffsets
+
+
 # ---- alignment report: sign counts and marker bytes of result rows (csrc/include/moc/cpu_engine.hpp)
 REPORT_EMPTY = int(np.iinfo(np.int64).min)        # report_scores of an empty row (score INT32_MIN, top-K padding)
 REPORT_INVALID = int(np.iinfo(np.int64).min) + 1  # ... of a row whose (n, k) does not place the record in Seq1
@@ -1286,6 +1372,162 @@ class HipSearchEngine:
         del keep
         return out
 
+    # ---- per-target top-K and threshold hits (byte letters, dense offsets; csrc/src/hip/targets_rows_kernels.hip)
+    def solve_targets_topk(self, codes: np.ndarray, offsets: np.ndarray, targets, K: int) -> np.ndarray:
+        """Host CSR -> int32 [n, T, K, 3] rows as :func:`search_targets_topk_cpu` returns them, against the engine's
+        Seq1 as the catalog of ``targets``. One pass: the chunks of :meth:`solve_targets` with the per-target top-K
+        kernel behind each chunk's catalog profile — 12 T K bytes come back per record, never the profile.
+        Synchronous; ``stats()["kernels"]`` names ``targets_topk``. ValueError for an invalid target set (first) and
+        for K outside 1..64, raised before anything is launched and without a change to ``stats()``."""
+        starts = _starts_of(targets, self.problem_L1)
+        K = _check_k(K)
+        T = starts.shape[0] - 1
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        out = np.zeros((n, T, K, 3), np.int32)
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_topk(self._h, _lib.ptr(codes), _lib.ptr(offsets), n,
+                                                                     _lib.ptr(starts), T, K, _lib.ptr(out)))
+        return out
+
+    def solve_targets_hits(self, codes: np.ndarray, offsets: np.ndarray, targets, min_score=None, thresholds=None,
+                           within=None, max_rows: Optional[int] = None):
+        """Host CSR -> ``(rows, toffsets)`` as :func:`search_targets_hits_cpu` returns them (exactly one of
+        ``min_score``, ``thresholds`` — [n, T], or [n] broadcast over the targets — and ``within``, each pair's own
+        best score from :meth:`solve_targets` on this engine minus D). One pass over the chunks of
+        :meth:`solve_targets` with count, prefix sum over the pairs and compaction behind each chunk's catalog
+        profile. Optimistic: room for ``max_rows`` rows (default n T) and exactly one more pass when more entries
+        qualify (:meth:`hits_passes`). Synchronous; ``stats()["kernels"]`` names ``targets_hits``. ValueError as
+        search_targets_hits_cpu, before anything is launched."""
+        starts = _starts_of(targets, self.problem_L1)
+        T = starts.shape[0] - 1
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        m, t = _targets_hits_thresholds(n, T, min_score, thresholds, within,
+                                        lambda: self.solve_targets(codes, offsets, starts))
+        toffsets = np.zeros(n * T + 1, np.int64)
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_hits(
+            self._h, _lib.ptr(codes), _lib.ptr(offsets), n, _lib.ptr(starts), T, m, _lib.ptr(t),
+            -1 if max_rows is None else int(max_rows), _lib.ptr(toffsets), None, 0))
+        total = int(toffsets[-1])
+        rows = np.zeros((total, 3), np.int32)
+        _lib.check(_lib.lib().moc_engine_hits_rows(_lib.ptr(rows) if total else None, total))
+        return rows, toffsets
+
+    def solve_targets_topk_device(self, codes_t, offsets_t, h_offsets: np.ndarray, targets, K: int, out_t=None,
+                                  starts_t=None, stream=None):
+        """Device-resident batch (as :meth:`solve_device`) -> ``out_t``, an int32 [n, T, K, 3] tensor of per-target
+        top-K rows on the codes' device (allocated when None; every row is written). ``starts_t`` as
+        :meth:`solve_targets_device`. Queued on ``stream`` (default: the current stream); returns immediately.
+        ValueError as :meth:`solve_targets_topk`."""
+        import torch
+
+        starts = _starts_of(targets, self.problem_L1)
+        K = _check_k(K)
+        T = starts.shape[0] - 1
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        n = h_offsets.shape[0] - 1
+        assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        if out_t is None:
+            out_t = torch.empty((n, T, K, 3), dtype=torch.int32, device=codes_t.device)
+        assert out_t.dtype == torch.int32 and out_t.is_contiguous() and tuple(out_t.shape) == (n, T, K, 3)
+        if starts_t is not None:
+            assert starts_t.dtype == torch.int64 and starts_t.is_contiguous() and starts_t.numel() == T + 1
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_topk_device(
+            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
+            n, ctypes.c_void_p(starts_t.data_ptr()) if starts_t is not None else None, _lib.ptr(starts), T, K,
+            ctypes.c_void_p(out_t.data_ptr()), ctypes.c_void_p(stream.cuda_stream)))
+        return out_t
+
+    def solve_targets_hits_device(self, codes_t, offsets_t, h_offsets: np.ndarray, targets, min_score=None,
+                                  thresholds_t=None, cap: Optional[int] = None, rows_t=None, toffsets_t=None,
+                                  starts_t=None, stream=None):
+        """Device-resident batch (as :meth:`solve_device`) -> ``(rows_t, toffsets_t)``: ``toffsets_t`` an int64
+        [n T + 1] tensor, always complete and exact; ``rows_t`` an int32 [cap, 3] tensor (``cap`` default n T) of
+        which the rows with a flat index < cap are written and nothing else is touched — compare
+        ``toffsets_t[-1]`` with ``cap`` after a sync. ``cap = 0`` counts only. Exactly one of ``min_score`` and
+        ``thresholds_t``, an int32 [n, T] tensor on the same device — ``solve_targets_device(...)[..., 0] - D``
+        (in int64, clamped to int32) queued on the same stream gives "within D of each pair's best" without a sync.
+        Both result tensors are allocated when None. Queued on ``stream`` (default: the current stream); returns
+        immediately. ValueError as :meth:`solve_targets_hits`."""
+        import torch
+
+        starts = _starts_of(targets, self.problem_L1)
+        T = starts.shape[0] - 1
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        n = h_offsets.shape[0] - 1
+        if (min_score is None) == (thresholds_t is None):
+            raise ValueError("hits: give exactly one of min_score, thresholds")
+        assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        m = 0
+        if min_score is not None:
+            m = int(min_score)
+            if not _I32.min <= m <= _I32.max:
+                raise ValueError(f"hits: min_score {m} is not an int32")
+        if thresholds_t is not None:
+            if thresholds_t.dtype != torch.int32 or tuple(thresholds_t.shape) != (n, T):
+                raise ValueError(f"hits: thresholds must be an int32 tensor of {n} x {T} entries (one per pair)")
+            assert thresholds_t.is_contiguous() and thresholds_t.device == codes_t.device
+        if cap is None:
+            cap = max(n * T, 1) if rows_t is None else rows_t.shape[0]
+        cap = int(cap)
+        if cap < 0:
+            raise ValueError("hits: cap must be >= 0")
+        if rows_t is None:
+            rows_t = torch.empty((cap, 3), dtype=torch.int32, device=codes_t.device)
+        if toffsets_t is None:
+            toffsets_t = torch.empty(n * T + 1, dtype=torch.int64, device=codes_t.device)
+        assert rows_t.dtype == torch.int32 and rows_t.is_contiguous() and rows_t.dim() == 2 and rows_t.shape[1] == 3
+        assert rows_t.shape[0] >= cap
+        assert toffsets_t.dtype == torch.int64 and toffsets_t.is_contiguous() and toffsets_t.numel() == n * T + 1
+        if starts_t is not None:
+            assert starts_t.dtype == torch.int64 and starts_t.is_contiguous() and starts_t.numel() == T + 1
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_hits_device(
+            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
+            n, ctypes.c_void_p(starts_t.data_ptr()) if starts_t is not None else None, _lib.ptr(starts), T, m,
+            ctypes.c_void_p(thresholds_t.data_ptr()) if thresholds_t is not None else None,
+            ctypes.c_void_p(toffsets_t.data_ptr()), ctypes.c_void_p(rows_t.data_ptr()) if cap else None, cap,
+            ctypes.c_void_p(stream.cuda_stream)))
+        return rows_t, toffsets_t
+
+    def solve_targets_topk_wire(self, ws, targets, K: int, shift: int = 0) -> np.ndarray:
+        """Host wire batch -> int32 [n, T, K, 3] per-target top-K rows, as :meth:`solve_targets_topk` on the decoded
+        records. See :meth:`solve_profile_wire`."""
+        starts = _starts_of(targets, self.problem_L1)
+        K = _check_k(K)
+        T = starts.shape[0] - 1
+        b, keep = wire_batch_of(ws, shift)
+        out = np.zeros((ws.n, T, K, 3), np.int32)
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_topk_wire(self._h, ctypes.byref(b), _lib.ptr(starts), T,
+                                                                          K, _lib.ptr(out)))
+        del keep
+        return out
+
+    def solve_targets_hits_wire(self, ws, targets, min_score=None, thresholds=None, within=None,
+                                max_rows: Optional[int] = None, shift: int = 0):
+        """Host wire batch -> ``(rows, toffsets)``, as :meth:`solve_targets_hits` on the decoded records (``within``
+        runs :meth:`solve_targets_wire` first). See :meth:`solve_profile_wire`."""
+        starts = _starts_of(targets, self.problem_L1)
+        T = starts.shape[0] - 1
+        n = ws.n
+        m, t = _targets_hits_thresholds(n, T, min_score, thresholds, within,
+                                        lambda: self.solve_targets_wire(ws, starts, shift))
+        b, keep = wire_batch_of(ws, shift)
+        toffsets = np.zeros(n * T + 1, np.int64)
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_hits_wire(
+            self._h, ctypes.byref(b), _lib.ptr(starts), T, m, _lib.ptr(t), -1 if max_rows is None else int(max_rows),
+            _lib.ptr(toffsets), None, 0))
+        del keep
+        total = int(toffsets[-1])
+        rows = np.zeros((total, 3), np.int32)
+        _lib.check(_lib.lib().moc_engine_hits_rows(_lib.ptr(rows) if total else None, total))
+        return rows, toffsets
+
     # ---- per-target profile summary (byte letters, dense offsets; csrc/src/hip/targets_summary_kernels.hip)
     def solve_targets_summary(self, codes: np.ndarray, offsets: np.ndarray, targets, bins: int = 0, lo: int = 0,
                               width: int = 1):
@@ -1609,7 +1851,8 @@ class HipSearchEngine:
         d["kernels"] = [k for b, k in ((1, "swipe"), (2, "short"), (4, "tiles"), (8, "tile16"), (16, "profile"),
                                              (32, "report"), (64, "hits"), (128, "wire"), (256, "peaks"),
                                              (512, "summary"), (1024, "targets"),
-                                             (2048, "targets_summary"))
+                                             (2048, "targets_summary"), (4096, "targets_topk"),
+                                             (8192, "targets_hits"))
                         if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
@@ -1729,6 +1972,20 @@ def align_targets_summary_device(engine: HipSearchEngine, codes_t, offsets_t, h_
     :meth:`HipSearchEngine.solve_targets_summary_device`."""
     return engine.solve_targets_summary_device(codes_t, offsets_t, h_offsets, targets, bins, lo, width, None, None,
                                                None, stream)
+
+
+def align_targets_topk_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, targets, K: int, stream=None):
+    """torch-facing op: the per-target top-K rows as an int32 [n, T, K, 3] tensor on the codes' device; see
+    :meth:`HipSearchEngine.solve_targets_topk_device`."""
+    return engine.solve_targets_topk_device(codes_t, offsets_t, h_offsets, targets, K, None, None, stream)
+
+
+def align_targets_hits_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, targets, min_score=None,
+                              thresholds_t=None, cap: Optional[int] = None, stream=None):
+    """torch-facing op: the per-target threshold hits as ``(rows_t, toffsets_t)`` on the codes' device; see
+    :meth:`HipSearchEngine.solve_targets_hits_device`."""
+    return engine.solve_targets_hits_device(codes_t, offsets_t, h_offsets, targets, min_score, thresholds_t, cap, None,
+                                            None, None, stream)
 
 
 def align_report_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, rows_t, marks: bool = False,

@@ -31,7 +31,8 @@ from ..ops.align import (HipSearchEngine, decode_keys, device_count, keys_to_ord
                         profile_offsets, search_cpu, search_hits_cpu, search_keys_cpu, search_report_cpu,
                         search_summary_cpu, search_targets_cpu, search_targets_summary_cpu, search_topk_cpu,
                          summary_bound, within_thresholds,
-                         TargetSet, check_targets, _summary_args)
+                         TargetSet, check_targets, _summary_args, _check_k, search_targets_hits_cpu,
+                         search_targets_topk_cpu)
 from ..utils.timer import PhaseTimer
 from . import dist as D
 from .partition import CPU_COST, GPU_COST, partition
@@ -338,6 +339,116 @@ class DistributedSearch:
             D.barrier(ctx)
             win.close(unlink=ctx.is_root)
         return rows.astype(np.int32) if ctx.is_root else None
+
+    def _bcast_starts(self, problem: Optional[Problem], targets) -> np.ndarray:
+        """The root's target set (a TargetSet or its starts) as checked starts on every rank; an invalid set raises
+        the same ValueError on every rank."""
+        ctx = self.ctx
+        hdr = None
+        starts = None
+        if ctx.is_root:
+            starts = np.ascontiguousarray(targets.starts if isinstance(targets, TargetSet) else targets,
+                                          dtype=np.int64).reshape(-1)
+            hdr = np.array([starts.shape[0], problem.L1], np.int64)
+        hdr = D.bcast_array(ctx, hdr, 2, np.int64)
+        starts = D.bcast_array(ctx, starts if ctx.is_root else None, int(hdr[0]), np.int64)
+        return check_targets(starts, int(hdr[1]))
+
+    def run_targets_topk(self, problem: Optional[Problem], targets=None, K: int = 1, semantics=Semantics.REFERENCE):
+        """Per-target top-K (ops.align.search_targets_topk_cpu's int32 [n, T, K, 3] rows; ``K`` the same on every rank,
+        ``targets`` as :meth:`run_targets`) for the ``records`` partition: every rank ranks its cost-balanced slice of
+        the node-shared input window against every target, and one MAX all-reduce of an int64 array that is INT64_MIN
+        outside the rank's slice collects the rows (no new transport). Returns the rows on the root, else None. One
+        node; byte letters through the engines' per-target top-K calls."""
+        if self.partition != "records":
+            raise ValueError("per-target top-K runs on record slices (--partition records, one node): the offsets "
+                             "partition combines one packed key per record and cannot carry T K rows")
+        ctx, T = self.ctx, self.timer
+        sem = Semantics.parse(semantics)
+        starts = self._bcast_starts(problem, targets)  # the target set's errors come first
+        K = _check_k(K)
+        nt = starts.shape[0] - 1
+        with T.phase("bcast"):
+            prob, sem, n, total, bounds = self._setup(problem, sem)
+        b, e = int(bounds[ctx.rank]), int(bounds[ctx.rank + 1])
+        with T.phase("distribute"):
+            win = self._open_window(problem, n, total)
+        with T.phase("compute"):
+            rows = np.full((n, nt, K, 3), np.iinfo(np.int64).min, np.int64)
+            if e > b:
+                offsets = np.asarray(win.offsets[b:e + 1])
+                if self.engine is not None:
+                    rows[b:e] = self.engine.solve_targets_topk(np.asarray(win.codes), offsets, starts, K)
+                else:
+                    sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
+                                  offsets - offsets[0])
+                    rows[b:e] = search_targets_topk_cpu(sub, starts, K, sem, self.threads)
+        with T.phase("gather"):
+            rows = D.allreduce_max_int64(ctx, rows.reshape(-1)).reshape(n, nt, K, 3)
+            D.barrier(ctx)
+            win.close(unlink=ctx.is_root)
+        return rows.astype(np.int32) if ctx.is_root else None
+
+    def run_targets_hits(self, problem: Optional[Problem], targets=None, min_score=None, within=None,
+                         semantics=Semantics.REFERENCE):
+        """Per-target threshold hits (ops.align.search_targets_hits_cpu's ``(rows, toffsets)``; exactly one of
+        ``min_score`` and ``within``, the same on every rank; ``targets`` as :meth:`run_targets`) together with the
+        multi-target rows, for the ``records`` partition: every rank computes its cost-balanced slice of the
+        node-shared input window; the root collects the pairs' counts and then the rows as :meth:`run_hits` does, each
+        with one MAX all-reduce of an int64 array that is INT64_MIN outside the rank's slice. ``within`` takes each
+        pair's own best score from the multi-target search of the same slice. Returns ``(best, rows, toffsets)`` on
+        the root — ``best`` the int32 [n, T, 3] multi-target rows — else None. One node; byte letters through the
+        engines' per-target hits calls."""
+        if self.partition != "records":
+            raise ValueError("per-target hits run on record slices (--partition records, one node): the offsets "
+                             "partition combines one packed key per record and cannot carry a list of rows")
+        ctx, T = self.ctx, self.timer
+        sem = Semantics.parse(semantics)
+        starts = self._bcast_starts(problem, targets)  # the target set's errors come first
+        if (min_score is None) == (within is None):
+            raise ValueError("hits: give exactly one of min_score, within")
+        if within is not None and int(within) < 0:
+            raise ValueError(f"hits: within must be >= 0, got {int(within)}")
+        nt = starts.shape[0] - 1
+        with T.phase("bcast"):
+            prob, sem, n, total, bounds = self._setup(problem, sem)
+        b, e = int(bounds[ctx.rank]), int(bounds[ctx.rank + 1])
+        with T.phase("distribute"):
+            win = self._open_window(problem, n, total)
+        lo = np.iinfo(np.int64).min
+
+        def kw(scores):  # the slice's thresholds from the multi-target search just done
+            return {"min_score": int(min_score)} if min_score is not None else \
+                {"thresholds": within_thresholds(scores, within).reshape(-1, nt)}
+
+        with T.phase("compute"):
+            best = np.full((n, nt, 3), lo, np.int64)
+            counts = np.full(n * nt, lo, np.int64)
+            mine = np.zeros((0, 3), np.int32)
+            if e > b:
+                offsets = np.asarray(win.offsets[b:e + 1])
+                if self.engine is not None:
+                    codes = np.asarray(win.codes)
+                    best[b:e] = self.engine.solve_targets(codes, offsets, starts)
+                    mine, h = self.engine.solve_targets_hits(codes, offsets, starts, **kw(best[b:e, :, 0]))
+                else:
+                    sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
+                                  offsets - offsets[0])
+                    best[b:e] = search_targets_cpu(sub, starts, sem, self.threads)
+                    mine, h = search_targets_hits_cpu(sub, starts, semantics=sem, threads=self.threads,
+                                                      **kw(best[b:e, :, 0]))
+                counts[b * nt:e * nt] = np.diff(h)
+        with T.phase("gather"):
+            counts = D.allreduce_max_int64(ctx, counts)
+            best = D.allreduce_max_int64(ctx, best.reshape(-1)).reshape(n, nt, 3)
+            toffsets = np.zeros(n * nt + 1, np.int64)
+            np.cumsum(counts, out=toffsets[1:])
+            rows = np.full((int(toffsets[-1]), 3), lo, np.int64)
+            rows[toffsets[b * nt]:toffsets[e * nt]] = mine
+            rows = D.allreduce_max_int64(ctx, rows.reshape(-1)).reshape(-1, 3)
+            D.barrier(ctx)
+            win.close(unlink=ctx.is_root)
+        return (best.astype(np.int32), rows.astype(np.int32), toffsets) if ctx.is_root else None
 
     def run_targets_summary(self, problem: Optional[Problem], targets=None, bins: int = 0, lo: int = 0, width: int = 1,
                             semantics=Semantics.REFERENCE):

@@ -125,6 +125,63 @@ def format_targets(results, rows, first_index: int = 0) -> str:
     return "".join(out)
 
 
+def _format_targets_under(results, rows, under, first_index: int) -> str:
+    """:func:`format_targets` with the lines ``under(i, t)`` yields below each "  target t: ..." line."""
+    from ..ops.align import as_triples, targets_best
+
+    res = as_triples(results)
+    best, _ = targets_best(rows)
+    none = np.iinfo(np.int32).min
+    out = []
+    for i, (score, n, k) in enumerate(res.tolist()):
+        out.append(f"#{i + first_index}: score: {score}, n: {n}, k: {k}\n")
+        for t, (ts, tn, tk) in enumerate(rows[i].tolist()):
+            out.append(f"  target {t + 1}: none\n" if ts == none else f"  target {t + 1}: score: {ts}, n: {tn}, k: {tk}\n")
+            out.extend(under(i, t))
+        out.append(f"  best: {int(best[i]) + 1}\n" if best[i] >= 0 else "  best: none\n")
+    return "".join(out)
+
+
+def format_targets_topk(results, topk, first_index: int = 0) -> str:
+    """:func:`format_targets` with every target's top-K rows (int32 [n, T, K, 3] from the per-target top-K calls; rank
+    1 is the multi-target row): under each "  target t: ..." line one line per rank j >= 2,
+    "    top j: score: S, n: N, k: K", real candidates only."""
+    from ..ops.align import as_triples
+
+    r = np.asarray(topk, dtype=np.int32)
+    if r.ndim != 4 or r.shape[3] != 3 or r.shape[2] < 1 or r.shape[1] < 1 or r.shape[0] != as_triples(results).shape[0]:
+        raise ValueError("format_targets_topk needs [n, T, K, 3] rows for the results' n records")
+    none = np.iinfo(np.int32).min
+
+    def under(i, t):
+        return [f"    top {j}: score: {s}, n: {n}, k: {k}\n" for j, (s, n, k) in enumerate(r[i, t, 1:].tolist(), start=2)
+                if s != none]
+
+    return _format_targets_under(results, np.ascontiguousarray(r[:, :, 0]), under, first_index)
+
+
+def format_targets_hits(results, rows, hits, toffsets, first_index: int = 0) -> str:
+    """:func:`format_targets` (``rows``: the multi-target rows, int32 [n, T, 3]) with every target's threshold hits
+    (``hits[toffsets[i * T + t]:toffsets[i * T + t + 1]]`` from the per-target hits calls): under each
+    "  target t: ..." line one line per hit, "    hit: score: S, n: N, k: K", n relative to the target's start."""
+    from ..ops.align import as_triples
+
+    r = np.asarray(rows, dtype=np.int32)
+    if r.ndim != 3 or r.shape[2] != 3 or r.shape[1] < 1 or r.shape[0] != as_triples(results).shape[0]:
+        raise ValueError("format_targets_hits needs [n, T, 3] rows for the results' n records")
+    h = np.asarray(hits, dtype=np.int64).reshape(-1, 3)
+    o = np.asarray(toffsets, dtype=np.int64).reshape(-1)
+    T = r.shape[1]
+    if o.shape[0] != r.shape[0] * T + 1 or o[0] != 0 or o[-1] != h.shape[0] or np.any(np.diff(o) < 0):
+        raise ValueError("format_targets_hits needs toffsets [n * T + 1] that index the hits of the rows' pairs")
+
+    def under(i, t):
+        p = i * T + t
+        return [f"    hit: score: {s}, n: {n}, k: {k}\n" for s, n, k in h[o[p]:o[p + 1]].tolist()]
+
+    return _format_targets_under(results, r, under, first_index)
+
+
 def format_targets_summary(summary, hist=None, first_index: int = 0) -> str:
     """:func:`format_targets` with every target's profile summary (int64 [n, T, 7] from the per-target summary calls;
     its (max, n, k) are the multi-target rows, and record i's own line is target 1's row): under each
