@@ -54,7 +54,7 @@ COMM_OBJS := $(OBJ)/comm/comm.o $(OBJ)/comm/mpi_device_comm.o
 RCCL_OBJS := $(OBJ)/comm/rccl_comm.o
 HEADERS   := $(shell find csrc/include -name '*.h' -o -name '*.hpp')
 
-.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san hits-san wire-san peaks-san summary-san targets-san targets-summary-san targets-rows-san
+.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san hits-san wire-san peaks-san summary-san targets-san targets-summary-san targets-rows-san targets-peaks-san
 
 all: build
 build: lib final $(GPU_PLUGIN)
@@ -284,6 +284,14 @@ targets-rows-san: $(BUILD)/targets_rows_san
 	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/targets_rows_san
 $(BUILD)/targets_rows_san: csrc/tests/targets_rows_san.cpp $(PSAN_OBJS) $(HEADERS)
 	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/targets_rows_san.cpp $(PSAN_OBJS) -ldl
+
+# stand-alone ASan/UBSan check of the per-target distinct placements' host code: targets_topk_batch_cpu and
+# targets_hits_batch_cpu with a radius against the single-Seq1 distinct calls run on every target alone, every buffer
+# in a heap block of exactly its size, and the planner's per-target peaks facts (own main, host code only)
+targets-peaks-san: $(BUILD)/targets_peaks_san
+	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/targets_peaks_san
+$(BUILD)/targets_peaks_san: csrc/tests/targets_peaks_san.cpp $(PSAN_OBJS) $(HEADERS)
+	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/targets_peaks_san.cpp $(PSAN_OBJS) -ldl
 
 # parser throughput (count vs fill, SIMD A/B): build/fill_bench [records]
 $(BUILD)/fill_bench: tools/fill_bench.cpp $(CPU_OBJS) $(HEADERS)

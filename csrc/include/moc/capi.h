@@ -398,6 +398,37 @@ int moc_engine_solve_targets_hits_device(void* e, const uint8_t* d_codes, const 
 int moc_engine_solve_targets_hits_wire(void* e, const moc_wire_batch* b, const int64_t* starts, int64_t T,
                                        int32_t min_score, const int32_t* thresholds, int64_t max_rows_hint,
                                        int64_t* toffsets, moc_result* rows, int64_t cap);
+/* The distinct forms of the eight calls above: `radius` (0 .. 2048, as moc_cpu_topk_distinct's) keeps only the peaks of
+ * every pair's OWN profile — local entry o is a peak iff it is the best of the local offsets [o - radius, o + radius]
+ * clipped to the pair's entries, the boundary entry among them — so pair (i, t)'s rows are those of the single-target
+ * distinct calls on target t alone. radius = 0 is the call above. Errors: as above, then the radius ("distinct:"). */
+int moc_cpu_targets_topk_distinct(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                                  const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics,
+                                  int threads, int K, int64_t radius, moc_result* rows);
+int moc_cpu_targets_hits_distinct(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                                  const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics,
+                                  int threads, int32_t min_score, const int32_t* thresholds, int64_t radius,
+                                  int64_t* toffsets, moc_result* rows, int64_t cap);
+int moc_engine_solve_targets_topk_distinct(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n,
+                                           const int64_t* starts, int64_t T, int K, int64_t radius, moc_result* rows);
+int moc_engine_solve_targets_topk_device_distinct(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                                  const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
+                                                  const int64_t* h_starts, int64_t T, int K, int64_t radius,
+                                                  moc_result* d_rows, void* stream);
+int moc_engine_solve_targets_topk_wire_distinct(void* e, const moc_wire_batch* b, const int64_t* starts, int64_t T, int K,
+                                                int64_t radius, moc_result* rows);
+int moc_engine_solve_targets_hits_distinct(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n,
+                                           const int64_t* starts, int64_t T, int32_t min_score, const int32_t* thresholds,
+                                           int64_t max_rows_hint, int64_t radius, int64_t* toffsets, moc_result* rows,
+                                           int64_t cap);
+int moc_engine_solve_targets_hits_device_distinct(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                                  const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
+                                                  const int64_t* h_starts, int64_t T, int32_t min_score,
+                                                  const int32_t* d_thresholds, int64_t radius, int64_t* d_toffsets,
+                                                  moc_result* d_rows, int64_t cap, void* stream);
+int moc_engine_solve_targets_hits_wire_distinct(void* e, const moc_wire_batch* b, const int64_t* starts, int64_t T,
+                                                int32_t min_score, const int32_t* thresholds, int64_t max_rows_hint,
+                                                int64_t radius, int64_t* toffsets, moc_result* rows, int64_t cap);
 /* stats: kernel_ms, total_ms, h2d_bytes, d2h_bytes, chunks, cells, records, direct, format, kernels,
  * r2 smin, r2 kw, r2 j, forms (moc::bounds::FormBits of the last solve) */
 int moc_engine_stats(void* e, double* out14);

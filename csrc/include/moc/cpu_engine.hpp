@@ -185,12 +185,23 @@ void targets_summary_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L
 // offset — hits_batch_cpu run on target t alone. toffsets (int64 [n * T + 1]) is hits_batch_cpu's index over pairs
 // and the capacity contract is its own: the index always complete and exact, a row written iff its flat index is
 // < cap, nothing at or past rows + cap touched, cap == 0 (rows may be null) counts only. A pair that does not fit
-// has no hits. Errors before any work: check_targets' ("targets: ..."), then the top-K / hits messages.
+// has no hits. Errors before any work: check_targets' ("targets: ..."), then the top-K / hits messages, then
+// check_peaks_radius' ("distinct: ...").
+// radius > 0, the distinct forms: local entry o of pair (i, t) is a peak iff its key is the maximum of the keys at
+// local offsets [o - radius, o + radius] clipped to the pair's own [0, C_{i,t}) — peaks_filter on the pair's target
+// profile, the boundary entry an ordinary entry of it. Nothing outside the pair's profile is ever in a window: not
+// the catalog's straddling entries, not the catalog's own value at the boundary offset, not a neighbouring target.
+// Top-K then ranks the peaks (min(K, #peaks) rows, then no_candidate()), hits are the peaks at or above the pair's
+// threshold in ascending local offset; index and capacity contract unchanged. Pair (i, t)'s rows are those of
+// topk_batch_cpu / hits_batch_cpu with the same radius on target t alone; row 0 is targets_batch_cpu's at every
+// radius; radius >= C_{i,t} - 1 leaves one peak per fitting pair; radius = 0 is the call without it.
 void targets_topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
-                            const int64_t* starts, int64_t T, int K, Result* out, Semantics sem, int num_threads = 0);
+                            const int64_t* starts, int64_t T, int K, Result* out, Semantics sem, int num_threads = 0,
+                            int64_t radius = 0);
 void targets_hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
                             const int64_t* starts, int64_t T, int32_t min_score, const int32_t* thresholds,
-                            int64_t* toffsets, Result* rows, int64_t cap, Semantics sem, int num_threads = 0);
+                            int64_t* toffsets, Result* rows, int64_t cap, Semantics sem, int num_threads = 0,
+                            int64_t radius = 0);
 
 // ---- alignment report: the signs under a result row's letter pairs
 // A row is a Result {score, n, k} of record i (L2 letters) against Seq1; rows[i*K .. i*K+K) belong to record i.

@@ -461,6 +461,35 @@ struct TargetsHitsArgs {
 // Queues count, scan (one or three launches) and, when cap > 0, the compaction on `stream`.
 void launch_targets_hits(const TargetsHitsArgs& ha, const ProblemView& pv, const BatchView& bv, hipStream_t stream);
 
+// ---- per-target distinct placements (targets_peaks_kernels.hip; definitions: moc/cpu_engine.hpp
+// targets_topk_batch_cpu / targets_hits_batch_cpu with radius > 0)
+// One chunk (ta.view) after its catalog profile is written: for every fitting pair (r, t) of the chunk with a target
+// profile of C >= 2 entries, peak[poffsets[r] - base + starts[t] + o] <- 1 when local entry o (the boundary entry, when
+// it takes part, is o = C - 1) is a peak of radius `radius` of the pair's own profile, else 0 — the catalog's layout:
+// slices of different targets are disjoint and a boundary entry's byte is that of a straddling catalog entry that no
+// pair owns. A pair of C == 1 has no mark (its one entry is a peak; under the reference semantics the byte would lie
+// one past the record's entries for a last target of the record's length) and the consumers never read one for it.
+// The host states what the chunk holds (plan::ProfileChunk's t_* facts): seg, the segment width of the lane-per-entry
+// kernel (4, 8, 16, 32 or 64); any_short, some pair may have 2 .. seg entries; max_tiles / lds_keys, the tile kernel's
+// geometry for the pairs of more than seg entries (0: none). ta.group and ta.out are the consumers'.
+struct TargetsPeaksArgs {
+  TargetsArgs ta;
+  int32_t radius = 0;  // 1 .. bounds::kPeaksMaxRadius
+  int32_t seg = 64;
+  int32_t any_short = 0;
+  int32_t max_tiles = 0;
+  int32_t lds_keys = 0;
+  int32_t num_cus = 256;
+  uint8_t* peak = nullptr;  // ta.view.prof_entries bytes
+};
+void launch_targets_peaks(const TargetsPeaksArgs& a, const ProblemView& pv, const BatchView& bv, hipStream_t stream);
+// launch_targets_topk / launch_targets_hits over the peaks only (peak: what launch_targets_peaks stored for the same
+// chunk); the same lane groups, ownership, prefix sum and capacity contract.
+void launch_targets_topk_peaks(const TargetsArgs& ta, const uint8_t* peak, int K, const ProblemView& pv,
+                               const BatchView& bv, hipStream_t stream);
+void launch_targets_hits_peaks(const TargetsHitsArgs& ha, const uint8_t* peak, const ProblemView& pv, const BatchView& bv,
+                               hipStream_t stream);
+
 // Loads every kernel file's code object onto the current device now (HIP loads them lazily, at the first
 // launch from each file: milliseconds inside the first timed search of a job otherwise).
 void preload_align_kernels();
@@ -478,6 +507,7 @@ void preload_summary_kernels();
 void preload_targets_kernels();
 void preload_targets_summary_kernels();
 void preload_targets_rows_kernels();
+void preload_targets_peaks_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -496,6 +526,7 @@ enum PreloadSet : unsigned {
   kPreloadTargets = 4096,  // targets_kernels.hip: likewise
   kPreloadTargetsSummary = 8192,  // targets_summary_kernels.hip: likewise
   kPreloadTargetsRows = 16384,    // targets_rows_kernels.hip: likewise
+  kPreloadTargetsPeaks = 32768,   // targets_peaks_kernels.hip: likewise
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -513,9 +544,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadTargets) preload_targets_kernels();
   if (set & kPreloadTargetsSummary) preload_targets_summary_kernels();
   if (set & kPreloadTargetsRows) preload_targets_rows_kernels();
+  if (set & kPreloadTargetsPeaks) preload_targets_peaks_kernels();
 }
 // "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
-// profile, report, hits, wire, peaks, summary, targets, targets_summary, targets_rows;
+// profile, report, hits, wire, peaks, summary, targets, targets_summary, targets_rows, targets_peaks;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

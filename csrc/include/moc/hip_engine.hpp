@@ -68,7 +68,9 @@ struct EngineStats {
                          // 1024 targets (the multi-target select kernel, next to 16),
                          // 2048 targets_summary (the per-target summary / histogram kernels, next to 16),
                          // 4096 targets_topk (the per-target top-K kernel, next to 16),
-                         // 8192 targets_hits (the per-target count / scan / compact kernels, next to 16)
+                         // 8192 targets_hits (the per-target count / scan / compact kernels, next to 16),
+                         // 16384 targets_peaks (the per-target peak pass and masked per-target kernels of a distinct
+                         // per-target call, next to 256 and 4096 or 8192)
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -254,6 +256,13 @@ class HipEngine {
   // solve_targets. Before anything is launched or any state changes the target set is checked ("targets:" errors),
   // then K (solve_topk's message) or the hits buffers (solve_hits_device's messages). targets_ms() covers the new
   // launches.
+  // radius > 0, the distinct forms (kernels: csrc/src/hip/targets_peaks_kernels.hip): only the peaks of radius
+  // `radius` of every pair's OWN profile are ranked or listed — its windows clipped to the pair's entries, the
+  // boundary entry among them — which is solve_topk / solve_hits with that radius on the target alone. Checked after
+  // the messages above ("distinct:" errors, 0 .. bounds::kPeaksMaxRadius). Per chunk the segmented peak pass runs
+  // between the profile kernel and masked forms of the per-target kernels (segment width: bounds::targets_peaks_seg;
+  // MOC_TARGETS_PEAKS_SEG=4|8|16|32|64 at engine start forces one); the profile scratch holds one more byte per entry.
+  // radius = 0 is launch for launch the call without it.
   // Device forms: queued on `stream` (0 = engine compute stream) with no sync, in the chunks of solve_targets — per
   // chunk the profile kernel over the catalog, then the per-target top-K kernel, or count, prefix sum over the
   // chunk's pairs (hits' own scan launches) and compaction, the lane group chosen as solve_targets chooses it (top-K:
@@ -264,19 +273,19 @@ class HipEngine {
   // An empty batch launches nothing, apart from the 8-byte memset of d_toffsets[0] of the hits form.
   void solve_targets_topk_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
                                  const int64_t* d_starts, const int64_t* h_starts, int64_t T, int K, Result* d_out,
-                                 hipStream_t stream);
+                                 hipStream_t stream, int64_t radius = 0);
   void solve_targets_hits_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
                                  const int64_t* d_starts, const int64_t* h_starts, int64_t T, int32_t min_score,
                                  const int32_t* d_thresholds, int64_t* d_toffsets, Result* d_rows, int64_t cap,
-                                 hipStream_t stream);
+                                 hipStream_t stream, int64_t radius = 0);
   // Host forms (upload through the pooled buffers; synchronous; fill stats()). thresholds: host int32 [n * T] or null.
   // Hits is optimistic as solve_hits is: one pass with room for max(max_rows_hint, 1) rows (hint < 0: n * T), and
   // exactly one more with toffsets[n * T] rows when that was too few; hits_passes() tells.
   void solve_targets_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T,
-                          int K, Result* out);
+                          int K, Result* out, int64_t radius = 0);
   void solve_targets_hits(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T,
                           int32_t min_score, const int32_t* thresholds, int64_t* toffsets_out,
-                          std::vector<Result>& rows_out, int64_t max_rows_hint = -1);
+                          std::vector<Result>& rows_out, int64_t max_rows_hint = -1, int64_t radius = 0);
 
   // ---- alignment report (definitions: moc/cpu_engine.hpp report_batch_cpu; kernels:
   // csrc/src/hip/report_kernels.hip): the sign counts and, optionally, the marker bytes of caller-supplied rows.
@@ -327,10 +336,11 @@ class HipEngine {
   void solve_targets_wire(const WireBatch& b, const int64_t* starts, int64_t T, Result* out);
   void solve_targets_summary_wire(const WireBatch& b, const int64_t* starts, int64_t T, int64_t* summary_out,
                                   int32_t* hist_out, int32_t bins, int32_t lo, int32_t width);
-  void solve_targets_topk_wire(const WireBatch& b, const int64_t* starts, int64_t T, int K, Result* out);
+  void solve_targets_topk_wire(const WireBatch& b, const int64_t* starts, int64_t T, int K, Result* out,
+                               int64_t radius = 0);
   void solve_targets_hits_wire(const WireBatch& b, const int64_t* starts, int64_t T, int32_t min_score,
                                const int32_t* thresholds, int64_t* toffsets_out, std::vector<Result>& rows_out,
-                               int64_t max_rows_hint = -1);
+                               int64_t max_rows_hint = -1, int64_t radius = 0);
   // poffsets[0..n] of a host wire batch (profile_offsets of its decoded lengths; no GPU work)
   void wire_profile_offsets(const WireBatch& b, int64_t* poffsets) const;
 
@@ -416,9 +426,9 @@ class HipEngine {
   void targets_placed(Placed& p, const int64_t* starts, int64_t T, Result* out);
   void targets_summary_placed(Placed& p, const int64_t* starts, int64_t T, int64_t* summary_out, int32_t* hist_out,
                               int32_t bins, int32_t lo, int32_t width);
-  void targets_topk_placed(Placed& p, const int64_t* starts, int64_t T, int K, Result* out);
+  void targets_topk_placed(Placed& p, const int64_t* starts, int64_t T, int K, Result* out, int64_t radius);
   void targets_hits_placed(Placed& p, const int64_t* starts, int64_t T, int32_t min_score, const int32_t* thresholds,
-                           int64_t* toffsets_out, std::vector<Result>& rows_out, int64_t max_rows_hint);
+                           int64_t* toffsets_out, std::vector<Result>& rows_out, int64_t max_rows_hint, int64_t radius);
   void report_placed(Placed& p, int K, const Result* rows, int32_t* counts, uint8_t* marks);
   void ensure_device_events();  // ev_d0_ / ev_d1_, made by the first call that records them
   dev::Plan device_plan(void* d_plan, size_t n_starts, bool has_long_recs, int64_t n_long, const plan::TilePlan& tp,
@@ -527,6 +537,7 @@ class HipEngine {
   size_t d_prof_scratch_cap_ = 0;
   bool profile_timing_ = false;
   int targets_group_ = 0;  // MOC_TARGETS_GROUP: 4, 16 or 64 forces that lane-group size; 0: chosen per chunk
+  int targets_peaks_seg_ = 0;  // MOC_TARGETS_PEAKS_SEG: 4, 8, 16, 32 or 64 forces that segment width of the per-target peak pass
   std::vector<hipEvent_t> ev_select_;
   size_t ev_select_used_ = 0;
   // hits: the scan's block sums, the host form's row buffer, and its pass count

@@ -199,6 +199,28 @@ inline int targets_topk_group(int64_t max_slice) {
   return max_slice <= kTargetsGroup4MaxSlice ? 4 : max_slice <= kTargetsTopKGroup16MaxSlice ? 16 : 64;
 }
 
+// ---- per-target distinct placements (targets_peaks_kernels.hip; definitions: moc/cpu_engine.hpp
+// targets_topk_batch_cpu / targets_hits_batch_cpu with radius > 0): the peak filter over every (record, target)
+// pair's own profile. A pair profile of 2 .. S entries takes a segment of S consecutive lanes of a wave (S = 4, 8, 16,
+// 32 or 64, a lane per entry), a longer one a workgroup per tile of kPeaksTile entries with peaks_tile_kernel's LDS
+// budget (kPeaksTile + 2 kPeaksMaxRadius keys); a profile of one entry is its own peak and has no mark. The host picks
+// S per chunk from the chunk's longest pair profile: the smallest of the five widths that holds it, a wave from 33
+// entries on — the narrowest segment that still gives every profile of at most kPeaksWaveEntries entries a lane per
+// entry, so none of them goes to a workgroup. MOC_TARGETS_PEAKS_SEG=4|8|16|32|64 at engine start forces S; a profile
+// longer than a forced S goes to the tile kernel, so every S gives the same marks. Tuning only. "The narrowest width
+// that fits" is a rule, not a set of measured crossings: measured on input6-shaped records against 256 targets (pair
+// profiles of 15 .. 20 entries; profiles/targets_peaks/README.md), 32 lanes — the rule's choice — are ahead of a wave,
+// and 4, 8 and 16 lanes, which send those profiles to the tile kernel, far behind; no shape with profiles of at most
+// 4, 8 or 16 entries was measured.
+constexpr int32_t kTargetsPeaksMinSeg = 4;
+inline bool targets_peaks_seg_valid(int s) { return s >= kTargetsPeaksMinSeg && s <= kPeaksWaveEntries && (s & (s - 1)) == 0; }
+inline int targets_peaks_seg(int64_t max_count) {
+  int s = kTargetsPeaksMinSeg;
+  while (s < kPeaksWaveEntries && s < max_count) s <<= 1;
+  return s;
+}
+static_assert(kPeaksWaveEntries == 64, "targets peaks: the widest segment is a wave");
+
 // Form bits reported per solve (EngineStats::forms; Python: stats()["forms"]).
 enum FormBits : int32_t {
   kFormSwipeKBits = 1,    // swipe, int16 keys with k bits

@@ -123,6 +123,13 @@ struct ProfileChunk {
   // entries; tiles of bounds::kPeaksTile entries of its longest profile when that is longer, else 0; the most keys
   // such a tile puts into LDS, halo included
   int32_t any_short = 0, max_tiles = 0, lds_keys = 0;
+  // per-target distinct forms (radius > 0 with targets), what dev::TargetsPeaksArgs states of a chunk, from the target
+  // lengths and the chunk's shortest and longest record (bounds::targets_pair_count): t_seg, the segment width (4, 8, 16,
+  // 32 or 64: bounds::targets_peaks_seg of the longest pair profile, or the forced one); t_any_short, some pair profile
+  // may have 2 .. t_seg entries; t_max_tiles, tiles of bounds::kPeaksTile entries of the longest pair profile when
+  // that has more than t_seg entries, else 0; t_lds_keys, the most keys such a tile puts into LDS, halo included.
+  // All 0 otherwise, and the three fields above stay 0 for such a call (the plain peak pass never runs for it).
+  int32_t t_seg = 0, t_any_short = 0, t_max_tiles = 0, t_lds_keys = 0;
 };
 struct ProfilePlan {
   std::vector<int64_t> poff;           // the batch's profile index, n + 1 entries
@@ -138,10 +145,12 @@ struct ProfilePlan {
 };
 // entry_bytes: 8, or 9 with a byte of peak marks beside every entry. radius: 0, or the peaks radius (the chunks'
 // peaks facts are filled only then). target_starts: null, or T + 1 host entries; upload_targets: they go into the
-// plan buffer. Throws Error for n >= 2^31 - 1 and for Seq1 / Seq2 lengths of 2^30 and more; n >= 1.
+// plan buffer. radius > 0 with target_starts is a per-target distinct call: the chunks' t_* facts are filled in
+// place of the plain peaks facts; targets_seg: 0, or the forced segment width (4, 8, 16, 32 or 64).
+// Throws Error for n >= 2^31 - 1 and for Seq1 / Seq2 lengths of 2^30 and more; n >= 1.
 ProfilePlan plan_profile(const Config& c, Semantics sem, const int64_t* offsets, int64_t n, bool chunked,
                          int64_t entry_bytes, int64_t scratch_bytes, int64_t radius, const int64_t* target_starts = nullptr,
-                         int64_t T = 0, bool upload_targets = false);
+                         int64_t T = 0, bool upload_targets = false, int targets_seg = 0);
 
 // ---- alignment report (report_kernels.hip): which records' rows take a lane each and which a wave each.
 // Records of at most bounds::kReportShortMaxL2 letters are short. A wave of the lane-per-row kernel takes up to

@@ -948,10 +948,10 @@ int moc_engine_targets_summary_ms(void* e, double* ms) {
   return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->targets_summary_ms(); });
 }
 
-// ---- per-target top-K and threshold hits
-int moc_cpu_targets_topk(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
-                         const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics, int threads,
-                         int K, moc_result* rows) {
+// ---- per-target top-K and threshold hits; the *_distinct forms carry the peaks radius, the frozen ones are radius 0
+int moc_cpu_targets_topk_distinct(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                                  const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics,
+                                  int threads, int K, int64_t radius, moc_result* rows) {
   return guard([&] {
     moc::check_targets(starts, T, L1);
     moc::Weights w = weights_of(weights4);
@@ -959,13 +959,20 @@ int moc_cpu_targets_topk(const int32_t* weights4, const uint8_t* seq1, int64_t L
     moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
     moc::ScoreTable t = moc::ScoreTable::build(w);
     moc::targets_topk_batch_cpu(t, seq1, L1, b, starts, T, K, reinterpret_cast<moc::Result*>(rows),
-                                static_cast<moc::Semantics>(semantics), threads);
+                                static_cast<moc::Semantics>(semantics), threads, radius);
   });
 }
 
-int moc_cpu_targets_hits(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+int moc_cpu_targets_topk(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
                          const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics, int threads,
-                         int32_t min_score, const int32_t* thresholds, int64_t* toffsets, moc_result* rows, int64_t cap) {
+                         int K, moc_result* rows) {
+  return moc_cpu_targets_topk_distinct(weights4, seq1, L1, codes, offsets, n, starts, T, semantics, threads, K, 0, rows);
+}
+
+int moc_cpu_targets_hits_distinct(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                                  const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics,
+                                  int threads, int32_t min_score, const int32_t* thresholds, int64_t radius,
+                                  int64_t* toffsets, moc_result* rows, int64_t cap) {
   return guard([&] {
     moc::check_targets(starts, T, L1);
     moc::Weights w = weights_of(weights4);
@@ -973,44 +980,93 @@ int moc_cpu_targets_hits(const int32_t* weights4, const uint8_t* seq1, int64_t L
     moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
     moc::ScoreTable t = moc::ScoreTable::build(w);
     moc::targets_hits_batch_cpu(t, seq1, L1, b, starts, T, min_score, thresholds, toffsets,
-                                reinterpret_cast<moc::Result*>(rows), cap, static_cast<moc::Semantics>(semantics), threads);
+                                reinterpret_cast<moc::Result*>(rows), cap, static_cast<moc::Semantics>(semantics), threads,
+                                radius);
+  });
+}
+
+int moc_cpu_targets_hits(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                         const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics, int threads,
+                         int32_t min_score, const int32_t* thresholds, int64_t* toffsets, moc_result* rows, int64_t cap) {
+  return moc_cpu_targets_hits_distinct(weights4, seq1, L1, codes, offsets, n, starts, T, semantics, threads, min_score,
+                                       thresholds, 0, toffsets, rows, cap);
+}
+
+int moc_engine_solve_targets_topk_distinct(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n,
+                                           const int64_t* starts, int64_t T, int K, int64_t radius, moc_result* rows) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_targets_topk(codes, offsets, n, starts, T, K, reinterpret_cast<moc::Result*>(rows),
+                                                        radius);
   });
 }
 
 int moc_engine_solve_targets_topk(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
                                   int64_t T, int K, moc_result* rows) {
+  return moc_engine_solve_targets_topk_distinct(e, codes, offsets, n, starts, T, K, 0, rows);
+}
+
+int moc_engine_solve_targets_topk_device_distinct(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                                  const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
+                                                  const int64_t* h_starts, int64_t T, int K, int64_t radius,
+                                                  moc_result* d_rows, void* stream) {
   return guard([&] {
-    static_cast<moc::HipEngine*>(e)->solve_targets_topk(codes, offsets, n, starts, T, K, reinterpret_cast<moc::Result*>(rows));
+    static_cast<moc::HipEngine*>(e)->solve_targets_topk_device(d_codes, d_offsets, h_offsets, n, d_starts, h_starts, T, K,
+                                                               reinterpret_cast<moc::Result*>(d_rows),
+                                                               static_cast<hipStream_t>(stream), radius);
   });
 }
 
 int moc_engine_solve_targets_topk_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
                                          const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
                                          const int64_t* h_starts, int64_t T, int K, moc_result* d_rows, void* stream) {
+  return moc_engine_solve_targets_topk_device_distinct(e, d_codes, d_offsets, h_offsets, n, d_starts, h_starts, T, K, 0,
+                                                       d_rows, stream);
+}
+
+int moc_engine_solve_targets_topk_wire_distinct(void* e, const moc_wire_batch* w, const int64_t* starts, int64_t T, int K,
+                                                int64_t radius, moc_result* rows) {
   return guard([&] {
-    static_cast<moc::HipEngine*>(e)->solve_targets_topk_device(d_codes, d_offsets, h_offsets, n, d_starts, h_starts, T, K,
-                                                               reinterpret_cast<moc::Result*>(d_rows),
-                                                               static_cast<hipStream_t>(stream));
+    static_cast<moc::HipEngine*>(e)->solve_targets_topk_wire(wire_batch(w), starts, T, K, reinterpret_cast<moc::Result*>(rows),
+                                                             radius);
   });
 }
 
 int moc_engine_solve_targets_topk_wire(void* e, const moc_wire_batch* w, const int64_t* starts, int64_t T, int K,
                                        moc_result* rows) {
+  return moc_engine_solve_targets_topk_wire_distinct(e, w, starts, T, K, 0, rows);
+}
+
+int moc_engine_solve_targets_hits_distinct(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n,
+                                           const int64_t* starts, int64_t T, int32_t min_score, const int32_t* thresholds,
+                                           int64_t max_rows_hint, int64_t radius, int64_t* toffsets, moc_result* rows,
+                                           int64_t cap) {
   return guard([&] {
-    static_cast<moc::HipEngine*>(e)->solve_targets_topk_wire(wire_batch(w), starts, T, K, reinterpret_cast<moc::Result*>(rows));
+    static_cast<moc::HipEngine*>(e)->check_targets_call(starts, T);  // the target set's errors come first
+    if (cap < 0 || (cap > 0 && !rows)) throw moc::Error("hits: cap rows need a rows buffer");
+    static_cast<moc::HipEngine*>(e)->solve_targets_hits(codes, offsets, n, starts, T, min_score, thresholds, toffsets,
+                                                        g_hits_rows, max_rows_hint, radius);
+    const size_t m = std::min(g_hits_rows.size(), static_cast<size_t>(cap));
+    if (m) std::memcpy(rows, g_hits_rows.data(), sizeof(moc::Result) * m);
   });
 }
 
 int moc_engine_solve_targets_hits(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
                                   int64_t T, int32_t min_score, const int32_t* thresholds, int64_t max_rows_hint,
                                   int64_t* toffsets, moc_result* rows, int64_t cap) {
+  return moc_engine_solve_targets_hits_distinct(e, codes, offsets, n, starts, T, min_score, thresholds, max_rows_hint, 0,
+                                                toffsets, rows, cap);
+}
+
+int moc_engine_solve_targets_hits_device_distinct(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                                  const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
+                                                  const int64_t* h_starts, int64_t T, int32_t min_score,
+                                                  const int32_t* d_thresholds, int64_t radius, int64_t* d_toffsets,
+                                                  moc_result* d_rows, int64_t cap, void* stream) {
   return guard([&] {
-    static_cast<moc::HipEngine*>(e)->check_targets_call(starts, T);  // the target set's errors come first
-    if (cap < 0 || (cap > 0 && !rows)) throw moc::Error("hits: cap rows need a rows buffer");
-    static_cast<moc::HipEngine*>(e)->solve_targets_hits(codes, offsets, n, starts, T, min_score, thresholds, toffsets,
-                                                        g_hits_rows, max_rows_hint);
-    const size_t m = std::min(g_hits_rows.size(), static_cast<size_t>(cap));
-    if (m) std::memcpy(rows, g_hits_rows.data(), sizeof(moc::Result) * m);
+    static_cast<moc::HipEngine*>(e)->solve_targets_hits_device(d_codes, d_offsets, h_offsets, n, d_starts, h_starts, T,
+                                                               min_score, d_thresholds, d_toffsets,
+                                                               reinterpret_cast<moc::Result*>(d_rows), cap,
+                                                               static_cast<hipStream_t>(stream), radius);
   });
 }
 
@@ -1019,25 +1075,28 @@ int moc_engine_solve_targets_hits_device(void* e, const uint8_t* d_codes, const 
                                          const int64_t* h_starts, int64_t T, int32_t min_score,
                                          const int32_t* d_thresholds, int64_t* d_toffsets, moc_result* d_rows, int64_t cap,
                                          void* stream) {
+  return moc_engine_solve_targets_hits_device_distinct(e, d_codes, d_offsets, h_offsets, n, d_starts, h_starts, T, min_score,
+                                                       d_thresholds, 0, d_toffsets, d_rows, cap, stream);
+}
+
+int moc_engine_solve_targets_hits_wire_distinct(void* e, const moc_wire_batch* w, const int64_t* starts, int64_t T,
+                                                int32_t min_score, const int32_t* thresholds, int64_t max_rows_hint,
+                                                int64_t radius, int64_t* toffsets, moc_result* rows, int64_t cap) {
   return guard([&] {
-    static_cast<moc::HipEngine*>(e)->solve_targets_hits_device(d_codes, d_offsets, h_offsets, n, d_starts, h_starts, T,
-                                                               min_score, d_thresholds, d_toffsets,
-                                                               reinterpret_cast<moc::Result*>(d_rows), cap,
-                                                               static_cast<hipStream_t>(stream));
+    static_cast<moc::HipEngine*>(e)->check_targets_call(starts, T);  // the target set's errors come first
+    if (cap < 0 || (cap > 0 && !rows)) throw moc::Error("hits: cap rows need a rows buffer");
+    static_cast<moc::HipEngine*>(e)->solve_targets_hits_wire(wire_batch(w), starts, T, min_score, thresholds, toffsets,
+                                                             g_hits_rows, max_rows_hint, radius);
+    const size_t m = std::min(g_hits_rows.size(), static_cast<size_t>(cap));
+    if (m) std::memcpy(rows, g_hits_rows.data(), sizeof(moc::Result) * m);
   });
 }
 
 int moc_engine_solve_targets_hits_wire(void* e, const moc_wire_batch* w, const int64_t* starts, int64_t T,
                                        int32_t min_score, const int32_t* thresholds, int64_t max_rows_hint,
                                        int64_t* toffsets, moc_result* rows, int64_t cap) {
-  return guard([&] {
-    static_cast<moc::HipEngine*>(e)->check_targets_call(starts, T);  // the target set's errors come first
-    if (cap < 0 || (cap > 0 && !rows)) throw moc::Error("hits: cap rows need a rows buffer");
-    static_cast<moc::HipEngine*>(e)->solve_targets_hits_wire(wire_batch(w), starts, T, min_score, thresholds, toffsets,
-                                                             g_hits_rows, max_rows_hint);
-    const size_t m = std::min(g_hits_rows.size(), static_cast<size_t>(cap));
-    if (m) std::memcpy(rows, g_hits_rows.data(), sizeof(moc::Result) * m);
-  });
+  return moc_engine_solve_targets_hits_wire_distinct(e, w, starts, T, min_score, thresholds, max_rows_hint, 0, toffsets,
+                                                     rows, cap);
 }
 
 int moc_engine_stats(void* e, double* out14) {

@@ -514,19 +514,39 @@ inline TargetPair target_pair(const ScoreTable& t, const uint8_t* s1, int64_t L1
 }
 }  // namespace
 
+namespace {
+// Pair p's own profile (its slice of the catalog profile, then the boundary entry as an ordinary entry) and the peak
+// marks of radius `radius` over exactly those entries: nothing outside the pair's [0, C_p) is ever in a window.
+// Returns the marks, or null for radius == 0 (every entry counts).
+inline const uint8_t* target_pair_peaks(const ProfileEntry* prof, const TargetPair& p, int64_t radius) {
+  if (radius == 0 || !p.fits) return nullptr;
+  thread_local std::vector<ProfileEntry> own;
+  thread_local std::vector<uint8_t> peak;
+  own.assign(prof + p.b, prof + p.b + p.slice);
+  if (p.boundary) own.push_back(ProfileEntry{p.bscore, 0});
+  peak.resize(own.size());
+  peaks_filter(own.data(), static_cast<int64_t>(own.size()), radius, peak.data());
+  return peak.data();
+}
+}  // namespace
+
 void targets_topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
-                            const int64_t* starts, int64_t T, int K, Result* out, Semantics sem, int num_threads) {
+                            const int64_t* starts, int64_t T, int K, Result* out, Semantics sem, int num_threads,
+                            int64_t radius) {
   check_targets(starts, T, L1);
   if (K < 1 || K > kMaxTopK) throw Error("top-K: K must be in 1.." + std::to_string(kMaxTopK));
+  check_peaks_radius(radius);
   for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
     thread_local std::vector<uint64_t> keys;
     const int64_t L2 = batch.length(i);
     for (int64_t q = 0; q < T; ++q) {
       Result* row = out + (i * T + q) * K;
       const TargetPair p = target_pair(t, s1, L1, batch.record(i), L2, starts, q, sem);
+      const uint8_t* peak = target_pair_peaks(prof, p, radius);
       keys.clear();
-      for (int64_t o = 0; o < p.slice; ++o) keys.push_back(profile_key(prof[p.b + o], o));
-      if (p.boundary) keys.push_back(profile_key(ProfileEntry{p.bscore, 0}, p.slice));
+      for (int64_t o = 0; o < p.slice; ++o)
+        if (!peak || peak[o]) keys.push_back(profile_key(prof[p.b + o], o));
+      if (p.boundary && (!peak || peak[p.slice])) keys.push_back(profile_key(ProfileEntry{p.bscore, 0}, p.slice));
       const int64_t m = std::min<int64_t>(K, static_cast<int64_t>(keys.size()));
       std::partial_sort(keys.begin(), keys.begin() + m, keys.end(), std::greater<uint64_t>());
       for (int64_t j = 0; j < m; ++j) {
@@ -542,10 +562,12 @@ void targets_topk_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, 
 
 void targets_hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
                             const int64_t* starts, int64_t T, int32_t min_score, const int32_t* thresholds,
-                            int64_t* toffsets, Result* rows, int64_t cap, Semantics sem, int num_threads) {
+                            int64_t* toffsets, Result* rows, int64_t cap, Semantics sem, int num_threads,
+                            int64_t radius) {
   check_targets(starts, T, L1);
   if (cap < 0 || (cap > 0 && !rows)) throw Error("hits: cap rows need a rows buffer (cap = 0 counts only)");
   if (!toffsets) throw Error("hits: no hoffsets buffer");
+  check_peaks_radius(radius);
   const int64_t n_pairs = batch.size() * T;
   auto threshold = [&](int64_t pair) { return thresholds ? thresholds[pair] : min_score; };
   // phase 1: counts into toffsets[pair + 1], then their running totals
@@ -554,10 +576,11 @@ void targets_hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, 
     const int64_t L2 = batch.length(i);
     for (int64_t q = 0; q < T; ++q) {
       const TargetPair p = target_pair(t, s1, L1, batch.record(i), L2, starts, q, sem);
+      const uint8_t* peak = target_pair_peaks(prof, p, radius);
       const int32_t tp = threshold(i * T + q);
       int64_t c = 0;
-      for (int64_t o = 0; o < p.slice; ++o) c += prof[p.b + o].score >= tp ? 1 : 0;
-      if (p.boundary && p.bscore >= tp) ++c;
+      for (int64_t o = 0; o < p.slice; ++o) c += prof[p.b + o].score >= tp && (!peak || peak[o]) ? 1 : 0;
+      if (p.boundary && p.bscore >= tp && (!peak || peak[p.slice])) ++c;
       toffsets[i * T + q + 1] = c;
     }
     (void)C;
@@ -573,12 +596,14 @@ void targets_hits_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, 
       if (at >= cap) return;
       if (at == toffsets[i * T + q + 1]) continue;
       const TargetPair p = target_pair(t, s1, L1, batch.record(i), L2, starts, q, sem);
+      const uint8_t* peak = target_pair_peaks(prof, p, radius);
       const int32_t tp = threshold(i * T + q);
       for (int64_t o = 0; o < p.slice && at < cap; ++o) {
         const ProfileEntry& e = prof[p.b + o];
-        if (e.score >= tp) rows[at++] = Result{e.score, static_cast<int32_t>(o), e.k};
+        if (e.score >= tp && (!peak || peak[o])) rows[at++] = Result{e.score, static_cast<int32_t>(o), e.k};
       }
-      if (p.boundary && p.bscore >= tp && at < cap) rows[at++] = Result{p.bscore, static_cast<int32_t>(p.slice), 0};
+      if (p.boundary && p.bscore >= tp && (!peak || peak[p.slice]) && at < cap)
+        rows[at++] = Result{p.bscore, static_cast<int32_t>(p.slice), 0};
     }
     (void)C;
   });

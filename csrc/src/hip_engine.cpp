@@ -113,7 +113,7 @@ int parse_preload_set(const char* s) {
                {"profile", kPreloadProfile}, {"report", kPreloadReport}, {"hits", kPreloadHits},
                {"wire", kPreloadWire}, {"peaks", kPreloadPeaks}, {"summary", kPreloadSummary},
                {"targets", kPreloadTargets}, {"targets_summary", kPreloadTargetsSummary},
-               {"targets_rows", kPreloadTargetsRows}};
+               {"targets_rows", kPreloadTargetsRows}, {"targets_peaks", kPreloadTargetsPeaks}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -168,6 +168,10 @@ HipEngine::HipEngine(const EngineOptions& opt) : opt_(opt) {
   if (const char* tg = std::getenv("MOC_TARGETS_GROUP")) {  // forces one lane-group size of the targets kernel
     const int g = std::atoi(tg);
     if (g == 4 || g == 16 || g == 64) targets_group_ = g;
+  }
+  if (const char* ts = std::getenv("MOC_TARGETS_PEAKS_SEG")) {  // forces one segment width of the per-target peak pass
+    const int g = std::atoi(ts);
+    if (bounds::targets_peaks_seg_valid(g)) targets_peaks_seg_ = g;
   }
   // MOC_TILE16_WINWIDE=0: short records on an L1 ~ 1500..3050 problem keep the whole byte-pair image (A/B)
   if (const char* ww = std::getenv("MOC_TILE16_WINWIDE")) cfg_.tile16_window_wide = std::atoi(ww) != 0;
@@ -1075,6 +1079,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   if (!stream) stream = s_compute_;
   const bool chunked = kind != ProfileKind::Profile;  // through the bounded scratch
   const bool peaks = chunked && call.radius > 0;  // the distinct forms: a byte of peak marks beside every scratch entry
+  const bool target_peaks = peaks && (kind == ProfileKind::TargetsTopK || kind == ProfileKind::TargetsHits);
   const bool targets = kind == ProfileKind::Targets || kind == ProfileKind::TargetsSummary ||
                        kind == ProfileKind::TargetsTopK || kind == ProfileKind::TargetsHits;
   const int64_t entry_bytes = static_cast<int64_t>(sizeof(ProfileEntry)) + (peaks ? 1 : 0);
@@ -1082,7 +1087,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   // throws for a batch past the record or length limits, before the trace range opens and anything is queued
   const plan::ProfilePlan pp =
       plan::plan_profile(cfg_, sem_, h_offsets, n, chunked, entry_bytes, opt_.profile_scratch_bytes, peaks ? call.radius : 0,
-                         targets ? tc.h_starts : nullptr, targets ? tc.T : 0, targets && !tc.d_starts);
+                         targets ? tc.h_starts : nullptr, targets ? tc.T : 0, targets && !tc.d_starts, targets_peaks_seg_);
   TraceRange tr(facts.trace);
   MOC_HIP_CHECK(hipEventSynchronize(ev_plan_));  // previous call's plan buffers are free again
   ensure(d_plan_, d_plan_cap_, pp.bytes);
@@ -1133,7 +1138,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
     dev::launch_offset_profile(pv, bv, pa, stream);
     if (!chunked) continue;
     if (profile_timing_) MOC_HIP_CHECK(hipEventRecord(ev_select_[ev_select_used_++], stream));
-    if (peaks) {
+    if (peaks && !target_peaks) {
       dev::PeaksArgs ka;
       ka.view = view;
       ka.radius = static_cast<int32_t>(call.radius);
@@ -1154,6 +1159,18 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
                      : kind == ProfileKind::TargetsTopK ? bounds::targets_topk_group(max_slice)
                                                         : bounds::targets_group(max_slice);
       tsa.ta.out = tc.d_out;
+    }
+    if (target_peaks) {  // the segmented pass over every pair's own profile, never the plain one
+      dev::TargetsPeaksArgs ka;
+      ka.ta = tsa.ta;
+      ka.radius = static_cast<int32_t>(call.radius);
+      ka.seg = c.t_seg;
+      ka.any_short = c.t_any_short;
+      ka.max_tiles = c.t_max_tiles;
+      ka.lds_keys = c.t_lds_keys;
+      ka.num_cus = cfg_.num_cus;
+      ka.peak = d_peak;
+      dev::launch_targets_peaks(ka, pv, bv, stream);
     }
     switch (kind) {
       case ProfileKind::Profile: break;
@@ -1198,7 +1215,12 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
         tsa.width = call.summary.width;
         dev::launch_targets_summary(tsa, pv, bv, stream);
         break;
-      case ProfileKind::TargetsTopK: dev::launch_targets_topk(tsa.ta, call.K, pv, bv, stream); break;
+      case ProfileKind::TargetsTopK:
+        if (target_peaks)
+          dev::launch_targets_topk_peaks(tsa.ta, d_peak, call.K, pv, bv, stream);
+        else
+          dev::launch_targets_topk(tsa.ta, call.K, pv, bv, stream);
+        break;
       case ProfileKind::TargetsHits: {
         dev::TargetsHitsArgs tha;
         tha.ta = tsa.ta;
@@ -1208,7 +1230,10 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
         tha.sums = static_cast<int64_t*>(d_hits_sums_);
         tha.rows = call.hits.d_rows;
         tha.cap = call.hits.cap;
-        dev::launch_targets_hits(tha, pv, bv, stream);
+        if (target_peaks)
+          dev::launch_targets_hits_peaks(tha, d_peak, pv, bv, stream);
+        else
+          dev::launch_targets_hits(tha, pv, bv, stream);
         break;
       }
     }
@@ -1221,7 +1246,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   stats_.cells = pp.cells;
   stats_.records = n;
   stats_.chunks = static_cast<int64_t>(pp.chunks.size());
-  stats_.kernels = facts.kernels | (peaks ? 256 : 0);
+  stats_.kernels = facts.kernels | (peaks ? 256 : 0) | (target_peaks ? 16384 : 0);
 }
 
 void HipEngine::solve_profile_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
@@ -1442,26 +1467,28 @@ void HipEngine::targets_summary_placed(Placed& p, const int64_t* starts, int64_t
 // ---- per-target top-K and threshold hits ----------------------------------------------------------------
 void HipEngine::solve_targets_topk_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
                                           int64_t n, const int64_t* d_starts, const int64_t* h_starts, int64_t T, int K,
-                                          Result* d_out, hipStream_t stream) {
+                                          Result* d_out, hipStream_t stream, int64_t radius) {
   check_targets_call(h_starts, T);  // before any launch or change of state
   check_topk_k(K);
+  check_peaks_radius(radius);
   if (n > 0 && !d_out) throw Error("targets: no rows buffer");
   const TargetsCall tc{d_starts, h_starts, T, d_out};
-  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::TargetsTopK, nullptr, K, 0, {}, {}, tc}, stream);  // n <= 0: no launch
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::TargetsTopK, nullptr, K, radius, {}, {}, tc}, stream);  // n <= 0: no launch
 }
 
 void HipEngine::solve_targets_topk(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
-                                   int64_t T, int K, Result* out) {
+                                   int64_t T, int K, Result* out, int64_t radius) {
   check_targets_call(starts, T);
   check_topk_k(K);
+  check_peaks_radius(radius);
   Placed p = place_host(codes, offsets, n, rows_bytes(n * T, K));
-  if (p.n > 0) targets_topk_placed(p, starts, T, K, out);
+  if (p.n > 0) targets_topk_placed(p, starts, T, K, out, radius);
 }
 
 // d_out: rows (n * T * K Result); starts travel with the plan buffer
-void HipEngine::targets_topk_placed(Placed& p, const int64_t* starts, int64_t T, int K, Result* out) {
+void HipEngine::targets_topk_placed(Placed& p, const int64_t* starts, int64_t T, int K, Result* out, int64_t radius) {
   solve_targets_topk_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, K,
-                            static_cast<Result*>(slots_[0]->d_out), s_compute_);
+                            static_cast<Result*>(slots_[0]->d_out), s_compute_, radius);
   finish_placed(p, {{out, rows_bytes(p.n * T, K)}});
   stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1);
 }
@@ -1469,10 +1496,11 @@ void HipEngine::targets_topk_placed(Placed& p, const int64_t* starts, int64_t T,
 void HipEngine::solve_targets_hits_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
                                           int64_t n, const int64_t* d_starts, const int64_t* h_starts, int64_t T,
                                           int32_t min_score, const int32_t* d_thresholds, int64_t* d_toffsets,
-                                          Result* d_rows, int64_t cap, hipStream_t stream) {
+                                          Result* d_rows, int64_t cap, hipStream_t stream, int64_t radius) {
   check_targets_call(h_starts, T);  // before any launch or change of state
   if (cap < 0 || (cap > 0 && !d_rows)) throw Error("hits: cap rows need a rows buffer (cap = 0 counts only)");
   if (!d_toffsets) throw Error("hits: no hoffsets buffer");
+  check_peaks_radius(radius);
   if (n <= 0) {  // no launch: the index of an empty batch is its single 0
     finish_wire();
     MOC_HIP_CHECK(hipSetDevice(device_));
@@ -1482,27 +1510,28 @@ void HipEngine::solve_targets_hits_device(const uint8_t* d_codes, const int64_t*
   }
   const HitsCall hc{min_score, d_thresholds, d_toffsets, d_rows, d_rows ? cap : 0};
   const TargetsCall tc{d_starts, h_starts, T, nullptr};
-  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::TargetsHits, nullptr, 0, 0, hc, {}, tc}, stream);
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::TargetsHits, nullptr, 0, radius, hc, {}, tc}, stream);
 }
 
 void HipEngine::solve_targets_hits(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
                                    int64_t T, int32_t min_score, const int32_t* thresholds, int64_t* toffsets_out,
-                                   std::vector<Result>& rows_out, int64_t max_rows_hint) {
+                                   std::vector<Result>& rows_out, int64_t max_rows_hint, int64_t radius) {
   check_targets_call(starts, T);
+  check_peaks_radius(radius);
   finish_wire();
   MOC_HIP_CHECK(hipSetDevice(device_));
   rows_out.clear();
   hits_passes_ = 0;
   toffsets_out[0] = 0;
   Placed p = place_host(codes, offsets, n, hits_index_bytes(n * T) + thresholds_bytes(n * T));
-  if (p.n > 0) targets_hits_placed(p, starts, T, min_score, thresholds, toffsets_out, rows_out, max_rows_hint);
+  if (p.n > 0) targets_hits_placed(p, starts, T, min_score, thresholds, toffsets_out, rows_out, max_rows_hint, radius);
 }
 
 // d_out: toffsets (n T + 1) | thresholds (n T); the rows have hits' buffer, which the second pass may grow; starts
 // travel with the plan buffer
 void HipEngine::targets_hits_placed(Placed& p, const int64_t* starts, int64_t T, int32_t min_score,
                                     const int32_t* thresholds, int64_t* toffsets_out, std::vector<Result>& rows_out,
-                                    int64_t max_rows_hint) {
+                                    int64_t max_rows_hint, int64_t radius) {
   const int64_t pairs = p.n * T;
   const size_t hbytes = hits_index_bytes(pairs), tbytes = thresholds_bytes(pairs);
   char* d = static_cast<char*>(slots_[0]->d_out);
@@ -1513,7 +1542,7 @@ void HipEngine::targets_hits_placed(Placed& p, const int64_t* starts, int64_t T,
     ensure(d_hits_rows_, d_hits_rows_cap_, sizeof(Result) * static_cast<size_t>(cap));
     solve_targets_hits_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, min_score,
                               thresholds ? reinterpret_cast<const int32_t*>(d + hbytes) : nullptr,
-                              reinterpret_cast<int64_t*>(d), static_cast<Result*>(d_hits_rows_), cap, s_compute_);
+                              reinterpret_cast<int64_t*>(d), static_cast<Result*>(d_hits_rows_), cap, s_compute_, radius);
     copy_d2h(toffsets_out, d, hbytes, s_compute_);
     MOC_HIP_CHECK(hipStreamSynchronize(s_compute_));
     kernel_ms += device_kernel_ms();
@@ -1820,20 +1849,23 @@ void HipEngine::solve_targets_summary_wire(const WireBatch& b, const int64_t* st
   if (p.n > 0) targets_summary_placed(p, starts, T, summary_out, hist_out, bins, lo, width);
 }
 
-void HipEngine::solve_targets_topk_wire(const WireBatch& b, const int64_t* starts, int64_t T, int K, Result* out) {
+void HipEngine::solve_targets_topk_wire(const WireBatch& b, const int64_t* starts, int64_t T, int K, Result* out,
+                                        int64_t radius) {
   check_targets_call(starts, T);
   check_topk_k(K);
+  check_peaks_radius(radius);
   validate_wire(b);
   require_host_batch(b);
   finish_wire();
   Placed p = place_wire(b, rows_bytes(b.n * T, K));
-  if (p.n > 0) targets_topk_placed(p, starts, T, K, out);
+  if (p.n > 0) targets_topk_placed(p, starts, T, K, out, radius);
 }
 
 void HipEngine::solve_targets_hits_wire(const WireBatch& b, const int64_t* starts, int64_t T, int32_t min_score,
                                         const int32_t* thresholds, int64_t* toffsets_out, std::vector<Result>& rows_out,
-                                        int64_t max_rows_hint) {
+                                        int64_t max_rows_hint, int64_t radius) {
   check_targets_call(starts, T);
+  check_peaks_radius(radius);
   validate_wire(b);
   require_host_batch(b);
   finish_wire();
@@ -1841,7 +1873,7 @@ void HipEngine::solve_targets_hits_wire(const WireBatch& b, const int64_t* start
   hits_passes_ = 0;
   toffsets_out[0] = 0;
   Placed p = place_wire(b, hits_index_bytes(b.n * T) + thresholds_bytes(b.n * T));
-  if (p.n > 0) targets_hits_placed(p, starts, T, min_score, thresholds, toffsets_out, rows_out, max_rows_hint);
+  if (p.n > 0) targets_hits_placed(p, starts, T, min_score, thresholds, toffsets_out, rows_out, max_rows_hint, radius);
 }
 
 void HipEngine::report_wire(const WireBatch& b, int K, const Result* rows, int32_t* counts, uint8_t* marks) {

@@ -429,9 +429,14 @@ std::vector<dev::WaveStart> profile_runs(const Config& c, const int64_t* offsets
 
 ProfilePlan plan_profile(const Config& c, Semantics sem, const int64_t* offsets, int64_t n, bool chunked,
                          int64_t entry_bytes, int64_t scratch_bytes, int64_t radius, const int64_t* target_starts, int64_t T,
-                         bool upload_targets) {
+                         bool upload_targets, int targets_seg) {
   if (n >= (int64_t{1} << 31) - 1) throw Error("profile / top-K: more than 2^31 - 2 records in one call");
+  int64_t min_target = INT64_MAX;  // the shortest and (pp.max_target) the longest target
+  for (int64_t t = 0; target_starts && t < T; ++t) min_target = std::min(min_target, target_starts[t + 1] - target_starts[t]);
+  const bool target_peaks = radius > 0 && target_starts && T > 0;  // the per-target distinct forms
+  const bool spec = sem == Semantics::Spec;
   ProfilePlan pp;
+  for (int64_t t = 0; target_starts && t < T; ++t) pp.max_target = std::max(pp.max_target, target_starts[t + 1] - target_starts[t]);
   pp.poff.resize(static_cast<size_t>(n) + 1);
   pp.poff[0] = 0;
   int64_t sum_l2 = 0, max_need = 1;
@@ -469,19 +474,30 @@ ProfilePlan plan_profile(const Config& c, Semantics sem, const int64_t* offsets,
       const int64_t L2 = offsets[r + 1] - offsets[r], C = poff[r + 1] - poff[r];
       k.min_l2 = std::min(k.min_l2, L2);
       k.max_l2 = std::max(k.max_l2, L2);
-      if (radius > 0 && C >= 1 && C <= bounds::kPeaksWaveEntries) k.any_short = 1;
+      if (radius > 0 && !target_peaks && C >= 1 && C <= bounds::kPeaksWaveEntries) k.any_short = 1;
       max_c = std::max(max_c, C);
     }
-    if (radius > 0 && max_c > bounds::kPeaksWaveEntries) {
+    if (radius > 0 && !target_peaks && max_c > bounds::kPeaksWaveEntries) {
       k.max_tiles = static_cast<int32_t>((max_c + bounds::kPeaksTile - 1) / bounds::kPeaksTile);
       k.lds_keys = static_cast<int32_t>(std::min<int64_t>(bounds::kPeaksTile, max_c) + 2 * std::min<int64_t>(radius, max_c - 1));
+    }
+    if (target_peaks) {
+      // the chunk's longest pair profile (its shortest record against the longest target) and a lower bound of its
+      // shortest fitting one (its longest record against the shortest target)
+      const int64_t hi = bounds::targets_pair_count(pp.max_target, std::max<int64_t>(k.min_l2, 1), spec);
+      const int64_t lo = k.max_l2 <= min_target ? bounds::targets_pair_count(min_target, std::max<int64_t>(k.max_l2, 1), spec) : 0;
+      k.t_seg = bounds::targets_peaks_seg_valid(targets_seg) ? targets_seg : bounds::targets_peaks_seg(hi);
+      k.t_any_short = hi >= 2 && lo <= k.t_seg ? 1 : 0;
+      if (hi > k.t_seg) {
+        k.t_max_tiles = static_cast<int32_t>((hi + bounds::kPeaksTile - 1) / bounds::kPeaksTile);
+        k.t_lds_keys = static_cast<int32_t>(std::min<int64_t>(bounds::kPeaksTile, hi) + 2 * std::min<int64_t>(radius, hi - 1));
+      }
     }
     pp.max_entries = std::max(pp.max_entries, k.entries);
     pp.max_records = std::max(pp.max_records, r1 - r0);
     pp.chunks.push_back(k);
     r0 = r1;
   }
-  for (int64_t t = 0; target_starts && t < T; ++t) pp.max_target = std::max(pp.max_target, target_starts[t + 1] - target_starts[t]);
   pp.starts_off = sizeof(int64_t) * pp.poff.size();
   pp.targets_off = pp.starts_off + sizeof(dev::WaveStart) * pp.starts.size();  // 8-byte aligned: both parts are
   pp.bytes = pp.targets_off + (target_starts && upload_targets ? sizeof(int64_t) * (static_cast<size_t>(T) + 1) : 0);

@@ -173,6 +173,27 @@ def _decl(lib):
                                                          c_int64, c_void_p]),
         "moc_engine_solve_targets_hits_wire": (c_int, [c_void_p, P(WireBatch), c_void_p, c_int64, c_int32, c_void_p,
                                                        c_int64, c_void_p, c_void_p, c_int64]),
+        "moc_cpu_targets_topk_distinct": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                                  c_int64, c_int, c_int, c_int, c_int64, c_void_p]),
+        "moc_cpu_targets_hits_distinct": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                                  c_int64, c_int, c_int, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                                  c_int64]),
+        "moc_engine_solve_targets_topk_distinct": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                                           c_int, c_int64, c_void_p]),
+        "moc_engine_solve_targets_topk_device_distinct": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                                                  c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p,
+                                                                  c_void_p]),
+        "moc_engine_solve_targets_topk_wire_distinct": (c_int, [c_void_p, P(WireBatch), c_void_p, c_int64, c_int,
+                                                                c_int64, c_void_p]),
+        "moc_engine_solve_targets_hits_distinct": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                                           c_int32, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                                           c_int64]),
+        "moc_engine_solve_targets_hits_device_distinct": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                                                  c_void_p, c_void_p, c_int64, c_int32, c_void_p,
+                                                                  c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+        "moc_engine_solve_targets_hits_wire_distinct": (c_int, [c_void_p, P(WireBatch), c_void_p, c_int64, c_int32,
+                                                                c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                                                c_int64]),
         "moc_partition": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_double, c_void_p]),
         "moc_device_count": (c_int, []),
         "moc_host_register": (c_int, [c_void_p, c_size_t]),

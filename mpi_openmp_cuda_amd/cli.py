@@ -94,6 +94,12 @@ def main(argv=None) -> int:
                     help="with --targets: as --target-min-score with every (record, target) pair's own threshold, that "
                          "target's best score minus D (D >= 0). Not with --target-summary, --target-top or "
                          "--target-min-score")
+    ap.add_argument("--target-distinct", type=int, default=None, metavar="R",
+                    help="with --targets and --target-top K (K > 1) or --target-min-score / --target-within: distinct "
+                         "placements inside every target only — a placement is printed only when no placement of the "
+                         "same target within R of it (0..2048) scores higher, or the same at a smaller n; the windows "
+                         "end at the target's own first and last placement. Same line formats, fewer lines; R = 0 "
+                         "prints what no flag prints")
     a = ap.parse_args(argv)
     if not 1 <= a.top <= 64:
         ap.error("--top K: K must be in 1..64")
@@ -149,6 +155,14 @@ def main(argv=None) -> int:
             ap.error("--target-min-score T: T must be an int32")
         if a.target_within is not None and a.target_within < 0:
             ap.error("--target-within D: D must be >= 0")
+    if a.target_distinct is not None:
+        if not 0 <= a.target_distinct <= 2048:
+            ap.error("--target-distinct R: R must be in 0..2048")
+        if a.targets is None or not (a.target_min_score is not None or a.target_within is not None or
+                                     (a.target_top or 0) > 1):
+            ap.error("--target-distinct R filters the lines of --targets FILE with --target-top K (K > 1) or "
+                     "--target-min-score / --target-within: give one of them")
+    target_radius = a.target_distinct or 0
     if a.targets is not None:
         if a.top > 1 or a.show_alignment or want_hits or a.distinct is not None or a.summary or a.hist is not None:
             ap.error("--targets does not combine with --top K > 1, --show-alignment, --min-score, --within, "
@@ -230,10 +244,11 @@ def main(argv=None) -> int:
     if a.targets is not None:
         try:
             if a.target_top is not None:
-                target_topk = search.run_targets_topk(problem, target_set, a.target_top, Semantics.parse(a.semantics))
+                target_topk = search.run_targets_topk(problem, target_set, a.target_top, Semantics.parse(a.semantics),
+                                                      target_radius)
             elif a.target_min_score is not None or a.target_within is not None:
                 target_hits = search.run_targets_hits(problem, target_set, a.target_min_score, a.target_within,
-                                                      Semantics.parse(a.semantics))
+                                                      Semantics.parse(a.semantics), target_radius)
             elif a.target_summary:
                 target_summary = search.run_targets_summary(problem, target_set, *target_hist_args,
                                                             semantics=Semantics.parse(a.semantics))

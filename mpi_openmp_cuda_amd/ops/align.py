@@ -530,27 +530,29 @@ def targets_best(rows, z=None):
 
 
 def targets_catalog_rows(rows, targets):
-    """Multi-target rows [n, T, 3] with their offsets moved from the targets to the catalog: n + starts[t]; empty
-    rows (score INT32_MIN) stay untouched. The result is a [n, T, 3] row block the report calls take as it is
-    (``search_report_cpu`` / ``report`` / ``report_device`` work on the catalog; T <= 64 there). ``rows``: a numpy
-    array, or a torch tensor — then the result is a tensor on its device, computed there without a
-    synchronisation (the starts go up with a non-blocking copy)."""
+    """Multi-target rows [n, T, 3], or per-target top-K rows [n, T, K, 3], with their offsets moved from the targets
+    to the catalog: n + starts[t]; empty rows (score INT32_MIN) stay untouched. The result has the shape of ``rows``;
+    a [n, T, 3] block — or a top-K one reshaped to [n, T * K, 3] — is what the report calls take as it is
+    (``search_report_cpu`` / ``report`` / ``report_device`` work on the catalog; at most 64 rows per record there).
+    ``rows``: a numpy array, or a torch tensor — then the result is a tensor on its device, computed there without
+    a synchronisation (the starts go up with a non-blocking copy)."""
     starts = np.ascontiguousarray(targets.starts if isinstance(targets, TargetSet) else targets, dtype=np.int64)
+    T = starts.shape[0] - 1
     if isinstance(rows, np.ndarray) or not hasattr(rows, "device"):
         r = np.array(rows, dtype=np.int32)
-        if r.ndim != 3 or r.shape[2] != 3 or r.shape[1] != starts.shape[0] - 1:
-            raise ValueError(f"targets_catalog_rows needs [n, T, 3] rows for the T = {starts.shape[0] - 1} targets")
-        shift = np.where(r[:, :, 0] == _I32.min, 0, starts[None, :-1])
-        r[:, :, 1] = (r[:, :, 1] + shift).astype(np.int32)
+        if r.ndim not in (3, 4) or r.shape[-1] != 3 or r.shape[1] != T:
+            raise ValueError(f"targets_catalog_rows needs [n, T, 3] or [n, T, K, 3] rows for the T = {T} targets")
+        b = starts[:-1].reshape((1, T) + (1,) * (r.ndim - 3))  # one start per target, broadcast over K
+        r[..., 1] = (r[..., 1] + np.where(r[..., 0] == _I32.min, 0, b)).astype(np.int32)
         return r
     import torch
 
-    assert rows.dtype == torch.int32 and rows.dim() == 3 and rows.shape[2] == 3
-    assert rows.shape[1] == starts.shape[0] - 1
+    assert rows.dtype == torch.int32 and rows.dim() in (3, 4) and rows.shape[-1] == 3
+    assert rows.shape[1] == T
     b = torch.from_numpy(starts[:-1].astype(np.int32)).to(rows.device, non_blocking=True)
-    shift = torch.where(rows[:, :, 0] == _I32.min, torch.zeros_like(b).expand(rows.shape[0], -1), b.expand(rows.shape[0], -1))
+    b = b.reshape((1, T) + (1,) * (rows.dim() - 3)).expand(rows.shape[:-1])
     out = rows.clone()
-    out[:, :, 1] += shift
+    out[..., 1] += torch.where(rows[..., 0] == _I32.min, torch.zeros_like(b), b)
     return out.contiguous()
 
 
@@ -624,10 +626,10 @@ def targets_zscore(summary):
 # ---- per-target top-K and threshold hits: the rows of every (record, target) pair's target profile
 def _targets_rows_check(rc):
     """A native per-target top-K / hits call's status: target-set errors ("targets:"), a K out of range ("top-K:")
-    and buffer errors ("hits:") are ValueErrors, anything else a NativeError."""
+    buffer errors ("hits:") and a radius out of range ("distinct:") are ValueErrors, anything else a NativeError."""
     if rc != 0:
         msg = _lib.lib().moc_last_error().decode(errors="replace")
-        if msg.startswith(("targets:", "top-K:", "hits:")):
+        if msg.startswith(("targets:", "top-K:", "hits:", "distinct:")):
             raise ValueError(msg)
         raise _lib.NativeError(msg)
 
@@ -658,45 +660,63 @@ def _targets_hits_thresholds(n: int, T: int, min_score, thresholds, within, best
     return 0, within_thresholds(np.asarray(best_rows())[:, :, 0], within)
 
 
+def _targets_hits_args(n: int, T: int, min_score, thresholds, within, radius, best_rows):
+    """:func:`_targets_hits_thresholds`, then :func:`_check_radius` — the order of the per-target hits errors — with
+    the radius checked before ``best_rows`` runs anything: (scalar, thresholds or None, radius)."""
+    def best():
+        _check_radius(radius)
+        return best_rows()
+
+    m, t = _targets_hits_thresholds(n, T, min_score, thresholds, within, best)
+    return m, t, _check_radius(radius)
+
+
 def search_targets_topk_cpu(problem: Problem, targets, K: int, semantics=Semantics.REFERENCE,
-                            threads: int = 0) -> np.ndarray:
+                            threads: int = 0, radius: int = 0) -> np.ndarray:
     """Per-target top-K on the CPU engine. ``problem.seq1`` is the catalog and ``targets`` its :class:`TargetSet` (or
     just the starts). Returns int32 [n, T, K, 3]: ``out[i, t]`` is exactly :func:`search_topk_cpu`'s [K, 3] block of
     record i against target t alone — the pair's best placements in the order higher score, then smaller n, n
     relative to the target's start, padded with (INT32_MIN, 0, 0) — so no row straddles two targets. ``K = 1`` is
-    :func:`search_targets_cpu`. ValueError for an invalid target set ("targets: ...", first) and for K outside
-    1..64."""
+    :func:`search_targets_cpu`. ``radius`` > 0 keeps the distinct placements only: the peaks of radius ``radius`` of
+    every pair's OWN profile (its windows clipped to the pair's entries, the boundary entry among them), so
+    ``out[i, t]`` is :func:`search_topk_cpu` with that radius on target t alone; row 0 is the same at every radius.
+    ValueError for an invalid target set ("targets: ...", first), for K outside 1..64, then for the radius
+    ("distinct: ...")."""
     starts = _starts_of(targets, problem.L1)
     K = _check_k(K)
+    radius = _check_radius(radius)
     T = starts.shape[0] - 1
     out = np.zeros((problem.n, T, K, 3), np.int32)
-    _targets_rows_check(_lib.lib().moc_cpu_targets_topk(
+    _targets_rows_check(_lib.lib().moc_cpu_targets_topk_distinct(
         _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
         _lib.ptr(problem.offsets), problem.n, _lib.ptr(starts), T, int(Semantics.parse(semantics)), int(threads), K,
-        _lib.ptr(out)))
+        radius, _lib.ptr(out)))
     return out
 
 
 def search_targets_hits_cpu(problem: Problem, targets, min_score=None, thresholds=None, within=None,
-                            semantics=Semantics.REFERENCE, threads: int = 0):
+                            semantics=Semantics.REFERENCE, threads: int = 0, radius: int = 0):
     """Per-target threshold hits on the CPU engine: ``(rows, toffsets)``. Pair p = i * T + t's hits are exactly
     :func:`search_hits_cpu`'s of record i against target t alone under the pair's threshold — int32 rows (score, n
     relative to the target's start, k), ascending in n, at ``rows[toffsets[p]:toffsets[p + 1]]``; ``toffsets`` is
     int64 [n * T + 1]. Exactly one of ``min_score`` (one int32 for the call; INT32_MIN selects every pair's whole
     target profile), ``thresholds`` (int32 [n, T], or [n] broadcast over the targets) and ``within`` (D >= 0: every
     placement within D of the pair's own best score, from :func:`search_targets_cpu`). A record longer than a target
-    has no hits there. ValueError for an invalid target set ("targets: ...", first) and for malformed thresholds."""
+    has no hits there. ``radius`` > 0 keeps the distinct placements only, the peaks of every pair's own profile as
+    :func:`search_targets_topk_cpu` defines them: :func:`search_hits_cpu` with that radius on target t alone (a pair's
+    best entry is always a peak, so ``within`` is relative to the same score). ValueError for an invalid target set
+    ("targets: ...", first), for malformed thresholds, then for the radius ("distinct: ...")."""
     sem = Semantics.parse(semantics)
     starts = _starts_of(targets, problem.L1)
     T = starts.shape[0] - 1
-    m, t = _targets_hits_thresholds(problem.n, T, min_score, thresholds, within,
-                                    lambda: search_targets_cpu(problem, starts, sem, threads))
+    m, t, radius = _targets_hits_args(problem.n, T, min_score, thresholds, within, radius,
+                                      lambda: search_targets_cpu(problem, starts, sem, threads))
     toffsets = np.zeros(problem.n * T + 1, np.int64)
 
     def call(rows, cap):
-        _targets_rows_check(_lib.lib().moc_cpu_targets_hits(
+        _targets_rows_check(_lib.lib().moc_cpu_targets_hits_distinct(
             _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
-            _lib.ptr(problem.offsets), problem.n, _lib.ptr(starts), T, int(sem), int(threads), m, _lib.ptr(t),
+            _lib.ptr(problem.offsets), problem.n, _lib.ptr(starts), T, int(sem), int(threads), m, _lib.ptr(t), radius,
             _lib.ptr(toffsets), _lib.ptr(rows), cap))
 
     call(None, 0)  # counts
@@ -1373,58 +1393,65 @@ class HipSearchEngine:
         return out
 
     # ---- per-target top-K and threshold hits (byte letters, dense offsets; csrc/src/hip/targets_rows_kernels.hip)
-    def solve_targets_topk(self, codes: np.ndarray, offsets: np.ndarray, targets, K: int) -> np.ndarray:
+    def solve_targets_topk(self, codes: np.ndarray, offsets: np.ndarray, targets, K: int, radius: int = 0) -> np.ndarray:
         """Host CSR -> int32 [n, T, K, 3] rows as :func:`search_targets_topk_cpu` returns them, against the engine's
         Seq1 as the catalog of ``targets``. One pass: the chunks of :meth:`solve_targets` with the per-target top-K
         kernel behind each chunk's catalog profile — 12 T K bytes come back per record, never the profile.
         Synchronous; ``stats()["kernels"]`` names ``targets_topk``. ValueError for an invalid target set (first) and
-        for K outside 1..64, raised before anything is launched and without a change to ``stats()``."""
+        for K outside 1..64, then for the radius, raised before anything is launched and without a change to
+        ``stats()``. ``radius`` > 0: the distinct placements per target (search_targets_topk_cpu's) — the segmented
+        peak pass over every pair's own profile (csrc/src/hip/targets_peaks_kernels.hip) runs between each chunk's
+        profile and masked per-target kernels, and ``stats()["kernels"]`` also names ``peaks`` and ``targets_peaks``;
+        ``radius = 0`` is launch for launch the call without it."""
         starts = _starts_of(targets, self.problem_L1)
         K = _check_k(K)
+        radius = _check_radius(radius)
         T = starts.shape[0] - 1
         codes = np.ascontiguousarray(codes, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = offsets.shape[0] - 1
         out = np.zeros((n, T, K, 3), np.int32)
-        _targets_rows_check(_lib.lib().moc_engine_solve_targets_topk(self._h, _lib.ptr(codes), _lib.ptr(offsets), n,
-                                                                     _lib.ptr(starts), T, K, _lib.ptr(out)))
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_topk_distinct(
+            self._h, _lib.ptr(codes), _lib.ptr(offsets), n, _lib.ptr(starts), T, K, radius, _lib.ptr(out)))
         return out
 
     def solve_targets_hits(self, codes: np.ndarray, offsets: np.ndarray, targets, min_score=None, thresholds=None,
-                           within=None, max_rows: Optional[int] = None):
+                           within=None, max_rows: Optional[int] = None, radius: int = 0):
         """Host CSR -> ``(rows, toffsets)`` as :func:`search_targets_hits_cpu` returns them (exactly one of
         ``min_score``, ``thresholds`` — [n, T], or [n] broadcast over the targets — and ``within``, each pair's own
         best score from :meth:`solve_targets` on this engine minus D). One pass over the chunks of
         :meth:`solve_targets` with count, prefix sum over the pairs and compaction behind each chunk's catalog
         profile. Optimistic: room for ``max_rows`` rows (default n T) and exactly one more pass when more entries
         qualify (:meth:`hits_passes`). Synchronous; ``stats()["kernels"]`` names ``targets_hits``. ValueError as
-        search_targets_hits_cpu, before anything is launched."""
+        search_targets_hits_cpu, before anything is launched. ``radius`` > 0: the distinct placements per target, as
+        :meth:`solve_targets_topk` (``stats()["kernels"]`` also names ``peaks`` and ``targets_peaks``)."""
         starts = _starts_of(targets, self.problem_L1)
         T = starts.shape[0] - 1
         codes = np.ascontiguousarray(codes, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = offsets.shape[0] - 1
-        m, t = _targets_hits_thresholds(n, T, min_score, thresholds, within,
-                                        lambda: self.solve_targets(codes, offsets, starts))
+        m, t, radius = _targets_hits_args(n, T, min_score, thresholds, within, radius,
+                                          lambda: self.solve_targets(codes, offsets, starts))
         toffsets = np.zeros(n * T + 1, np.int64)
-        _targets_rows_check(_lib.lib().moc_engine_solve_targets_hits(
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_hits_distinct(
             self._h, _lib.ptr(codes), _lib.ptr(offsets), n, _lib.ptr(starts), T, m, _lib.ptr(t),
-            -1 if max_rows is None else int(max_rows), _lib.ptr(toffsets), None, 0))
+            -1 if max_rows is None else int(max_rows), radius, _lib.ptr(toffsets), None, 0))
         total = int(toffsets[-1])
         rows = np.zeros((total, 3), np.int32)
         _lib.check(_lib.lib().moc_engine_hits_rows(_lib.ptr(rows) if total else None, total))
         return rows, toffsets
 
     def solve_targets_topk_device(self, codes_t, offsets_t, h_offsets: np.ndarray, targets, K: int, out_t=None,
-                                  starts_t=None, stream=None):
+                                  starts_t=None, stream=None, radius: int = 0):
         """Device-resident batch (as :meth:`solve_device`) -> ``out_t``, an int32 [n, T, K, 3] tensor of per-target
         top-K rows on the codes' device (allocated when None; every row is written). ``starts_t`` as
         :meth:`solve_targets_device`. Queued on ``stream`` (default: the current stream); returns immediately.
-        ValueError as :meth:`solve_targets_topk`."""
+        ``radius`` and ValueError as :meth:`solve_targets_topk`."""
         import torch
 
         starts = _starts_of(targets, self.problem_L1)
         K = _check_k(K)
+        radius = _check_radius(radius)
         T = starts.shape[0] - 1
         h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
         n = h_offsets.shape[0] - 1
@@ -1436,15 +1463,15 @@ class HipSearchEngine:
         assert out_t.dtype == torch.int32 and out_t.is_contiguous() and tuple(out_t.shape) == (n, T, K, 3)
         if starts_t is not None:
             assert starts_t.dtype == torch.int64 and starts_t.is_contiguous() and starts_t.numel() == T + 1
-        _targets_rows_check(_lib.lib().moc_engine_solve_targets_topk_device(
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_topk_device_distinct(
             self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
-            n, ctypes.c_void_p(starts_t.data_ptr()) if starts_t is not None else None, _lib.ptr(starts), T, K,
+            n, ctypes.c_void_p(starts_t.data_ptr()) if starts_t is not None else None, _lib.ptr(starts), T, K, radius,
             ctypes.c_void_p(out_t.data_ptr()), ctypes.c_void_p(stream.cuda_stream)))
         return out_t
 
     def solve_targets_hits_device(self, codes_t, offsets_t, h_offsets: np.ndarray, targets, min_score=None,
                                   thresholds_t=None, cap: Optional[int] = None, rows_t=None, toffsets_t=None,
-                                  starts_t=None, stream=None):
+                                  starts_t=None, stream=None, radius: int = 0):
         """Device-resident batch (as :meth:`solve_device`) -> ``(rows_t, toffsets_t)``: ``toffsets_t`` an int64
         [n T + 1] tensor, always complete and exact; ``rows_t`` an int32 [cap, 3] tensor (``cap`` default n T) of
         which the rows with a flat index < cap are written and nothing else is touched — compare
@@ -1452,7 +1479,7 @@ class HipSearchEngine:
         ``thresholds_t``, an int32 [n, T] tensor on the same device — ``solve_targets_device(...)[..., 0] - D``
         (in int64, clamped to int32) queued on the same stream gives "within D of each pair's best" without a sync.
         Both result tensors are allocated when None. Queued on ``stream`` (default: the current stream); returns
-        immediately. ValueError as :meth:`solve_targets_hits`."""
+        immediately. ``radius`` and ValueError as :meth:`solve_targets_hits`."""
         import torch
 
         starts = _starts_of(targets, self.problem_L1)
@@ -1478,6 +1505,7 @@ class HipSearchEngine:
         cap = int(cap)
         if cap < 0:
             raise ValueError("hits: cap must be >= 0")
+        radius = _check_radius(radius)
         if rows_t is None:
             rows_t = torch.empty((cap, 3), dtype=torch.int32, device=codes_t.device)
         if toffsets_t is None:
@@ -1487,41 +1515,42 @@ class HipSearchEngine:
         assert toffsets_t.dtype == torch.int64 and toffsets_t.is_contiguous() and toffsets_t.numel() == n * T + 1
         if starts_t is not None:
             assert starts_t.dtype == torch.int64 and starts_t.is_contiguous() and starts_t.numel() == T + 1
-        _targets_rows_check(_lib.lib().moc_engine_solve_targets_hits_device(
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_hits_device_distinct(
             self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
             n, ctypes.c_void_p(starts_t.data_ptr()) if starts_t is not None else None, _lib.ptr(starts), T, m,
-            ctypes.c_void_p(thresholds_t.data_ptr()) if thresholds_t is not None else None,
+            ctypes.c_void_p(thresholds_t.data_ptr()) if thresholds_t is not None else None, radius,
             ctypes.c_void_p(toffsets_t.data_ptr()), ctypes.c_void_p(rows_t.data_ptr()) if cap else None, cap,
             ctypes.c_void_p(stream.cuda_stream)))
         return rows_t, toffsets_t
 
-    def solve_targets_topk_wire(self, ws, targets, K: int, shift: int = 0) -> np.ndarray:
+    def solve_targets_topk_wire(self, ws, targets, K: int, shift: int = 0, radius: int = 0) -> np.ndarray:
         """Host wire batch -> int32 [n, T, K, 3] per-target top-K rows, as :meth:`solve_targets_topk` on the decoded
-        records. See :meth:`solve_profile_wire`."""
+        records (``radius`` included). See :meth:`solve_profile_wire`."""
         starts = _starts_of(targets, self.problem_L1)
         K = _check_k(K)
+        radius = _check_radius(radius)
         T = starts.shape[0] - 1
         b, keep = wire_batch_of(ws, shift)
         out = np.zeros((ws.n, T, K, 3), np.int32)
-        _targets_rows_check(_lib.lib().moc_engine_solve_targets_topk_wire(self._h, ctypes.byref(b), _lib.ptr(starts), T,
-                                                                          K, _lib.ptr(out)))
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_topk_wire_distinct(
+            self._h, ctypes.byref(b), _lib.ptr(starts), T, K, radius, _lib.ptr(out)))
         del keep
         return out
 
     def solve_targets_hits_wire(self, ws, targets, min_score=None, thresholds=None, within=None,
-                                max_rows: Optional[int] = None, shift: int = 0):
+                                max_rows: Optional[int] = None, shift: int = 0, radius: int = 0):
         """Host wire batch -> ``(rows, toffsets)``, as :meth:`solve_targets_hits` on the decoded records (``within``
-        runs :meth:`solve_targets_wire` first). See :meth:`solve_profile_wire`."""
+        runs :meth:`solve_targets_wire` first; ``radius`` included). See :meth:`solve_profile_wire`."""
         starts = _starts_of(targets, self.problem_L1)
         T = starts.shape[0] - 1
         n = ws.n
-        m, t = _targets_hits_thresholds(n, T, min_score, thresholds, within,
-                                        lambda: self.solve_targets_wire(ws, starts, shift))
+        m, t, radius = _targets_hits_args(n, T, min_score, thresholds, within, radius,
+                                          lambda: self.solve_targets_wire(ws, starts, shift))
         b, keep = wire_batch_of(ws, shift)
         toffsets = np.zeros(n * T + 1, np.int64)
-        _targets_rows_check(_lib.lib().moc_engine_solve_targets_hits_wire(
+        _targets_rows_check(_lib.lib().moc_engine_solve_targets_hits_wire_distinct(
             self._h, ctypes.byref(b), _lib.ptr(starts), T, m, _lib.ptr(t), -1 if max_rows is None else int(max_rows),
-            _lib.ptr(toffsets), None, 0))
+            radius, _lib.ptr(toffsets), None, 0))
         del keep
         total = int(toffsets[-1])
         rows = np.zeros((total, 3), np.int32)
@@ -1852,7 +1881,7 @@ class HipSearchEngine:
                                              (32, "report"), (64, "hits"), (128, "wire"), (256, "peaks"),
                                              (512, "summary"), (1024, "targets"),
                                              (2048, "targets_summary"), (4096, "targets_topk"),
-                                             (8192, "targets_hits"))
+                                             (8192, "targets_hits"), (16384, "targets_peaks"))
                         if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
@@ -1974,18 +2003,19 @@ def align_targets_summary_device(engine: HipSearchEngine, codes_t, offsets_t, h_
                                                None, stream)
 
 
-def align_targets_topk_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, targets, K: int, stream=None):
-    """torch-facing op: the per-target top-K rows as an int32 [n, T, K, 3] tensor on the codes' device; see
-    :meth:`HipSearchEngine.solve_targets_topk_device`."""
-    return engine.solve_targets_topk_device(codes_t, offsets_t, h_offsets, targets, K, None, None, stream)
+def align_targets_topk_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, targets, K: int, stream=None,
+                              radius: int = 0):
+    """torch-facing op: the per-target top-K rows as an int32 [n, T, K, 3] tensor on the codes' device (``radius`` >
+    0: the distinct placements per target); see :meth:`HipSearchEngine.solve_targets_topk_device`."""
+    return engine.solve_targets_topk_device(codes_t, offsets_t, h_offsets, targets, K, None, None, stream, radius)
 
 
 def align_targets_hits_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, targets, min_score=None,
-                              thresholds_t=None, cap: Optional[int] = None, stream=None):
-    """torch-facing op: the per-target threshold hits as ``(rows_t, toffsets_t)`` on the codes' device; see
-    :meth:`HipSearchEngine.solve_targets_hits_device`."""
+                              thresholds_t=None, cap: Optional[int] = None, stream=None, radius: int = 0):
+    """torch-facing op: the per-target threshold hits as ``(rows_t, toffsets_t)`` on the codes' device (``radius`` >
+    0: the distinct placements per target); see :meth:`HipSearchEngine.solve_targets_hits_device`."""
     return engine.solve_targets_hits_device(codes_t, offsets_t, h_offsets, targets, min_score, thresholds_t, cap, None,
-                                            None, None, stream)
+                                            None, None, stream, radius)
 
 
 def align_report_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, rows_t, marks: bool = False,

@@ -31,7 +31,7 @@ from ..ops.align import (HipSearchEngine, decode_keys, device_count, keys_to_ord
                         profile_offsets, search_cpu, search_hits_cpu, search_keys_cpu, search_report_cpu,
                         search_summary_cpu, search_targets_cpu, search_targets_summary_cpu, search_topk_cpu,
                          summary_bound, within_thresholds,
-                         TargetSet, check_targets, _summary_args, _check_k, search_targets_hits_cpu,
+                         TargetSet, check_targets, _summary_args, _check_k, _check_radius, search_targets_hits_cpu,
                          search_targets_topk_cpu)
 from ..utils.timer import PhaseTimer
 from . import dist as D
@@ -354,12 +354,14 @@ class DistributedSearch:
         starts = D.bcast_array(ctx, starts if ctx.is_root else None, int(hdr[0]), np.int64)
         return check_targets(starts, int(hdr[1]))
 
-    def run_targets_topk(self, problem: Optional[Problem], targets=None, K: int = 1, semantics=Semantics.REFERENCE):
+    def run_targets_topk(self, problem: Optional[Problem], targets=None, K: int = 1, semantics=Semantics.REFERENCE,
+                         radius: int = 0):
         """Per-target top-K (ops.align.search_targets_topk_cpu's int32 [n, T, K, 3] rows; ``K`` the same on every rank,
         ``targets`` as :meth:`run_targets`) for the ``records`` partition: every rank ranks its cost-balanced slice of
         the node-shared input window against every target, and one MAX all-reduce of an int64 array that is INT64_MIN
         outside the rank's slice collects the rows (no new transport). Returns the rows on the root, else None. One
-        node; byte letters through the engines' per-target top-K calls."""
+        node; byte letters through the engines' per-target top-K calls. ``radius`` > 0 (the same on every rank): the
+        distinct placements per target, search_targets_topk_cpu's."""
         if self.partition != "records":
             raise ValueError("per-target top-K runs on record slices (--partition records, one node): the offsets "
                              "partition combines one packed key per record and cannot carry T K rows")
@@ -367,6 +369,7 @@ class DistributedSearch:
         sem = Semantics.parse(semantics)
         starts = self._bcast_starts(problem, targets)  # the target set's errors come first
         K = _check_k(K)
+        radius = _check_radius(radius)
         nt = starts.shape[0] - 1
         with T.phase("bcast"):
             prob, sem, n, total, bounds = self._setup(problem, sem)
@@ -378,11 +381,11 @@ class DistributedSearch:
             if e > b:
                 offsets = np.asarray(win.offsets[b:e + 1])
                 if self.engine is not None:
-                    rows[b:e] = self.engine.solve_targets_topk(np.asarray(win.codes), offsets, starts, K)
+                    rows[b:e] = self.engine.solve_targets_topk(np.asarray(win.codes), offsets, starts, K, radius)
                 else:
                     sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
                                   offsets - offsets[0])
-                    rows[b:e] = search_targets_topk_cpu(sub, starts, K, sem, self.threads)
+                    rows[b:e] = search_targets_topk_cpu(sub, starts, K, sem, self.threads, radius)
         with T.phase("gather"):
             rows = D.allreduce_max_int64(ctx, rows.reshape(-1)).reshape(n, nt, K, 3)
             D.barrier(ctx)
@@ -390,7 +393,7 @@ class DistributedSearch:
         return rows.astype(np.int32) if ctx.is_root else None
 
     def run_targets_hits(self, problem: Optional[Problem], targets=None, min_score=None, within=None,
-                         semantics=Semantics.REFERENCE):
+                         semantics=Semantics.REFERENCE, radius: int = 0):
         """Per-target threshold hits (ops.align.search_targets_hits_cpu's ``(rows, toffsets)``; exactly one of
         ``min_score`` and ``within``, the same on every rank; ``targets`` as :meth:`run_targets`) together with the
         multi-target rows, for the ``records`` partition: every rank computes its cost-balanced slice of the
@@ -398,7 +401,8 @@ class DistributedSearch:
         with one MAX all-reduce of an int64 array that is INT64_MIN outside the rank's slice. ``within`` takes each
         pair's own best score from the multi-target search of the same slice. Returns ``(best, rows, toffsets)`` on
         the root — ``best`` the int32 [n, T, 3] multi-target rows — else None. One node; byte letters through the
-        engines' per-target hits calls."""
+        engines' per-target hits calls. ``radius`` > 0 (the same on every rank): the distinct placements per target,
+        search_targets_hits_cpu's."""
         if self.partition != "records":
             raise ValueError("per-target hits run on record slices (--partition records, one node): the offsets "
                              "partition combines one packed key per record and cannot carry a list of rows")
@@ -409,6 +413,7 @@ class DistributedSearch:
             raise ValueError("hits: give exactly one of min_score, within")
         if within is not None and int(within) < 0:
             raise ValueError(f"hits: within must be >= 0, got {int(within)}")
+        radius = _check_radius(radius)
         nt = starts.shape[0] - 1
         with T.phase("bcast"):
             prob, sem, n, total, bounds = self._setup(problem, sem)
@@ -430,12 +435,12 @@ class DistributedSearch:
                 if self.engine is not None:
                     codes = np.asarray(win.codes)
                     best[b:e] = self.engine.solve_targets(codes, offsets, starts)
-                    mine, h = self.engine.solve_targets_hits(codes, offsets, starts, **kw(best[b:e, :, 0]))
+                    mine, h = self.engine.solve_targets_hits(codes, offsets, starts, radius=radius, **kw(best[b:e, :, 0]))
                 else:
                     sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
                                   offsets - offsets[0])
                     best[b:e] = search_targets_cpu(sub, starts, sem, self.threads)
-                    mine, h = search_targets_hits_cpu(sub, starts, semantics=sem, threads=self.threads,
+                    mine, h = search_targets_hits_cpu(sub, starts, semantics=sem, threads=self.threads, radius=radius,
                                                       **kw(best[b:e, :, 0]))
                 counts[b * nt:e * nt] = np.diff(h)
         with T.phase("gather"):

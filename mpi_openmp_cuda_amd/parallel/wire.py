@@ -143,12 +143,12 @@ class WireSlice:
     def solve_targets_summary_wire(self, engine, targets, bins: int = 0, lo: int = 0, width: int = 1, shift: int = 0):
         return engine.solve_targets_summary_wire(self, targets, bins, lo, width, shift)
 
-    def solve_targets_topk_wire(self, engine, targets, K: int, shift: int = 0):
-        return engine.solve_targets_topk_wire(self, targets, K, shift)
+    def solve_targets_topk_wire(self, engine, targets, K: int, shift: int = 0, radius: int = 0):
+        return engine.solve_targets_topk_wire(self, targets, K, shift, radius)
 
     def solve_targets_hits_wire(self, engine, targets, min_score=None, thresholds=None, within=None, max_rows=None,
-                                shift: int = 0):
-        return engine.solve_targets_hits_wire(self, targets, min_score, thresholds, within, max_rows, shift)
+                                shift: int = 0, radius: int = 0):
+        return engine.solve_targets_hits_wire(self, targets, min_score, thresholds, within, max_rows, shift, radius)
 
     def decode_cpu(self, shift: int = 0):
         """``(codes, offsets)`` of the slice from the native host decode (ops.align.decode_wire_cpu)."""
