@@ -54,7 +54,7 @@ COMM_OBJS := $(OBJ)/comm/comm.o $(OBJ)/comm/mpi_device_comm.o
 RCCL_OBJS := $(OBJ)/comm/rccl_comm.o
 HEADERS   := $(shell find csrc/include -name '*.h' -o -name '*.hpp')
 
-.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san hits-san wire-san peaks-san summary-san targets-san targets-summary-san targets-rows-san targets-peaks-san
+.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san hits-san wire-san peaks-san summary-san targets-san targets-summary-san targets-rows-san targets-peaks-san targets-rank-san
 
 all: build
 build: lib final $(GPU_PLUGIN)
@@ -292,6 +292,14 @@ targets-peaks-san: $(BUILD)/targets_peaks_san
 	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/targets_peaks_san
 $(BUILD)/targets_peaks_san: csrc/tests/targets_peaks_san.cpp $(PSAN_OBJS) $(HEADERS)
 	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/targets_peaks_san.cpp $(PSAN_OBJS) -ldl
+
+# stand-alone ASan/UBSan check of the target ranking's host code: targets_rank_batch_cpu against a letter-by-letter
+# replay run on every target alone, catalog, starts and rank rows in heap blocks of exactly their sizes, the planner's
+# record_bytes (0 is the old plan; the cut's edges) and the order of the errors (own main, host code only)
+targets-rank-san: $(BUILD)/targets_rank_san
+	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/targets_rank_san
+$(BUILD)/targets_rank_san: csrc/tests/targets_rank_san.cpp $(PSAN_OBJS) $(HEADERS)
+	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/targets_rank_san.cpp $(PSAN_OBJS) -ldl
 
 # parser throughput (count vs fill, SIMD A/B): build/fill_bench [records]
 $(BUILD)/fill_bench: tools/fill_bench.cpp $(CPU_OBJS) $(HEADERS)

@@ -336,6 +336,35 @@ int moc_engine_solve_targets_device(void* e, const uint8_t* d_codes, const int64
 int moc_engine_solve_targets_wire(void* e, const moc_wire_batch* b, const int64_t* starts, int64_t T, moc_result* rows);
 /* device time (ms) of the last targets call's select launches (MOC_PROFILE_TIMING=1; else 0) */
 int moc_engine_targets_ms(void* e, double* ms);
+/* ---- target ranking (moc/cpu_engine.hpp targets_rank_batch_cpu) ----
+ * Seq1 is a catalog delimited by starts as above. rows: moc_rank_row [n * M], record-major, 1 <= M <= 64: record i's
+ * min(M, F_i) best targets among the F_i that fit it (record length <= target length), higher score first, then
+ * smaller target index, each (target, score, n, k) with (score, n, k) exactly moc_cpu_targets' row [i, target]; then
+ * (-1, INT32_MIN, 0, 0) rows. The n * T pair rows never exist as a whole. Errors, all reported before any work: the
+ * target set's ("targets:"), then M ("rank:"). The engine forms are as moc_engine_solve_targets* (d_rows: device
+ * moc_rank_row [n * M]); moc_engine_targets_ms gives the device time of the select and rank launches. */
+typedef struct moc_rank_row {
+  int32_t target, score, n, k;
+} moc_rank_row;
+int moc_cpu_targets_rank(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                         const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics, int threads,
+                         int M, moc_rank_row* rows);
+/* out3: the bytes of profile scratch a chunk of the engine's rank call needs per (record, target) pair, and the most
+ * targets a 4-lane and a 16-lane group of the rank kernel take (moc/kernel_bounds.hpp); no GPU needed */
+int moc_targets_rank_geometry(int32_t* out3);
+/* The chunks an engine's rank call cuts a batch into under `scratch_bytes` of profile scratch (moc/tile_plan.hpp
+ * plan::plan_profile with record_bytes = 12 T; T = 0: no per-record bytes, the cut of top-K and hits); no GPU needed.
+ * Their bounds 0 = b0 < b1 < ... = n go into bounds_out (room for n + 1 entries). Returns the number of chunks, -1 on
+ * error. */
+int64_t moc_targets_rank_chunks(int64_t L1, const int64_t* offsets, int64_t n, int64_t T, int64_t scratch_bytes,
+                                int semantics, int64_t* bounds_out);
+int moc_engine_solve_targets_rank(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
+                                  int64_t T, int M, moc_rank_row* rows);
+int moc_engine_solve_targets_rank_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                         const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
+                                         const int64_t* h_starts, int64_t T, int M, moc_rank_row* d_rows, void* stream);
+int moc_engine_solve_targets_rank_wire(void* e, const moc_wire_batch* b, const int64_t* starts, int64_t T, int M,
+                                       moc_rank_row* rows);
 /* ---- per-target profile summary (moc/cpu_engine.hpp targets_summary_batch_cpu) ----
  * Seq1 is a catalog delimited by starts as above. summary: int64 [n * T * 7], record-major: row (i * T + t) holds
  * (count, sum, sumsq, min, max, n, k) of record i's profile against target t alone, n relative to the target's start;

@@ -58,6 +58,17 @@ static_assert(sizeof(ProfileEntry) == 8, "ProfileEntry is one 8-byte device stor
 
 constexpr int kMaxTopK = 64;  // rows per record of a top-K search
 
+// One row of a target ranking (moc/cpu_engine.hpp targets_rank_batch_cpu): the target's index and the record's row
+// against it, n local to the target. Past a record's fitting targets: no_rank().
+struct RankRow {
+  int32_t target;
+  int32_t score;
+  int32_t n;
+  int32_t k;
+};
+static_assert(sizeof(RankRow) == 16, "RankRow is one 16-byte device store");
+inline RankRow no_rank() { return RankRow{-1, kNoCandidateScore, 0, 0}; }
+
 class Error : public std::runtime_error {
  public:
   explicit Error(const std::string& what) : std::runtime_error(what) {}

@@ -155,6 +155,18 @@ void check_targets(const int64_t* starts, int64_t T, int64_t L1);
 void targets_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
                        const int64_t* starts, int64_t T, Result* out, Semantics sem, int num_threads = 0);
 
+// ---- target ranking: each record's M best targets, without the n * T pair rows
+// Terms as above. F_i counts the targets that fit record i (1 <= L2 <= len_t). out[i * M + j], j < min(M, F_i), are
+// record i's best fitting targets in the order higher score, then smaller target index, as (t, score, n, k) with
+// (score, n, k) exactly targets_batch_cpu's row [i, t] (n local to the target); the rows past F_i are no_rank() =
+// (-1, INT32_MIN, 0, 0). 1 <= M <= kMaxTopK. So row 0 is the best target; the whole result is targets_batch_cpu's
+// rows of the record stably sorted by (-score, t) with the pairs that do not fit dropped (M >= T lists every fitting
+// target); T = 1 is solve_batch_cpu with a leading 0. One record's T pair rows exist at a time per thread.
+// Errors before any work: check_targets' ("targets: ..."), then check_targets_rank's ("rank: ...").
+void check_targets_rank(int64_t M);
+void targets_rank_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                            const int64_t* starts, int64_t T, int M, RankRow* out, Semantics sem, int num_threads = 0);
+
 // ---- per-target profile summary: the summary row and histogram of every (record, target) pair's target profile
 // Terms as above (catalog, starts, b = starts[t], len = len_t, P the catalog's profile of record i, L2 letters).
 // The pair (i, t) fits iff 1 <= L2 <= len. Its target profile holds the slice entries P[b + o], o in [0, len - L2),

@@ -417,6 +417,9 @@ struct TargetsArgs {
   int32_t T = 0;
   int32_t group = 64;        // lanes per pair: 4, 16 or 64
   Result* out = nullptr;     // device, [n_total * T]
+  // targets_select_kernel only: pair (r, t)'s row goes to out[(r - out_rec0) * T + t]. 0: `out` holds the batch's
+  // rows; view.rec0: `out` holds the chunk's rows alone (the target ranking's part of the profile scratch).
+  int64_t out_rec0 = 0;
 };
 // Queues the select kernel (more than one launch when the blocks would pass the grid limit) on `stream`; pv
 // supplies the LUT, Seq1 (padded), L1 and the semantics, bv the records' letters.
@@ -490,6 +493,22 @@ void launch_targets_topk_peaks(const TargetsArgs& ta, const uint8_t* peak, int K
 void launch_targets_hits_peaks(const TargetsHitsArgs& ha, const uint8_t* peak, const ProblemView& pv, const BatchView& bv,
                                hipStream_t stream);
 
+// ---- target ranking (targets_rank_kernels.hip; definitions: moc/cpu_engine.hpp targets_rank_batch_cpu)
+// One chunk (`view`: rec0, n_rec and n_total are read, the profile is not) after launch_targets has stored the
+// chunk's pair rows at pairs[(r - view.rec0) * T + t]. A group of `group` consecutive lanes (4, 16 or 64) owns one
+// record and stores its M rows at out[r * M ..) (batch-wide record index; every row is stored, no_rank() past the
+// record's fitting targets), 1 <= M <= kMaxTopK.
+struct TargetsRankArgs {
+  ChunkView view;
+  const Result* pairs = nullptr;  // device, [view.n_rec * T]
+  int32_t T = 0;
+  int32_t M = 1;
+  int32_t group = 64;             // lanes per record: 4, 16 or 64
+  RankRow* out = nullptr;         // device, [n_total * M]
+};
+// Queues the rank kernel (more than one launch when the blocks would pass the grid limit) on `stream`.
+void launch_targets_rank(const TargetsRankArgs& ra, hipStream_t stream);
+
 // Loads every kernel file's code object onto the current device now (HIP loads them lazily, at the first
 // launch from each file: milliseconds inside the first timed search of a job otherwise).
 void preload_align_kernels();
@@ -508,6 +527,7 @@ void preload_targets_kernels();
 void preload_targets_summary_kernels();
 void preload_targets_rows_kernels();
 void preload_targets_peaks_kernels();
+void preload_targets_rank_kernels();
 // Kernel files by code object, for a preload of only what a job will launch.
 enum PreloadSet : unsigned {
   kPreloadAlign = 1,
@@ -527,6 +547,7 @@ enum PreloadSet : unsigned {
   kPreloadTargetsSummary = 8192,  // targets_summary_kernels.hip: likewise
   kPreloadTargetsRows = 16384,    // targets_rows_kernels.hip: likewise
   kPreloadTargetsPeaks = 32768,   // targets_peaks_kernels.hip: likewise
+  kPreloadTargetsRank = 65536,    // targets_rank_kernels.hip: likewise
 };
 inline void preload_kernels(unsigned set) {
   if (set & kPreloadMfma) preload_mfma_kernels();
@@ -545,9 +566,10 @@ inline void preload_kernels(unsigned set) {
   if (set & kPreloadTargetsSummary) preload_targets_summary_kernels();
   if (set & kPreloadTargetsRows) preload_targets_rows_kernels();
   if (set & kPreloadTargetsPeaks) preload_targets_peaks_kernels();
+  if (set & kPreloadTargetsRank) preload_targets_rank_kernels();
 }
 // "all", "none", or a comma list of align, short, swipe (both letter forms), swipe8, swipe33, tile16, mfma,
-// profile, report, hits, wire, peaks, summary, targets, targets_summary, targets_rows, targets_peaks;
+// profile, report, hits, wire, peaks, summary, targets, targets_summary, targets_rows, targets_peaks, targets_rank;
 // returns -1 for a name it does not know
 int parse_preload_set(const char* s);
 

@@ -70,7 +70,8 @@ struct EngineStats {
                          // 4096 targets_topk (the per-target top-K kernel, next to 16),
                          // 8192 targets_hits (the per-target count / scan / compact kernels, next to 16),
                          // 16384 targets_peaks (the per-target peak pass and masked per-target kernels of a distinct
-                         // per-target call, next to 256 and 4096 or 8192)
+                         // per-target call, next to 256 and 4096 or 8192),
+                         // 32768 targets_rank (the rank kernel of a target ranking, next to 16 and 1024)
   int32_t forms = 0;     // bitmask of the arithmetic forms they ran (moc::bounds::FormBits)
   R2Params r2;           // parameters of the R2 results of the last solve (when fmt == R2)
 };
@@ -224,7 +225,8 @@ class HipEngine {
   // The check every targets call makes first: throws unless a problem is set and (h_starts, T) is a valid target set
   // over its Seq1; touches nothing.
   void check_targets_call(const int64_t* h_starts, int64_t T) const;
-  // Device time (ms) of the targets select launches of the last targets call; as topk_select_ms().
+  // Device time (ms) of the targets select launches of the last targets call (a target ranking: select and rank); as
+  // topk_select_ms().
   double targets_ms() { return topk_select_ms(); }
 
   // ---- per-target profile summary (definitions: moc/cpu_engine.hpp targets_summary_batch_cpu; kernels:
@@ -287,6 +289,28 @@ class HipEngine {
                           int32_t min_score, const int32_t* thresholds, int64_t* toffsets_out,
                           std::vector<Result>& rows_out, int64_t max_rows_hint = -1, int64_t radius = 0);
 
+  // ---- target ranking (definitions: moc/cpu_engine.hpp targets_rank_batch_cpu; kernels:
+  // csrc/src/hip/targets_kernels.hip, csrc/src/hip/targets_rank_kernels.hip): the engine's Seq1 is a catalog as for
+  // solve_targets, and every record gets its M best fitting targets as rows (t, score, n, k) — rows [n * M],
+  // record-major, padded with no_rank() — without the n * T pair rows ever existing as a whole. Limits as
+  // solve_targets. Before anything is launched or any state changes the target set is checked ("targets:" errors),
+  // then M (1 .. kMaxTopK; "rank:" errors).
+  // Device form: queued on `stream` (0 = engine compute stream) with no sync. Per chunk the profile kernel over the
+  // catalog, then the targets select kernel — its pair rows go into the chunk's part of the profile scratch, laid out
+  // entries | pair rows [records * T] — then the rank kernel over the chunk's records. A chunk takes records while
+  // 8 * entries + 12 * T * records stay within profile_scratch_bytes (plan::plan_profile's record_bytes; at least one
+  // record). The select kernel's lane group is chosen as solve_targets chooses it, the rank kernel's from T
+  // (bounds::targets_rank_group; MOC_TARGETS_RANK_GROUP=4|16|64 at engine start forces one). d_starts / h_starts as
+  // solve_targets_device. d_out: device RankRow [n * M], every row stored. An empty batch launches nothing.
+  // targets_ms() covers the select and rank launches.
+  void solve_targets_rank_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
+                                 const int64_t* d_starts, const int64_t* h_starts, int64_t T, int M, RankRow* d_out,
+                                 hipStream_t stream);
+  // Host form (uploads through the pooled buffers; synchronous; fills stats()): the result slot and the copy back
+  // are n * M * 16 bytes.
+  void solve_targets_rank(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T,
+                          int M, RankRow* out);
+
   // ---- alignment report (definitions: moc/cpu_engine.hpp report_batch_cpu; kernels:
   // csrc/src/hip/report_kernels.hip): the sign counts and, optionally, the marker bytes of caller-supplied rows.
   // Byte letters and dense int64 offsets (wire batches: report_wire); no Semantics (row validity does not depend on
@@ -341,6 +365,7 @@ class HipEngine {
   void solve_targets_hits_wire(const WireBatch& b, const int64_t* starts, int64_t T, int32_t min_score,
                                const int32_t* thresholds, int64_t* toffsets_out, std::vector<Result>& rows_out,
                                int64_t max_rows_hint = -1, int64_t radius = 0);
+  void solve_targets_rank_wire(const WireBatch& b, const int64_t* starts, int64_t T, int M, RankRow* out);
   // poffsets[0..n] of a host wire batch (profile_offsets of its decoded lengths; no GPU work)
   void wire_profile_offsets(const WireBatch& b, int64_t* poffsets) const;
 
@@ -429,6 +454,7 @@ class HipEngine {
   void targets_topk_placed(Placed& p, const int64_t* starts, int64_t T, int K, Result* out, int64_t radius);
   void targets_hits_placed(Placed& p, const int64_t* starts, int64_t T, int32_t min_score, const int32_t* thresholds,
                            int64_t* toffsets_out, std::vector<Result>& rows_out, int64_t max_rows_hint, int64_t radius);
+  void targets_rank_placed(Placed& p, const int64_t* starts, int64_t T, int M, RankRow* out);
   void report_placed(Placed& p, int K, const Result* rows, int32_t* counts, uint8_t* marks);
   void ensure_device_events();  // ev_d0_ / ev_d1_, made by the first call that records them
   dev::Plan device_plan(void* d_plan, size_t n_starts, bool has_long_recs, int64_t n_long, const plan::TilePlan& tp,
@@ -459,7 +485,7 @@ class HipEngine {
                   bool packed5);
   void solve_wire_impl(const WireBatch& b, void* out, ResultFormat fmt, bool async);
   // ---- the profile family: one run loop over plan::plan_profile's chunks; a ProfileCall names the form
-  enum class ProfileKind { Profile, TopK, Hits, Summary, Targets, TargetsSummary, TargetsTopK, TargetsHits };
+  enum class ProfileKind { Profile, TopK, Hits, Summary, Targets, TargetsSummary, TargetsTopK, TargetsHits, TargetsRank };
   struct HitsCall {
     int32_t min_score;
     const int32_t* d_thresholds;
@@ -477,15 +503,16 @@ class HipEngine {
     const int64_t* h_starts;
     int64_t T;
     Result* d_out;            // Targets: [n, T]; TargetsTopK: [n, T, K]
+    RankRow* d_rank = nullptr;  // TargetsRank: [n, M] (M in ProfileCall::K); d_out is not used
   };
   struct ProfileCall {
     ProfileKind kind = ProfileKind::Profile;
     void* d_dst = nullptr;  // Profile: ProfileEntry [poffsets[n]], written in one chunk; TopK: Result [n, K]
-    int K = 0;              // TopK, TargetsTopK
+    int K = 0;              // TopK, TargetsTopK; TargetsRank: M
     int64_t radius = 0;     // TopK, Hits: > 0 selects among the peaks of that radius only
     HitsCall hits{};        // Hits; TargetsHits: over pairs (d_hoffsets is toffsets, d_thresholds int32 [n * T])
     SummaryCall summary{};  // Summary, TargetsSummary
-    TargetsCall targets{};  // Targets, TargetsSummary, TargetsTopK, TargetsHits
+    TargetsCall targets{};  // Targets, TargetsSummary, TargetsTopK, TargetsHits, TargetsRank
   };
   void run_profile(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n,
                    const ProfileCall& call, hipStream_t stream);
@@ -537,6 +564,7 @@ class HipEngine {
   size_t d_prof_scratch_cap_ = 0;
   bool profile_timing_ = false;
   int targets_group_ = 0;  // MOC_TARGETS_GROUP: 4, 16 or 64 forces that lane-group size; 0: chosen per chunk
+  int targets_rank_group_ = 0;  // MOC_TARGETS_RANK_GROUP: 4, 16 or 64 forces that lane-group size of the rank kernel; 0: from T
   int targets_peaks_seg_ = 0;  // MOC_TARGETS_PEAKS_SEG: 4, 8, 16, 32 or 64 forces that segment width of the per-target peak pass
   std::vector<hipEvent_t> ev_select_;
   size_t ev_select_used_ = 0;

@@ -221,6 +221,22 @@ inline int targets_peaks_seg(int64_t max_count) {
 }
 static_assert(kPeaksWaveEntries == 64, "targets peaks: the widest segment is a wave");
 
+// ---- target ranking (targets_rank_kernels.hip; definitions: moc/cpu_engine.hpp targets_rank_batch_cpu): each record's
+// M best targets out of the chunk's pair rows, which the select kernel leaves in the profile scratch behind the
+// chunk's entries — kTargetsRankRecordBytes = 12 bytes per (record, target) pair, the planner's record_bytes = 12 T.
+// A group of G consecutive lanes (4, 16 or 64) owns one record and walks its T rows once per round, ceil(T / G) rows
+// per lane; the host picks G from T alone (a record's rows are T whatever its length): up to kTargetsRankGroup4MaxT
+// targets G = 4 (at most four rows per lane and round), up to kTargetsRankGroup16MaxT G = 16 (at most sixteen), else a
+// wave. The two cut-overs are a rule — "no lane walks more than G rows per round until the group is a wave" — not
+// measured crossings (profiles/targets_rank/README.md says what was measured). MOC_TARGETS_RANK_GROUP=4|16|64 at
+// engine start forces G. Tuning constants only, every G gives the same rows for any T.
+constexpr int64_t kTargetsRankRecordBytes = 12;
+constexpr int64_t kTargetsRankGroup4MaxT = 16;
+constexpr int64_t kTargetsRankGroup16MaxT = 256;
+inline int targets_rank_group(int64_t T) {
+  return T <= kTargetsRankGroup4MaxT ? 4 : T <= kTargetsRankGroup16MaxT ? 16 : 64;
+}
+
 // Form bits reported per solve (EngineStats::forms; Python: stats()["forms"]).
 enum FormBits : int32_t {
   kFormSwipeKBits = 1,    // swipe, int16 keys with k bits

@@ -147,10 +147,13 @@ struct ProfilePlan {
 // peaks facts are filled only then). target_starts: null, or T + 1 host entries; upload_targets: they go into the
 // plan buffer. radius > 0 with target_starts is a per-target distinct call: the chunks' t_* facts are filled in
 // place of the plain peaks facts; targets_seg: 0, or the forced segment width (4, 8, 16, 32 or 64).
+// record_bytes: scratch bytes a chunk needs per record beside its profile entries (the target ranking's pair rows, 12 T).
+// 0: a chunk takes records while their entries number at most max(1, scratch_bytes / entry_bytes); > 0: while
+// entry_bytes * entries + record_bytes * records <= scratch_bytes. Either way a chunk holds at least one record.
 // Throws Error for n >= 2^31 - 1 and for Seq1 / Seq2 lengths of 2^30 and more; n >= 1.
 ProfilePlan plan_profile(const Config& c, Semantics sem, const int64_t* offsets, int64_t n, bool chunked,
                          int64_t entry_bytes, int64_t scratch_bytes, int64_t radius, const int64_t* target_starts = nullptr,
-                         int64_t T = 0, bool upload_targets = false, int targets_seg = 0);
+                         int64_t T = 0, bool upload_targets = false, int targets_seg = 0, int64_t record_bytes = 0);
 
 // ---- alignment report (report_kernels.hip): which records' rows take a lane each and which a wave each.
 // Records of at most bounds::kReportShortMaxL2 letters are short. A wave of the lane-per-row kernel takes up to

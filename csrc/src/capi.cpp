@@ -22,6 +22,7 @@
 #include "moc/tile_plan.hpp"
 
 static_assert(sizeof(moc_result) == sizeof(moc::Result), "ABI result layout");
+static_assert(sizeof(moc_rank_row) == sizeof(moc::RankRow), "ABI rank row layout");
 static_assert(sizeof(moc_profile_entry) == sizeof(moc::ProfileEntry), "ABI profile entry layout");
 
 namespace {
@@ -893,6 +894,79 @@ int moc_engine_solve_targets_wire(void* e, const moc_wire_batch* w, const int64_
 
 int moc_engine_targets_ms(void* e, double* ms) {
   return guard([&] { *ms = static_cast<moc::HipEngine*>(e)->targets_ms(); });
+}
+
+// ---- target ranking
+int moc_targets_rank_geometry(int32_t* out3) {
+  out3[0] = static_cast<int32_t>(moc::bounds::kTargetsRankRecordBytes);
+  out3[1] = static_cast<int32_t>(moc::bounds::kTargetsRankGroup4MaxT);
+  out3[2] = static_cast<int32_t>(moc::bounds::kTargetsRankGroup16MaxT);
+  return 0;
+}
+
+int moc_cpu_targets_rank(const int32_t* weights4, const uint8_t* seq1, int64_t L1, const uint8_t* codes,
+                         const int64_t* offsets, int64_t n, const int64_t* starts, int64_t T, int semantics, int threads,
+                         int M, moc_rank_row* rows) {
+  return guard([&] {
+    moc::check_targets(starts, T, L1);
+    moc::check_targets_rank(M);
+    moc::Weights w = weights_of(weights4);
+    moc::RecordBatch b = view_batch(codes, offsets, n);
+    moc::validate_score_range(w, std::max<int64_t>(b.max_length(), 1));
+    moc::ScoreTable t = moc::ScoreTable::build(w);
+    moc::targets_rank_batch_cpu(t, seq1, L1, b, starts, T, M, reinterpret_cast<moc::RankRow*>(rows),
+                                static_cast<moc::Semantics>(semantics), threads);
+  });
+}
+
+int64_t moc_targets_rank_chunks(int64_t L1, const int64_t* offsets, int64_t n, int64_t T, int64_t scratch_bytes,
+                                int semantics, int64_t* bounds_out) {
+  int64_t chunks = -1;
+  guard([&] {
+    if (n < 0 || L1 < 1) throw moc::Error("rank chunks: negative size");
+    if (T < 0 || T > moc::bounds::kTargetsMax)
+      throw moc::Error("rank chunks: T must be in 0.." + std::to_string(moc::bounds::kTargetsMax));
+    if (scratch_bytes < static_cast<int64_t>(sizeof(moc::ProfileEntry)))
+      throw moc::Error("profile scratch: at least one entry (8 bytes)");
+    for (int64_t i = 0; i < n; ++i)
+      if (offsets[i + 1] < offsets[i]) throw moc::Error("rank chunks: offsets must not decrease");
+    bounds_out[0] = 0;
+    chunks = 0;
+    if (n == 0) return;
+    moc::plan::Config c;  // the cut reads L1 alone; the runs' geometry (CUs, tuning) does not move it
+    c.L1 = L1;
+    const moc::plan::ProfilePlan pp =
+        moc::plan::plan_profile(c, static_cast<moc::Semantics>(semantics), offsets, n, true, sizeof(moc::ProfileEntry),
+                                scratch_bytes, 0, nullptr, 0, false, 0, moc::bounds::kTargetsRankRecordBytes * T);
+    for (const moc::plan::ProfileChunk& k : pp.chunks) bounds_out[++chunks] = k.r1;
+  });
+  return chunks;
+}
+
+int moc_engine_solve_targets_rank(void* e, const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
+                                  int64_t T, int M, moc_rank_row* rows) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_targets_rank(codes, offsets, n, starts, T, M,
+                                                        reinterpret_cast<moc::RankRow*>(rows));
+  });
+}
+
+int moc_engine_solve_targets_rank_device(void* e, const uint8_t* d_codes, const int64_t* d_offsets,
+                                         const int64_t* h_offsets, int64_t n, const int64_t* d_starts,
+                                         const int64_t* h_starts, int64_t T, int M, moc_rank_row* d_rows, void* stream) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_targets_rank_device(d_codes, d_offsets, h_offsets, n, d_starts, h_starts, T, M,
+                                                               reinterpret_cast<moc::RankRow*>(d_rows),
+                                                               static_cast<hipStream_t>(stream));
+  });
+}
+
+int moc_engine_solve_targets_rank_wire(void* e, const moc_wire_batch* w, const int64_t* starts, int64_t T, int M,
+                                       moc_rank_row* rows) {
+  return guard([&] {
+    static_cast<moc::HipEngine*>(e)->solve_targets_rank_wire(wire_batch(w), starts, T, M,
+                                                             reinterpret_cast<moc::RankRow*>(rows));
+  });
 }
 
 // ---- per-target profile summary

@@ -390,38 +390,77 @@ void check_targets(const int64_t* starts, int64_t T, int64_t L1) {
     throw Error("targets: starts[T] must be the catalog's length " + std::to_string(L1) + ", got " + std::to_string(starts[T]));
 }
 
+namespace {
+// rows[q] = record (s2, L2)'s row against target q alone, from the record's catalog profile `prof`: the definition
+// both targets_batch_cpu and targets_rank_batch_cpu state their rows by
+inline void target_rows(const ScoreTable& t, const uint8_t* s1, int64_t L1, const uint8_t* s2, int64_t L2,
+                        const ProfileEntry* prof, const int64_t* starts, int64_t T, Semantics sem, Result* rows) {
+  for (int64_t q = 0; q < T; ++q) {
+    const int64_t b = starts[q], len = starts[q + 1] - b;
+    if (L2 < 1 || L2 > len || L2 > L1) {
+      rows[q] = no_candidate();
+      continue;
+    }
+    Result best = no_candidate();
+    bool have = false;
+    const int64_t slice = len - L2;  // b + slice <= L1 - L2 <= C
+    for (int64_t o = 0; o < slice; ++o) {
+      const ProfileEntry& e = prof[b + o];
+      if (!have || e.score > best.score) {  // strict: the smallest offset keeps a tie
+        best = Result{e.score, static_cast<int32_t>(o), e.k};
+        have = true;
+      }
+    }
+    if (sem == Semantics::Spec || slice == 0) {  // the boundary diagonal, from the letters
+      const uint8_t* a = s1 + b + slice;
+      int32_t s = 0;
+      for (int64_t l = 0; l < L2; ++l) s += t.lut[s2[l] * kLutStride + a[l]];
+      if (!have || s > best.score) best = Result{s, static_cast<int32_t>(slice), 0};
+    }
+    rows[q] = best;
+  }
+}
+}  // namespace
+
 void targets_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
                        const int64_t* starts, int64_t T, Result* out, Semantics sem, int num_threads) {
   check_targets(starts, T, L1);
-  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t C) {
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t) {
+    target_rows(t, s1, L1, batch.record(i), batch.length(i), prof, starts, T, sem, out + i * T);
+  });
+}
+
+void check_targets_rank(int64_t M) {
+  if (M < 1 || M > kMaxTopK) throw Error("rank: M must be in 1.." + std::to_string(kMaxTopK) + ", got " + std::to_string(M));
+}
+
+void targets_rank_batch_cpu(const ScoreTable& t, const uint8_t* s1, int64_t L1, const RecordBatch& batch,
+                            const int64_t* starts, int64_t T, int M, RankRow* out, Semantics sem, int num_threads) {
+  check_targets(starts, T, L1);
+  check_targets_rank(M);
+  for_each_profile(t, s1, L1, batch, sem, num_threads, [&](int64_t i, const ProfileEntry* prof, int64_t) {
+    thread_local std::vector<Result> rows;   // the record's T pair rows: one record's at a time per thread
+    thread_local std::vector<int32_t> order;  // its fitting targets, best first
     const int64_t L2 = batch.length(i);
-    const uint8_t* s2 = batch.record(i);
-    Result* rows = out + i * T;
-    for (int64_t q = 0; q < T; ++q) {
-      const int64_t b = starts[q], len = starts[q + 1] - b;
-      if (L2 < 1 || L2 > len || L2 > L1) {
-        rows[q] = no_candidate();
-        continue;
+    rows.resize(static_cast<size_t>(T));
+    target_rows(t, s1, L1, batch.record(i), L2, prof, starts, T, sem, rows.data());
+    order.clear();
+    for (int64_t q = 0; q < T; ++q)
+      if (L2 >= 1 && L2 <= starts[q + 1] - starts[q]) order.push_back(static_cast<int32_t>(q));
+    const size_t keep = std::min(order.size(), static_cast<size_t>(M));
+    // higher score, then smaller target index: a total order, so the partial sort is the stable sort's prefix
+    std::partial_sort(order.begin(), order.begin() + static_cast<std::ptrdiff_t>(keep), order.end(), [&](int32_t a, int32_t b) {
+      return rows[a].score != rows[b].score ? rows[a].score > rows[b].score : a < b;
+    });
+    RankRow* dst = out + i * M;
+    for (size_t j = 0; j < static_cast<size_t>(M); ++j) {
+      if (j < keep) {
+        const Result& r = rows[order[j]];
+        dst[j] = RankRow{order[j], r.score, r.n, r.k};
+      } else {
+        dst[j] = no_rank();
       }
-      Result best = no_candidate();
-      bool have = false;
-      const int64_t slice = len - L2;  // b + slice <= L1 - L2 <= C
-      for (int64_t o = 0; o < slice; ++o) {
-        const ProfileEntry& e = prof[b + o];
-        if (!have || e.score > best.score) {  // strict: the smallest offset keeps a tie
-          best = Result{e.score, static_cast<int32_t>(o), e.k};
-          have = true;
-        }
-      }
-      if (sem == Semantics::Spec || slice == 0) {  // the boundary diagonal, from the letters
-        const uint8_t* a = s1 + b + slice;
-        int32_t s = 0;
-        for (int64_t l = 0; l < L2; ++l) s += t.lut[s2[l] * kLutStride + a[l]];
-        if (!have || s > best.score) best = Result{s, static_cast<int32_t>(slice), 0};
-      }
-      rows[q] = best;
     }
-    (void)C;
   });
 }
 

@@ -12,7 +12,9 @@
 //                             spec semantics or with len_t == L2 — over the record's L2 letters, summing
 //                             LUT[s2[l]][Seq1[starts[t] + len_t - L2 + l]]; xor-shuffle reductions; the group's first
 //                             lane re-reads the winning entry's k, merges the boundary entry (it has the largest
-//                             offset: it wins only with a strictly higher score) and stores the row. Every lane of a
+//                             offset: it wins only with a strictly higher score) and stores the row at
+//                             out[(r - out_rec0) * T + t] — the batch's rows, or (the target ranking) the chunk's
+//                             alone in the profile scratch behind the chunk's entries. Every lane of a
 //                             wave reaches every shuffle: groups without a pair or with an empty slice carry key 0.
 #include <hip/hip_runtime.h>
 
@@ -105,7 +107,9 @@ __global__ __launch_bounds__(256) void targets_select_kernel(TargetsArgs ta, Pro
       row = Result{e.score, o, e.k};
     }
     if (boundary && (key == 0ull || bsum > row.score)) row = Result{bsum, slice, 0};
-    ta.out[r * ta.T + t] = row;
+    const int64_t at = (r - ta.out_rec0) * ta.T + t;  // 64-bit; out_rec0 is 0 or the chunk's first record
+    MOC_DCHECK(at >= 0 && at < (ta.out_rec0 ? ta.view.n_rec : ta.view.n_total) * ta.T);
+    ta.out[at] = row;
   }
 }
 

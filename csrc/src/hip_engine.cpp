@@ -113,7 +113,8 @@ int parse_preload_set(const char* s) {
                {"profile", kPreloadProfile}, {"report", kPreloadReport}, {"hits", kPreloadHits},
                {"wire", kPreloadWire}, {"peaks", kPreloadPeaks}, {"summary", kPreloadSummary},
                {"targets", kPreloadTargets}, {"targets_summary", kPreloadTargetsSummary},
-               {"targets_rows", kPreloadTargetsRows}, {"targets_peaks", kPreloadTargetsPeaks}};
+               {"targets_rows", kPreloadTargetsRows}, {"targets_peaks", kPreloadTargetsPeaks},
+               {"targets_rank", kPreloadTargetsRank}};
   unsigned set = 0;
   std::string list(s);
   size_t at = 0;
@@ -168,6 +169,10 @@ HipEngine::HipEngine(const EngineOptions& opt) : opt_(opt) {
   if (const char* tg = std::getenv("MOC_TARGETS_GROUP")) {  // forces one lane-group size of the targets kernel
     const int g = std::atoi(tg);
     if (g == 4 || g == 16 || g == 64) targets_group_ = g;
+  }
+  if (const char* rg = std::getenv("MOC_TARGETS_RANK_GROUP")) {  // forces one lane-group size of the rank kernel
+    const int g = std::atoi(rg);
+    if (g == 4 || g == 16 || g == 64) targets_rank_group_ = g;
   }
   if (const char* ts = std::getenv("MOC_TARGETS_PEAKS_SEG")) {  // forces one segment width of the per-target peak pass
     const int g = std::atoi(ts);
@@ -1019,6 +1024,9 @@ namespace {
 size_t rows_bytes(int64_t n, int64_t per_record) {
   return n > 0 ? sizeof(Result) * static_cast<size_t>(n) * static_cast<size_t>(per_record) : 0;
 }
+size_t rank_bytes(int64_t n, int64_t M) {
+  return n > 0 ? sizeof(RankRow) * static_cast<size_t>(n) * static_cast<size_t>(M) : 0;
+}
 size_t summary_bytes(int64_t rows) { return rows > 0 ? sizeof(int64_t) * kSummaryCols * static_cast<size_t>(rows) : 0; }
 size_t hist_bytes(int64_t rows, int32_t bins) {
   return rows > 0 ? sizeof(int32_t) * static_cast<size_t>(bins) * static_cast<size_t>(rows) : 0;
@@ -1066,6 +1074,7 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
       {"moc.solve_hits_device", 16 | 64},      {"moc.solve_summary_device", 16 | 512},
       {"moc.solve_targets_device", 16 | 1024}, {"moc.solve_targets_summary_device", 16 | 2048},
       {"moc.solve_targets_topk_device", 16 | 4096}, {"moc.solve_targets_hits_device", 16 | 8192},
+      {"moc.solve_targets_rank_device", 16 | 1024 | 32768},
   };
   const ProfileKind kind = call.kind;
   const KindFacts& facts = kFacts[static_cast<int>(kind)];
@@ -1081,20 +1090,29 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
   const bool peaks = chunked && call.radius > 0;  // the distinct forms: a byte of peak marks beside every scratch entry
   const bool target_peaks = peaks && (kind == ProfileKind::TargetsTopK || kind == ProfileKind::TargetsHits);
   const bool targets = kind == ProfileKind::Targets || kind == ProfileKind::TargetsSummary ||
-                       kind == ProfileKind::TargetsTopK || kind == ProfileKind::TargetsHits;
+                       kind == ProfileKind::TargetsTopK || kind == ProfileKind::TargetsHits || kind == ProfileKind::TargetsRank;
+  // a target ranking keeps the chunk's pair rows behind its entries: 12 T bytes per record
+  const int64_t record_bytes = kind == ProfileKind::TargetsRank ? bounds::kTargetsRankRecordBytes * call.targets.T : 0;
   const int64_t entry_bytes = static_cast<int64_t>(sizeof(ProfileEntry)) + (peaks ? 1 : 0);
   const TargetsCall& tc = call.targets;
   // throws for a batch past the record or length limits, before the trace range opens and anything is queued
   const plan::ProfilePlan pp =
       plan::plan_profile(cfg_, sem_, h_offsets, n, chunked, entry_bytes, opt_.profile_scratch_bytes, peaks ? call.radius : 0,
-                         targets ? tc.h_starts : nullptr, targets ? tc.T : 0, targets && !tc.d_starts, targets_peaks_seg_);
+                         targets ? tc.h_starts : nullptr, targets ? tc.T : 0, targets && !tc.d_starts, targets_peaks_seg_,
+                         record_bytes);
   TraceRange tr(facts.trace);
   MOC_HIP_CHECK(hipEventSynchronize(ev_plan_));  // previous call's plan buffers are free again
   ensure(d_plan_, d_plan_cap_, pp.bytes);
   ensure_host(h_plan_, h_plan_cap_, pp.bytes);
-  // scratch: the largest chunk's profile entries | its peak marks (distinct forms)
+  // scratch: the largest chunk's profile entries | its peak marks (distinct forms); a target ranking: each chunk's
+  // entries | its pair rows
   const size_t scratch_entries = static_cast<size_t>(std::max<int64_t>(pp.max_entries, 1));
-  if (chunked) ensure(d_prof_scratch_, d_prof_scratch_cap_, static_cast<size_t>(entry_bytes) * scratch_entries);
+  size_t scratch_bytes = static_cast<size_t>(entry_bytes) * scratch_entries;
+  for (const plan::ProfileChunk& c : pp.chunks)  // entries | pair rows: the chunk that needs the most of both
+    if (record_bytes > 0)
+      scratch_bytes = std::max(scratch_bytes, sizeof(ProfileEntry) * static_cast<size_t>(c.entries) +
+                                                  static_cast<size_t>(record_bytes) * static_cast<size_t>(c.r1 - c.r0));
+  if (chunked) ensure(d_prof_scratch_, d_prof_scratch_cap_, scratch_bytes);
   uint8_t* d_peak = peaks ? static_cast<uint8_t*>(d_prof_scratch_) + sizeof(ProfileEntry) * scratch_entries : nullptr;
   if (kind == ProfileKind::Hits)
     ensure(d_hits_sums_, d_hits_sums_cap_,
@@ -1159,6 +1177,10 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
                      : kind == ProfileKind::TargetsTopK ? bounds::targets_topk_group(max_slice)
                                                         : bounds::targets_group(max_slice);
       tsa.ta.out = tc.d_out;
+      if (kind == ProfileKind::TargetsRank) {  // the chunk's pair rows, behind its entries (8-byte entries: aligned)
+        tsa.ta.out = reinterpret_cast<Result*>(static_cast<char*>(d_prof_scratch_) + sizeof(ProfileEntry) * static_cast<size_t>(c.entries));
+        tsa.ta.out_rec0 = c.r0;
+      }
     }
     if (target_peaks) {  // the segmented pass over every pair's own profile, never the plain one
       dev::TargetsPeaksArgs ka;
@@ -1207,6 +1229,18 @@ void HipEngine::run_profile(const uint8_t* d_codes, const int64_t* d_offsets, co
         break;
       }
       case ProfileKind::Targets: dev::launch_targets(tsa.ta, pv, bv, stream); break;
+      case ProfileKind::TargetsRank: {
+        dev::launch_targets(tsa.ta, pv, bv, stream);
+        dev::TargetsRankArgs ra;
+        ra.view = view;
+        ra.pairs = tsa.ta.out;
+        ra.T = tsa.ta.T;
+        ra.M = call.K;
+        ra.group = targets_rank_group_ ? targets_rank_group_ : bounds::targets_rank_group(tc.T);
+        ra.out = tc.d_rank;
+        dev::launch_targets_rank(ra, stream);
+        break;
+      }
       case ProfileKind::TargetsSummary:
         tsa.summary = call.summary.d_summary;
         tsa.hist = call.summary.d_hist;
@@ -1421,6 +1455,34 @@ void HipEngine::targets_placed(Placed& p, const int64_t* starts, int64_t T, Resu
   solve_targets_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, static_cast<Result*>(slots_[0]->d_out),
                        s_compute_);
   finish_placed(p, {{out, rows_bytes(p.n, T)}});
+  stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1);
+}
+
+// ---- target ranking -------------------------------------------------------------------------------------
+void HipEngine::solve_targets_rank_device(const uint8_t* d_codes, const int64_t* d_offsets, const int64_t* h_offsets,
+                                          int64_t n, const int64_t* d_starts, const int64_t* h_starts, int64_t T, int M,
+                                          RankRow* d_out, hipStream_t stream) {
+  check_targets_call(h_starts, T);  // before any launch or change of state
+  check_targets_rank(M);
+  if (n > 0 && !d_out) throw Error("rank: no rows buffer");
+  TargetsCall tc{d_starts, h_starts, T, nullptr};
+  tc.d_rank = d_out;
+  run_profile(d_codes, d_offsets, h_offsets, n, ProfileCall{ProfileKind::TargetsRank, nullptr, M, 0, {}, {}, tc}, stream);  // n <= 0: no launch
+}
+
+void HipEngine::solve_targets_rank(const uint8_t* codes, const int64_t* offsets, int64_t n, const int64_t* starts,
+                                   int64_t T, int M, RankRow* out) {
+  check_targets_call(starts, T);
+  check_targets_rank(M);
+  Placed p = place_host(codes, offsets, n, rank_bytes(n, M));
+  if (p.n > 0) targets_rank_placed(p, starts, T, M, out);
+}
+
+// d_out: rows (n * M RankRow); starts travel with the plan buffer
+void HipEngine::targets_rank_placed(Placed& p, const int64_t* starts, int64_t T, int M, RankRow* out) {
+  solve_targets_rank_device(p.d_codes, p.d_offsets, p.h_offsets, p.n, nullptr, starts, T, M,
+                            static_cast<RankRow*>(slots_[0]->d_out), s_compute_);
+  finish_placed(p, {{out, rank_bytes(p.n, M)}});
   stats_.h2d_bytes += static_cast<int64_t>(sizeof(int64_t)) * (T + 1);
 }
 
@@ -1837,6 +1899,16 @@ void HipEngine::solve_targets_wire(const WireBatch& b, const int64_t* starts, in
   finish_wire();
   Placed p = place_wire(b, rows_bytes(b.n, T));
   if (p.n > 0) targets_placed(p, starts, T, out);
+}
+
+void HipEngine::solve_targets_rank_wire(const WireBatch& b, const int64_t* starts, int64_t T, int M, RankRow* out) {
+  check_targets_call(starts, T);
+  check_targets_rank(M);
+  validate_wire(b);
+  require_host_batch(b);
+  finish_wire();
+  Placed p = place_wire(b, rank_bytes(b.n, M));
+  if (p.n > 0) targets_rank_placed(p, starts, T, M, out);
 }
 
 void HipEngine::solve_targets_summary_wire(const WireBatch& b, const int64_t* starts, int64_t T, int64_t* summary_out,

@@ -429,7 +429,7 @@ std::vector<dev::WaveStart> profile_runs(const Config& c, const int64_t* offsets
 
 ProfilePlan plan_profile(const Config& c, Semantics sem, const int64_t* offsets, int64_t n, bool chunked,
                          int64_t entry_bytes, int64_t scratch_bytes, int64_t radius, const int64_t* target_starts, int64_t T,
-                         bool upload_targets, int targets_seg) {
+                         bool upload_targets, int targets_seg, int64_t record_bytes) {
   if (n >= (int64_t{1} << 31) - 1) throw Error("profile / top-K: more than 2^31 - 2 records in one call");
   int64_t min_target = INT64_MAX;  // the shortest and (pp.max_target) the longest target
   for (int64_t t = 0; target_starts && t < T; ++t) min_target = std::min(min_target, target_starts[t + 1] - target_starts[t]);
@@ -454,12 +454,20 @@ ProfilePlan plan_profile(const Config& c, Semantics sem, const int64_t* offsets,
   pp.u = profile_u(c, sum_l2, n, max_need);
   const std::vector<int64_t>& poff = pp.poff;
   const int64_t cap_entries = std::max<int64_t>(1, scratch_bytes / entry_bytes);
+  // records [r0, r1] fit one chunk: their entries alone (record_bytes == 0, the rule of every call without per-record
+  // scratch), or their entries and record_bytes for each of them within scratch_bytes; in int64 for every batch the
+  // checks above let through (entries < 2^61 / n, record_bytes a few KiB times n < 2^31)
+  const auto fits = [&](int64_t r0, int64_t r1) {
+    const int64_t entries = poff[r1 + 1] - poff[r0];
+    if (record_bytes <= 0) return entries <= cap_entries;
+    return entry_bytes * entries + record_bytes * (r1 + 1 - r0) <= scratch_bytes;
+  };
   for (int64_t r0 = 0; r0 < n;) {
     int64_t r1 = r0 + 1;
     if (!chunked)
       r1 = n;
     else
-      while (r1 < n && poff[r1 + 1] - poff[r0] <= cap_entries) ++r1;
+      while (r1 < n && fits(r0, r1)) ++r1;
     ProfileChunk k;
     k.r0 = r0;
     k.r1 = r1;

@@ -194,6 +194,15 @@ def _decl(lib):
         "moc_engine_solve_targets_hits_wire_distinct": (c_int, [c_void_p, P(WireBatch), c_void_p, c_int64, c_int32,
                                                                 c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                                                 c_int64]),
+        "moc_cpu_targets_rank": (c_int, [P(c_int32), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                         c_int, c_int, c_int, c_void_p]),
+        "moc_targets_rank_geometry": (c_int, [c_void_p]),
+        "moc_targets_rank_chunks": (c_int64, [c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p]),
+        "moc_engine_solve_targets_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                                  c_void_p]),
+        "moc_engine_solve_targets_rank_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                                         c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+        "moc_engine_solve_targets_rank_wire": (c_int, [c_void_p, P(WireBatch), c_void_p, c_int64, c_int, c_void_p]),
         "moc_partition": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_double, c_void_p]),
         "moc_device_count": (c_int, []),
         "moc_host_register": (c_int, [c_void_p, c_size_t]),

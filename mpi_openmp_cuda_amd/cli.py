@@ -17,7 +17,7 @@ from .models.scoring import Semantics
 from .parallel import dist as D
 from .parallel.search import DistributedSearch
 from .utils.io import (format_hits, format_report, format_summary, format_targets, format_targets_hits,
-                       format_targets_summary, format_targets_topk, format_topk,
+                       format_targets_rank, format_targets_summary, format_targets_topk, format_topk,
                        write_results)
 
 
@@ -100,6 +100,12 @@ def main(argv=None) -> int:
                          "same target within R of it (0..2048) scores higher, or the same at a smaller n; the windows "
                          "end at the target's own first and last placement. Same line formats, fewer lines; R = 0 "
                          "prints what no flag prints")
+    ap.add_argument("--target-best", type=int, default=None, metavar="M",
+                    help="with --targets: only each record's M (1..64) best targets; under the record's line print "
+                         "'  best j: target t: score: S, n: N, k: K' for j = 1 .. min(M, targets the record fits), "
+                         "the higher score first, then the smaller t, or '  best: none' when no target fits — and none "
+                         "of the per-target lines. Not with --target-top, --target-min-score, --target-within, "
+                         "--target-summary, --target-hist or --target-distinct")
     a = ap.parse_args(argv)
     if not 1 <= a.top <= 64:
         ap.error("--top K: K must be in 1..64")
@@ -163,6 +169,14 @@ def main(argv=None) -> int:
             ap.error("--target-distinct R filters the lines of --targets FILE with --target-top K (K > 1) or "
                      "--target-min-score / --target-within: give one of them")
     target_radius = a.target_distinct or 0
+    if a.target_best is not None:
+        if a.targets is None:
+            ap.error("--target-best needs --targets FILE")
+        if target_rows_flags or a.target_summary or a.target_hist is not None or a.target_distinct is not None:
+            ap.error("--target-best does not combine with --target-top, --target-min-score, --target-within, "
+                     "--target-summary, --target-hist or --target-distinct")
+        if not 1 <= a.target_best <= 64:
+            ap.error("--target-best M: M must be in 1..64")
     if a.targets is not None:
         if a.top > 1 or a.show_alignment or want_hits or a.distinct is not None or a.summary or a.hist is not None:
             ap.error("--targets does not combine with --top K > 1, --show-alignment, --min-score, --within, "
@@ -177,6 +191,7 @@ def main(argv=None) -> int:
     ctx = D.init(a.dist_backend, use_gpu=use_gpu and a.dist_backend != "gloo")
     rc = 0
     problem = None
+    own_problem = None  # --target-best: the input as it came, for the records' own lines
     target_set = None
     err = ""
     if ctx.is_root:
@@ -192,6 +207,7 @@ def main(argv=None) -> int:
                 if a.strict_limits and any(len(ln) > 3000 for ln in lines):
                     raise ValueError("--targets: a target sequence is longer than 3000 letters")
                 target_set = TargetSet.from_sequences([problem.seq1] + [TargetSet.from_strings([ln]).seq1 for ln in lines])
+                own_problem = problem
                 problem = Problem(problem.weights, target_set.seq1, problem.codes, problem.offsets)
         except Exception as e:  # report, then make every rank exit consistently
             err = str(e)
@@ -241,9 +257,12 @@ def main(argv=None) -> int:
     target_summary = None
     target_topk = None
     target_hits = None
+    target_rank = None
     if a.targets is not None:
         try:
-            if a.target_top is not None:
+            if a.target_best is not None:
+                target_rank = search.run_targets_rank(problem, target_set, a.target_best, Semantics.parse(a.semantics))
+            elif a.target_top is not None:
                 target_topk = search.run_targets_topk(problem, target_set, a.target_top, Semantics.parse(a.semantics),
                                                       target_radius)
             elif a.target_min_score is not None or a.target_within is not None:
@@ -259,7 +278,8 @@ def main(argv=None) -> int:
                 print(f"input error: {e}", file=sys.stderr)
             D.finalize(ctx)
             return 1
-        results = None
+        # the records' own lines are the search against the input's Seq1 alone (target 1), which a ranking may not list
+        results = search.run(own_problem, Semantics.parse(a.semantics)) if a.target_best is not None else None
     elif a.summary:
         try:
             summary = search.run_summary(problem, *hist_args, semantics=Semantics.parse(a.semantics))
@@ -295,6 +315,9 @@ def main(argv=None) -> int:
             sys.stdout.flush()
         elif a.target_summary:
             sys.stdout.write(format_targets_summary(*target_summary))
+            sys.stdout.flush()
+        elif target_rank is not None:
+            sys.stdout.write(format_targets_rank(results, target_rank))
             sys.stdout.flush()
         elif target_topk is not None:
             sys.stdout.write(format_targets_topk(target_topk[:, 0, 0], target_topk))

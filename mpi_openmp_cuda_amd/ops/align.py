@@ -556,6 +556,108 @@ def targets_catalog_rows(rows, targets):
     return out.contiguous()
 
 
+# ---- target ranking: each record's M best targets, without the n x T pair rows
+RANK_COLS = ("target", "score", "n", "k")
+
+
+def _check_rank_m(M) -> int:
+    M = int(M)
+    if not 1 <= M <= MAX_TOP_K:
+        raise ValueError(f"rank: M must be in 1..{MAX_TOP_K}, got {M}")
+    return M
+
+
+def _targets_rank_check(rc):
+    """A native rank call's status: target-set errors ("targets:") and an M out of range ("rank:") are ValueErrors,
+    anything else a NativeError."""
+    if rc != 0:
+        msg = _lib.lib().moc_last_error().decode(errors="replace")
+        if msg.startswith(("targets:", "rank:")):
+            raise ValueError(msg)
+        raise _lib.NativeError(msg)
+
+
+def targets_rank_geometry() -> tuple:
+    """(bytes of profile scratch a chunk of the engine's rank call needs per (record, target) pair, the most targets a
+    4-lane group of the rank kernel takes, the most a 16-lane group takes) — csrc/include/moc/kernel_bounds.hpp; no
+    GPU needed."""
+    g = np.zeros(3, np.int32)
+    _lib.check(_lib.lib().moc_targets_rank_geometry(_lib.ptr(g)))
+    return tuple(int(x) for x in g)
+
+
+def search_targets_rank_cpu(problem: Problem, targets, M: int, semantics=Semantics.REFERENCE,
+                            threads: int = 0) -> np.ndarray:
+    """Target ranking on the CPU engine. ``problem.seq1`` is the catalog and ``targets`` its :class:`TargetSet` (or
+    just the starts). Returns int32 [n, M, 4] with the columns :data:`RANK_COLS`: ``out[i, j]`` = (t, score, n, k) is
+    record i's j-th best target among the F_i that fit it (record length <= target length) — higher score first, then
+    smaller target index — with (score, n, k) exactly :func:`search_targets_cpu`'s row [i, t], n relative to the
+    target's start; the rows past F_i are (-1, INT32_MIN, 0, 0). So ``out[:, 0]`` is :func:`targets_best`, the whole
+    result is search_targets_cpu's rows stably sorted by (-score, t) with the pairs that do not fit dropped, and
+    T = 1 is :func:`search_cpu` with a leading 0. The n x T pair rows never exist as a whole. ValueError for an
+    invalid target set ("targets: ...", first), then for M outside 1..64 ("rank: ...")."""
+    starts = _starts_of(targets, problem.L1)
+    M = _check_rank_m(M)
+    T = starts.shape[0] - 1
+    out = np.zeros((problem.n, M, 4), np.int32)
+    _targets_rank_check(_lib.lib().moc_cpu_targets_rank(
+        _lib.weights_arg(problem.weights.as_list()), _lib.ptr(problem.seq1), problem.L1, _lib.ptr(problem.codes),
+        _lib.ptr(problem.offsets), problem.n, _lib.ptr(starts), T, int(Semantics.parse(semantics)), int(threads), M,
+        _lib.ptr(out)))
+    return out
+
+
+def targets_rank_catalog_rows(rank, targets):
+    """Rank rows [n, M, 4] (columns :data:`RANK_COLS`) as int32 [n, M, 3] rows (score, n, k) on the catalog: n +
+    starts[t]; padding rows (target -1) become (INT32_MIN, 0, 0). What the report calls take as it is
+    (``search_report_cpu`` / ``report`` / ``report_device`` work on the catalog). ``rank``: a numpy array, or a torch
+    tensor — then the result is a tensor on its device, computed there without a synchronisation (the starts go up
+    with a non-blocking copy)."""
+    starts = np.ascontiguousarray(targets.starts if isinstance(targets, TargetSet) else targets, dtype=np.int64)
+    T = starts.shape[0] - 1
+    if isinstance(rank, np.ndarray) or not hasattr(rank, "device"):
+        r = np.asarray(rank, dtype=np.int32)
+        if r.ndim != 3 or r.shape[2] != 4:
+            raise ValueError(f"targets_rank_catalog_rows needs [n, M, 4] rank rows, got {r.shape}")
+        t = r[:, :, 0].astype(np.int64)
+        if t.size and (t.min() < -1 or t.max() >= T):
+            raise ValueError(f"targets_rank_catalog_rows: a target index outside -1..{T - 1}")
+        pad = t < 0
+        out = np.ascontiguousarray(r[:, :, 1:])
+        out[:, :, 1] = (out[:, :, 1] + starts[np.where(pad, 0, t)]).astype(np.int32)
+        out[pad] = (_I32.min, 0, 0)
+        return out
+    import torch
+
+    assert rank.dtype == torch.int32 and rank.dim() == 3 and rank.shape[2] == 4
+    b = torch.from_numpy(starts[:-1].astype(np.int32)).to(rank.device, non_blocking=True)
+    t = rank[:, :, 0].to(torch.int64)
+    pad = t < 0
+    score, n, k = rank[:, :, 1], rank[:, :, 2] + b[t.clamp(0, T - 1)], rank[:, :, 3]
+    zero = torch.zeros_like(score)  # the padding row's values are filled on the device: no host tensor, no copy
+    return torch.stack([torch.where(pad, torch.full_like(score, _I32.min), score), torch.where(pad, zero, n),
+                        torch.where(pad, zero, k)], dim=2).contiguous()
+
+
+def targets_rank_chunks(L1: int, offsets, T: int, scratch_bytes: int, semantics=Semantics.REFERENCE) -> np.ndarray:
+    """The chunks :meth:`HipSearchEngine.solve_targets_rank` cuts a batch into after
+    ``set_profile_scratch(scratch_bytes)`` against a catalog of ``L1`` letters and ``T`` targets
+    (csrc/include/moc/tile_plan.hpp plan_profile), no GPU needed: int64 bounds ``0 = b0 < b1 < ... = n``. A chunk takes
+    records while ``8 * entries + 12 * T * records <= scratch_bytes`` — its profile entries and its pair rows — and at
+    least one record. ``T = 0`` has no per-record bytes: the cut of top-K and hits, records while their entries number
+    at most ``max(1, scratch_bytes // 8)``. ``offsets`` as :meth:`HipSearchEngine.solve` takes them."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = offsets.shape[0] - 1
+    if n < 0:
+        raise ValueError("offsets needs at least one entry")
+    bounds = np.zeros(n + 1, np.int64)
+    chunks = int(_lib.lib().moc_targets_rank_chunks(int(L1), _lib.ptr(offsets), n, int(T), int(scratch_bytes),
+                                                    int(Semantics.parse(semantics)), _lib.ptr(bounds)))
+    if chunks < 0:
+        raise _lib.NativeError(_lib.lib().moc_last_error().decode(errors="replace"))
+    return bounds[:chunks + 1].copy()
+
+
 # ---- per-target profile summary: one summary row and histogram per (record, target) pair
 def targets_summary_geometry() -> tuple:
     """(threads per workgroup of the GPU's per-target summary kernels, largest ``bins``, the most bins a 4-lane group
@@ -1392,6 +1494,67 @@ class HipSearchEngine:
         del keep
         return out
 
+    # ---- target ranking (byte letters, dense offsets; csrc/src/hip/targets_rank_kernels.hip)
+    def solve_targets_rank(self, codes: np.ndarray, offsets: np.ndarray, targets, M: int) -> np.ndarray:
+        """Host CSR -> int32 [n, M, 4] rank rows (columns :data:`RANK_COLS`) as :func:`search_targets_rank_cpu`
+        returns them, against the engine's Seq1 as the catalog of ``targets``. One pass: per chunk the catalog
+        profile, the targets select kernel — its pair rows stay in the profile scratch behind the chunk's entries —
+        and the rank kernel; a chunk takes records while 8 * entries + 12 * T * records fit
+        :meth:`set_profile_scratch` (:func:`targets_rank_chunks`). 16 M bytes come back per record, never the n x T
+        rows. Synchronous; ``stats()["kernels"]`` names ``profile``, ``targets`` and ``targets_rank``. ValueError for
+        an invalid target set (first), then for M outside 1..64, raised before anything is launched and without a
+        change to ``stats()``."""
+        starts = _starts_of(targets, self.problem_L1)
+        M = _check_rank_m(M)
+        T = starts.shape[0] - 1
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = offsets.shape[0] - 1
+        out = np.zeros((n, M, 4), np.int32)
+        _targets_rank_check(_lib.lib().moc_engine_solve_targets_rank(self._h, _lib.ptr(codes), _lib.ptr(offsets), n,
+                                                                     _lib.ptr(starts), T, M, _lib.ptr(out)))
+        return out
+
+    def solve_targets_rank_device(self, codes_t, offsets_t, h_offsets: np.ndarray, targets, M: int, out_t=None,
+                                  starts_t=None, stream=None):
+        """Device-resident batch (as :meth:`solve_device`) -> ``out_t``, an int32 [n, M, 4] tensor of rank rows on
+        the codes' device (allocated when None; every row is written). ``starts_t`` as :meth:`solve_targets_device`.
+        Queued on ``stream`` (default: the current stream); returns immediately — :func:`targets_rank_catalog_rows`
+        and :meth:`report_device` can follow on the same stream. ValueError as :meth:`solve_targets_rank`."""
+        import torch
+
+        starts = _starts_of(targets, self.problem_L1)
+        M = _check_rank_m(M)
+        T = starts.shape[0] - 1
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        n = h_offsets.shape[0] - 1
+        assert codes_t.dtype == torch.uint8 and offsets_t.dtype == torch.int64 and offsets_t.numel() == n + 1
+        if stream is None:
+            stream = torch.cuda.current_stream(codes_t.device)
+        if out_t is None:
+            out_t = torch.empty((n, M, 4), dtype=torch.int32, device=codes_t.device)
+        assert out_t.dtype == torch.int32 and out_t.is_contiguous() and tuple(out_t.shape) == (n, M, 4)
+        if starts_t is not None:
+            assert starts_t.dtype == torch.int64 and starts_t.is_contiguous() and starts_t.numel() == T + 1
+        _targets_rank_check(_lib.lib().moc_engine_solve_targets_rank_device(
+            self._h, ctypes.c_void_p(codes_t.data_ptr()), ctypes.c_void_p(offsets_t.data_ptr()), _lib.ptr(h_offsets),
+            n, ctypes.c_void_p(starts_t.data_ptr()) if starts_t is not None else None, _lib.ptr(starts), T, M,
+            ctypes.c_void_p(out_t.data_ptr()), ctypes.c_void_p(stream.cuda_stream)))
+        return out_t
+
+    def solve_targets_rank_wire(self, ws, targets, M: int, shift: int = 0) -> np.ndarray:
+        """Host wire batch -> int32 [n, M, 4] rank rows, as :meth:`solve_targets_rank` on the decoded records.
+        See :meth:`solve_profile_wire`."""
+        starts = _starts_of(targets, self.problem_L1)
+        M = _check_rank_m(M)
+        T = starts.shape[0] - 1
+        b, keep = wire_batch_of(ws, shift)
+        out = np.zeros((ws.n, M, 4), np.int32)
+        _targets_rank_check(_lib.lib().moc_engine_solve_targets_rank_wire(self._h, ctypes.byref(b), _lib.ptr(starts), T,
+                                                                          M, _lib.ptr(out)))
+        del keep
+        return out
+
     # ---- per-target top-K and threshold hits (byte letters, dense offsets; csrc/src/hip/targets_rows_kernels.hip)
     def solve_targets_topk(self, codes: np.ndarray, offsets: np.ndarray, targets, K: int, radius: int = 0) -> np.ndarray:
         """Host CSR -> int32 [n, T, K, 3] rows as :func:`search_targets_topk_cpu` returns them, against the engine's
@@ -1881,7 +2044,8 @@ class HipSearchEngine:
                                              (32, "report"), (64, "hits"), (128, "wire"), (256, "peaks"),
                                              (512, "summary"), (1024, "targets"),
                                              (2048, "targets_summary"), (4096, "targets_topk"),
-                                             (8192, "targets_hits"), (16384, "targets_peaks"))
+                                             (8192, "targets_hits"), (16384, "targets_peaks"),
+                                             (32768, "targets_rank"))
                         if int(d["kernels"]) & b]
         d["forms"] = [k for b, k in FORM_NAMES if int(v[13]) & b]
         return d
@@ -1992,6 +2156,12 @@ def align_targets_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets,
     """torch-facing op: the multi-target rows as an int32 [n, T, 3] tensor on the codes' device; see
     :meth:`HipSearchEngine.solve_targets_device`."""
     return engine.solve_targets_device(codes_t, offsets_t, h_offsets, targets, None, None, stream)
+
+
+def align_targets_rank_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, targets, M: int, stream=None):
+    """torch-facing op: each record's M best targets as an int32 [n, M, 4] tensor (columns :data:`RANK_COLS`) on the
+    codes' device; see :meth:`HipSearchEngine.solve_targets_rank_device`."""
+    return engine.solve_targets_rank_device(codes_t, offsets_t, h_offsets, targets, M, None, None, stream)
 
 
 def align_targets_summary_device(engine: HipSearchEngine, codes_t, offsets_t, h_offsets, targets, bins: int = 0,

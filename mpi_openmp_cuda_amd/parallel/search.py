@@ -32,7 +32,7 @@ from ..ops.align import (HipSearchEngine, decode_keys, device_count, keys_to_ord
                         search_summary_cpu, search_targets_cpu, search_targets_summary_cpu, search_topk_cpu,
                          summary_bound, within_thresholds,
                          TargetSet, check_targets, _summary_args, _check_k, _check_radius, search_targets_hits_cpu,
-                         search_targets_topk_cpu)
+                         search_targets_topk_cpu, search_targets_rank_cpu, _check_rank_m)
 from ..utils.timer import PhaseTimer
 from . import dist as D
 from .partition import CPU_COST, GPU_COST, partition
@@ -388,6 +388,40 @@ class DistributedSearch:
                     rows[b:e] = search_targets_topk_cpu(sub, starts, K, sem, self.threads, radius)
         with T.phase("gather"):
             rows = D.allreduce_max_int64(ctx, rows.reshape(-1)).reshape(n, nt, K, 3)
+            D.barrier(ctx)
+            win.close(unlink=ctx.is_root)
+        return rows.astype(np.int32) if ctx.is_root else None
+
+    def run_targets_rank(self, problem: Optional[Problem], targets=None, M: int = 1, semantics=Semantics.REFERENCE):
+        """Target ranking (ops.align.search_targets_rank_cpu's int32 [n, M, 4] rows; ``M`` the same on every rank,
+        ``targets`` as :meth:`run_targets`) for the ``records`` partition: every rank ranks the targets of its
+        cost-balanced slice of the node-shared input window, and one MAX all-reduce of an int64 array that is
+        INT64_MIN outside the rank's slice collects the n M rows (no new transport; the n T pair rows exist nowhere).
+        Returns the rows on the root, else None. One node; byte letters through the engines' rank calls."""
+        if self.partition != "records":
+            raise ValueError("the target ranking runs on record slices (--partition records, one node): the offsets "
+                             "partition combines one packed key per record and cannot carry M rows")
+        ctx, T = self.ctx, self.timer
+        sem = Semantics.parse(semantics)
+        starts = self._bcast_starts(problem, targets)  # the target set's errors come first
+        M = _check_rank_m(M)
+        with T.phase("bcast"):
+            prob, sem, n, total, bounds = self._setup(problem, sem)
+        b, e = int(bounds[ctx.rank]), int(bounds[ctx.rank + 1])
+        with T.phase("distribute"):
+            win = self._open_window(problem, n, total)
+        with T.phase("compute"):
+            rows = np.full((n, M, 4), np.iinfo(np.int64).min, np.int64)
+            if e > b:
+                offsets = np.asarray(win.offsets[b:e + 1])
+                if self.engine is not None:
+                    rows[b:e] = self.engine.solve_targets_rank(np.asarray(win.codes), offsets, starts, M)
+                else:
+                    sub = Problem(prob.weights, prob.seq1, np.asarray(win.codes[offsets[0]:offsets[-1]]),
+                                  offsets - offsets[0])
+                    rows[b:e] = search_targets_rank_cpu(sub, starts, M, sem, self.threads)
+        with T.phase("gather"):
+            rows = D.allreduce_max_int64(ctx, rows.reshape(-1)).reshape(n, M, 4)
             D.barrier(ctx)
             win.close(unlink=ctx.is_root)
         return rows.astype(np.int32) if ctx.is_root else None

@@ -140,6 +140,9 @@ class WireSlice:
     def solve_targets_wire(self, engine, targets, shift: int = 0):
         return engine.solve_targets_wire(self, targets, shift)
 
+    def solve_targets_rank_wire(self, engine, targets, M: int, shift: int = 0):
+        return engine.solve_targets_rank_wire(self, targets, M, shift)
+
     def solve_targets_summary_wire(self, engine, targets, bins: int = 0, lo: int = 0, width: int = 1, shift: int = 0):
         return engine.solve_targets_summary_wire(self, targets, bins, lo, width, shift)
 

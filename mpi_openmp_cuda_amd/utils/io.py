@@ -125,6 +125,28 @@ def format_targets(results, rows, first_index: int = 0) -> str:
     return "".join(out)
 
 
+def format_targets_rank(results, rank, first_index: int = 0) -> str:
+    """Results with their target ranking (int32 [n, M, 4] rows of ops.align.RANK_COLS from the rank calls): record i's
+    line as :func:`format_results` prints it, then "  best j: target t: score: S, n: N, k: K" for its j-th best
+    target, j = 1 .. min(M, fitting targets), targets numbered from 1 and n relative to that target's start — or
+    "  best: none" when no target fits the record. No per-target lines."""
+    from ..ops.align import as_triples
+
+    r = np.asarray(rank, dtype=np.int32)
+    res = as_triples(results)
+    if r.ndim != 3 or r.shape[2] != 4 or r.shape[1] < 1 or r.shape[0] != res.shape[0]:
+        raise ValueError("format_targets_rank needs [n, M, 4] rank rows for the results' n records")
+    out = []
+    for i, (score, n, k) in enumerate(res.tolist()):
+        out.append(f"#{i + first_index}: score: {score}, n: {n}, k: {k}\n")
+        listed = [row for row in r[i].tolist() if row[0] >= 0]
+        for j, (t, ts, tn, tk) in enumerate(listed, start=1):
+            out.append(f"  best {j}: target {t + 1}: score: {ts}, n: {tn}, k: {tk}\n")
+        if not listed:
+            out.append("  best: none\n")
+    return "".join(out)
+
+
 def _format_targets_under(results, rows, under, first_index: int) -> str:
     """:func:`format_targets` with the lines ``under(i, t)`` yields below each "  target t: ..." line."""
     from ..ops.align import as_triples, targets_best
