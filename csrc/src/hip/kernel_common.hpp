@@ -331,6 +331,18 @@ __device__ __forceinline__ void stage_bytes(uint8_t* dst, const uint8_t* src, in
   for (int t = threadIdx.x; t < n4; t += blockDim.x) d[t] = s[t];
 }
 
+// ---- histogram bin (summary_hist_kernel, targets_hist_kernel) ----------------------------------------
+// clamp(floor((score - lo) / width), 0, bins - 1). The difference is formed in 64 bits (it spans -2^32 .. 2^32 - 1);
+// a negative one clamps to bin 0 whatever its floor is, and a non-negative one is below 2^32, so its floor division
+// by width >= 1 is an unsigned 32-bit one with the same quotient as the int64 division of the definition.
+__device__ __forceinline__ int summary_bin_dev(int score, int lo, int width, int bins) {
+  const long long d = static_cast<long long>(score) - static_cast<long long>(lo);
+  if (d < 0) return 0;
+  MOC_DCHECK(d <= 0xffffffffll && width >= 1);
+  const uint32_t q = static_cast<uint32_t>(d) / static_cast<uint32_t>(width);
+  return q < static_cast<uint32_t>(bins) ? static_cast<int>(q) : bins - 1;
+}
+
 // ---- a chunk's profile (dev::ChunkView) --------------------------------------------------------------
 // Index in v.prof (and in a peak-mark array beside it) of entry 0 of record r, a batch-wide index of one of the
 // chunk's records. Debug builds check here that r is the chunk's and that all of its entries lie inside prof: an

@@ -38,17 +38,6 @@ __device__ __forceinline__ int wave_min_i32(int v) {
   for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
   return v;
 }
-
-// clamp(floor((score - lo) / width), 0, bins - 1). The difference is formed in 64 bits (it spans -2^32 .. 2^32 - 1);
-// a negative one clamps to bin 0 whatever its floor is, and a non-negative one is below 2^32, so its floor division
-// by width >= 1 is an unsigned 32-bit one with the same quotient as the int64 division of the definition.
-__device__ __forceinline__ int summary_bin_dev(int score, int lo, int width, int bins) {
-  const long long d = static_cast<long long>(score) - static_cast<long long>(lo);
-  if (d < 0) return 0;
-  MOC_DCHECK(d <= 0xffffffffll && width >= 1);
-  const uint32_t q = static_cast<uint32_t>(d) / static_cast<uint32_t>(width);
-  return q < static_cast<uint32_t>(bins) ? static_cast<int>(q) : bins - 1;
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void profile_summary_kernel(SummaryArgs sa) {

@@ -36,9 +36,10 @@
 //   targets_topk_peaks_kernel<G> / targets_hits_count_peaks_kernel<G> / targets_hits_compact_peaks_kernel<G>
 //                                 targets_topk_kernel, targets_hits_count_kernel and targets_hits_compact_kernel over
 //                                 the peaks: the same lane groups and ownership, a non-peak has key 0 or hit = false,
-//                                 the boundary entry is masked like any other. The unmasked kernels and their code
-//                                 object are untouched (this file carries its own copy of their pair helpers); the
-//                                 prefix sum is launch_hits_scan, the compaction's padded wave-uniform trip count stays.
+//                                 the boundary entry is masked like any other. They are kernels of their own beside
+//                                 the unmasked ones and share only the pair view, group reductions and launch
+//                                 splitter of targets_pair.hpp, from which every kernel here starts; the prefix sum is
+//                                 launch_hits_scan, the compaction's padded wave-uniform trip count stays.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,38 +47,21 @@
 #include "kernel_common.hpp"
 #include "moc/kernel_bounds.hpp"
 #include "moc/runtime/hip_check.hpp"
+#include "targets_pair.hpp"
 
 namespace moc {
 namespace dev {
 
 using namespace kc;
+using namespace tp;
 
 namespace {
 constexpr int kBlock = bounds::kTargetsThreads;
-constexpr int64_t kMaxBlocksPerLaunch = int64_t{1} << 30;  // below the 2^31 - 1 grid limit
 constexpr int kHeld = 4;  // slice keys a lane keeps in registers (targets_topk_kernel's held[])
 constexpr int kTile = bounds::kPeaksTile;
 constexpr int kKeysPerThread = bounds::kPeaksKeysPerThread;
 constexpr int kMaxKeys = kTile + 2 * bounds::kPeaksMaxRadius;
 static_assert(bounds::kPeaksThreads == kBlock, "targets peaks: the tile kernel's keys per thread are kPeaksThreads'");
-
-template <int G>
-__device__ __forceinline__ unsigned long long group_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) {
-    const int lo = __shfl_xor(static_cast<int>(v), d, 64);
-    const int hi = __shfl_xor(static_cast<int>(v >> 32), d, 64);
-    v = max_u64(v, (static_cast<unsigned long long>(static_cast<uint32_t>(hi)) << 32) | static_cast<uint32_t>(lo));
-  }
-  return v;
-}
-
-template <int G>
-__device__ __forceinline__ int group_sum_i32(int v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 // v of lane `src` of this lane's segment of S lanes, or 0 when src is no lane of the segment
 template <int S>
@@ -87,67 +71,6 @@ __device__ __forceinline__ unsigned long long shfl_seg_u64_or0(unsigned long lon
   const int hi = __shfl(static_cast<int>(v >> 32), s, 64);
   const unsigned long long r = (static_cast<unsigned long long>(static_cast<uint32_t>(hi)) << 32) | static_cast<uint32_t>(lo);
   return src >= 0 && src < S ? r : 0ull;
-}
-
-// What a group knows about its pair (targets_rows_kernels.hip's): every kernel here starts from it.
-struct Pair {
-  int64_t r = 0, pb = 0, b = 0;  // batch-wide record, its profile's first entry in `prof`, the target's start
-  int64_t p = 0;                 // batch-wide pair index r * T + t
-  int t = 0, L2 = 0;
-  int slice = 0;          // entries of the pair's slice; local offset of its boundary entry
-  bool active = false;    // the group has a pair (uniform over the group)
-  bool fits = false;
-  bool boundary = false;  // the boundary entry takes part
-  const uint8_t* rec = nullptr;
-};
-
-__device__ __forceinline__ Pair pair_of(const TargetsArgs& ta, const ProblemView& pv, const BatchView& bv, int64_t pair,
-                                        int64_t n_pairs) {
-  Pair p;
-  p.active = pair >= 0 && pair < n_pairs;
-  int len = 0;
-  if (p.active) {
-    const int64_t li = pair / ta.T;
-    p.t = static_cast<int>(pair - li * ta.T);
-    p.r = ta.view.rec0 + li;
-    p.p = p.r * ta.T + p.t;
-    MOC_DCHECK(li >= 0 && li < ta.view.n_rec && p.r >= 0 && p.r < bv.n && p.t >= 0 && p.t < ta.T);
-    p.rec = bv.codes + (bv.offsets[p.r] - bv.offsets[0]);
-    p.L2 = static_cast<int>(bv.offsets[p.r + 1] - bv.offsets[p.r]);
-    p.b = ta.starts[p.t];
-    len = static_cast<int>(ta.starts[p.t + 1] - p.b);
-    p.pb = chunk_first(ta.view, p.r);
-    MOC_DCHECK(p.b >= 0 && len >= 1 && p.b + len <= pv.L1);
-  }
-  p.fits = p.active && p.L2 >= 1 && p.L2 <= len && p.L2 <= pv.L1;
-  p.slice = p.fits ? len - p.L2 : 0;
-  p.boundary = p.fits && (pv.semantics == static_cast<int>(Semantics::Spec) || p.slice == 0);
-  return p;
-}
-
-// entries of the pair's profile (0: no pair, or it does not fit)
-__device__ __forceinline__ int pair_count(const Pair& p) { return p.slice + (p.boundary ? 1 : 0); }
-
-// this thread's share of the boundary entry's score, letters sub, sub + stride, ... (0 where the entry does not take part)
-__device__ __forceinline__ int boundary_part(const Pair& p, const ProblemView& pv, int sub, int stride) {
-  int bsum = 0;
-  if (p.boundary) {
-    const int64_t a0 = p.b + p.slice;  // the entry's first Seq1 letter; its last is b + len - 1 < L1
-    for (int l = sub; l < p.L2; l += stride) {
-      const int c = p.rec[l];
-      MOC_DCHECK(c >= 0 && c < kLutStride);
-      MOC_DCHECK(a0 + l >= 0 && a0 + l < pv.L1);
-      bsum += pv.lut[(c << 5) + pv.seq1[a0 + l]];
-    }
-  }
-  return bsum;
-}
-
-// entry o of the pair's slice
-__device__ __forceinline__ ProfileEntry slice_entry(const TargetsArgs& ta, const Pair& p, int o) {
-  MOC_DCHECK(o >= 0 && o < p.slice);
-  MOC_DCHECK(p.b + o < chunk_count(ta.view, p.r));  // the slice lies inside the record's entries
-  return ta.view.prof[p.pb + p.b + o];
 }
 
 // index of the mark of local entry o (o <= slice) of a pair of C >= 2 entries: inside the record's entries
@@ -160,12 +83,6 @@ __device__ __forceinline__ int64_t mark_at(const TargetsArgs& ta, const Pair& p,
 // whether local entry o of the pair is a peak: the stored mark, or true for the pair of one entry (never stored)
 __device__ __forceinline__ bool is_peak(const TargetsArgs& ta, const uint8_t* __restrict__ peak, const Pair& p, int C, int o) {
   return C <= 1 || peak[mark_at(ta, p, o)] != 0;
-}
-
-__device__ __forceinline__ int pair_threshold(const TargetsHitsArgs& ha, const Pair& p) {
-  if (!p.active || !ha.thresholds) return ha.min_score;
-  MOC_DCHECK(p.p >= 0 && p.p < ha.ta.view.n_total * ha.ta.T);
-  return ha.thresholds[p.p];
 }
 }  // namespace
 
@@ -436,17 +353,6 @@ void preload_targets_peaks_kernels() {
 }
 
 namespace {
-// fn(blocks, pair0) for every launch over n_pairs pairs with G lanes each, split below the grid limit
-template <int G, class Fn>
-void for_each_launch(int64_t n_pairs, Fn&& fn) {
-  constexpr int64_t kGroupsPerBlock = kBlock / G;
-  for (int64_t pair0 = 0; pair0 < n_pairs;) {
-    const int64_t blocks = std::min<int64_t>((n_pairs - pair0 + kGroupsPerBlock - 1) / kGroupsPerBlock, kMaxBlocksPerLaunch);
-    fn(static_cast<unsigned>(blocks), pair0);
-    pair0 += blocks * kGroupsPerBlock;
-  }
-}
-
 template <int S>
 void launch_seg_s(const TargetsPeaksArgs& a, const ProblemView& pv, const BatchView& bv, hipStream_t stream) {
   const int64_t n_pairs = a.ta.view.n_rec * a.ta.T;
@@ -511,21 +417,13 @@ void launch_targets_peaks(const TargetsPeaksArgs& a, const ProblemView& pv, cons
 void launch_targets_topk_peaks(const TargetsArgs& ta, const uint8_t* peak, int K, const ProblemView& pv,
                                const BatchView& bv, hipStream_t stream) {
   if (ta.view.n_rec <= 0 || ta.T <= 0) return;
-  switch (ta.group) {
-    case 4: launch_topk_g<4>(ta, peak, K, pv, bv, stream); break;
-    case 16: launch_topk_g<16>(ta, peak, K, pv, bv, stream); break;
-    default: launch_topk_g<64>(ta, peak, K, pv, bv, stream); break;
-  }
+  with_group(ta.group, [&](auto g) { launch_topk_g<g()>(ta, peak, K, pv, bv, stream); });
 }
 
 void launch_targets_hits_peaks(const TargetsHitsArgs& ha, const uint8_t* peak, const ProblemView& pv, const BatchView& bv,
                                hipStream_t stream) {
   if (ha.ta.view.n_rec <= 0 || ha.ta.T <= 0) return;
-  switch (ha.ta.group) {
-    case 4: launch_hits_g<4>(ha, peak, pv, bv, stream); break;
-    case 16: launch_hits_g<16>(ha, peak, pv, bv, stream); break;
-    default: launch_hits_g<64>(ha, peak, pv, bv, stream); break;
-  }
+  with_group(ha.ta.group, [&](auto g) { launch_hits_g<g()>(ha, peak, pv, bv, stream); });
 }
 
 }  // namespace dev

@@ -4,7 +4,8 @@
 //
 // The kernel reads a chunk's pair rows where targets_select_kernel stored them just before on the same stream
 // (pairs[li * T + t], li the record's index within the chunk: the part of the profile scratch behind the chunk's
-// entries) and never the profile. No atomics on global memory, no kernel waits on another block, no LDS; ordering is
+// entries) and never the profile: a group owns a record, not a pair, and takes only the group maximum and the launch
+// splitter from targets_pair.hpp. No atomics on global memory, no kernel waits on another block, no LDS; ordering is
 // launch order.
 //   targets_rank_kernel<G>  a group of G consecutive lanes (4, 16 or 64; aligned to G, so __shfl_xor steps below G
 //                           stay inside it) owns record li of the chunk. M rounds (M is a kernel argument, so the trip
@@ -23,26 +24,16 @@
 #include "kernel_common.hpp"
 #include "moc/kernel_bounds.hpp"
 #include "moc/runtime/hip_check.hpp"
+#include "targets_pair.hpp"
 
 namespace moc {
 namespace dev {
 
 using namespace kc;
+using namespace tp;
 
 namespace {
 constexpr int kBlock = bounds::kTargetsThreads;
-constexpr int64_t kMaxBlocksPerLaunch = int64_t{1} << 30;  // below the 2^31 - 1 grid limit
-
-template <int G>
-__device__ __forceinline__ unsigned long long group_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) {
-    const int lo = __shfl_xor(static_cast<int>(v), d, 64);
-    const int hi = __shfl_xor(static_cast<int>(v >> 32), d, 64);
-    v = max_u64(v, (static_cast<unsigned long long>(static_cast<uint32_t>(hi)) << 32) | static_cast<uint32_t>(lo));
-  }
-  return v;
-}
 }  // namespace
 
 // records [rec_at, rec_at + gridDim.x * (kBlock / G)) of the chunk's view.n_rec
@@ -96,23 +87,15 @@ void preload_targets_rank_kernels() {
 namespace {
 template <int G>
 void launch_targets_rank_g(const TargetsRankArgs& ra, hipStream_t stream) {
-  constexpr int64_t kGroupsPerBlock = kBlock / G;
-  const int64_t n_rec = ra.view.n_rec;
-  for (int64_t rec_at = 0; rec_at < n_rec;) {
-    const int64_t blocks = std::min<int64_t>((n_rec - rec_at + kGroupsPerBlock - 1) / kGroupsPerBlock, kMaxBlocksPerLaunch);
-    hipLaunchKernelGGL((targets_rank_kernel<G>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, stream, ra, rec_at);
-    rec_at += blocks * kGroupsPerBlock;
-  }
+  for_each_launch<G>(ra.view.n_rec, [&](unsigned blocks, int64_t rec_at) {
+    hipLaunchKernelGGL((targets_rank_kernel<G>), dim3(blocks), dim3(kBlock), 0, stream, ra, rec_at);
+  });
 }
 }  // namespace
 
 void launch_targets_rank(const TargetsRankArgs& ra, hipStream_t stream) {
   if (ra.view.n_rec <= 0 || ra.T <= 0 || ra.M <= 0) return;
-  switch (ra.group) {
-    case 4: launch_targets_rank_g<4>(ra, stream); break;
-    case 16: launch_targets_rank_g<16>(ra, stream); break;
-    default: launch_targets_rank_g<64>(ra, stream); break;
-  }
+  with_group(ra.group, [&](auto g) { launch_targets_rank_g<g()>(ra, stream); });
 }
 
 }  // namespace dev

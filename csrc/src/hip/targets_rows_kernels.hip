@@ -4,8 +4,9 @@
 //
 // The kernels read a chunk's catalog profile where targets_select_kernel reads it (prof[poffsets[r] - base + o],
 // written by offset_profile_kernel just before on the same stream). A pair's target profile is the target's slice of
-// it plus at most one un-mutated boundary entry summed from the letters, which has the largest local offset. No
-// atomics on global memory, no kernel waits on another block, no LDS; ordering is launch order:
+// it plus at most one un-mutated boundary entry summed from the letters, which has the largest local offset: the
+// pair view of targets_pair.hpp, from which all three kernels start (its group reductions and launch splitter too).
+// No atomics on global memory, no kernel waits on another block, no LDS; ordering is launch order:
 //   targets_topk_kernel<G>          targets_select_kernel's ownership: a group of G consecutive lanes (4, 16 or 64;
 //                                   aligned to G, so __shfl_xor steps below G stay inside it) owns pair p = li * T + t
 //                                   of the chunk (64-bit). The group sums the boundary entry first; it is one more
@@ -34,99 +35,17 @@
 #include "kernel_common.hpp"
 #include "moc/kernel_bounds.hpp"
 #include "moc/runtime/hip_check.hpp"
+#include "targets_pair.hpp"
 
 namespace moc {
 namespace dev {
 
 using namespace kc;
+using namespace tp;
 
 namespace {
 constexpr int kBlock = bounds::kTargetsThreads;
-constexpr int64_t kMaxBlocksPerLaunch = int64_t{1} << 30;  // below the 2^31 - 1 grid limit
 constexpr int kHeld = 4;  // slice keys a lane keeps in registers (topk_select_kernel's held[])
-
-template <int G>
-__device__ __forceinline__ unsigned long long group_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) {
-    const int lo = __shfl_xor(static_cast<int>(v), d, 64);
-    const int hi = __shfl_xor(static_cast<int>(v >> 32), d, 64);
-    v = max_u64(v, (static_cast<unsigned long long>(static_cast<uint32_t>(hi)) << 32) | static_cast<uint32_t>(lo));
-  }
-  return v;
-}
-
-template <int G>
-__device__ __forceinline__ int group_sum_i32(int v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// What a group knows about its pair (targets_summary_kernels.hip's): all three kernels start from it.
-struct Pair {
-  int64_t r = 0, pb = 0, b = 0;  // batch-wide record, its profile's first entry in `prof`, the target's start
-  int64_t p = 0;                 // batch-wide pair index r * T + t
-  int t = 0, L2 = 0;
-  int slice = 0;          // entries of the pair's slice; local offset of its boundary entry
-  bool active = false;    // the group has a pair (uniform over the group)
-  bool fits = false;
-  bool boundary = false;  // the boundary entry takes part
-  const uint8_t* rec = nullptr;
-};
-
-__device__ __forceinline__ Pair pair_of(const TargetsArgs& ta, const ProblemView& pv, const BatchView& bv, int64_t pair,
-                                        int64_t n_pairs) {
-  Pair p;
-  p.active = pair < n_pairs;
-  int len = 0;
-  if (p.active) {
-    const int64_t li = pair / ta.T;
-    p.t = static_cast<int>(pair - li * ta.T);
-    p.r = ta.view.rec0 + li;
-    p.p = p.r * ta.T + p.t;
-    MOC_DCHECK(li >= 0 && li < ta.view.n_rec && p.r >= 0 && p.r < bv.n && p.t >= 0 && p.t < ta.T);
-    p.rec = bv.codes + (bv.offsets[p.r] - bv.offsets[0]);
-    p.L2 = static_cast<int>(bv.offsets[p.r + 1] - bv.offsets[p.r]);
-    p.b = ta.starts[p.t];
-    len = static_cast<int>(ta.starts[p.t + 1] - p.b);
-    p.pb = chunk_first(ta.view, p.r);
-    MOC_DCHECK(p.b >= 0 && len >= 1 && p.b + len <= pv.L1);
-  }
-  p.fits = p.active && p.L2 >= 1 && p.L2 <= len && p.L2 <= pv.L1;
-  p.slice = p.fits ? len - p.L2 : 0;
-  p.boundary = p.fits && (pv.semantics == static_cast<int>(Semantics::Spec) || p.slice == 0);
-  return p;
-}
-
-// this lane's share of the boundary entry's score (0 where the entry does not take part)
-template <int G>
-__device__ __forceinline__ int boundary_part(const Pair& p, const ProblemView& pv, int sub) {
-  int bsum = 0;
-  if (p.boundary) {
-    const int64_t a0 = p.b + p.slice;  // the entry's first Seq1 letter; its last is b + len - 1 < L1
-    for (int l = sub; l < p.L2; l += G) {
-      const int c = p.rec[l];
-      MOC_DCHECK(c >= 0 && c < kLutStride);
-      MOC_DCHECK(a0 + l >= 0 && a0 + l < pv.L1);
-      bsum += pv.lut[(c << 5) + pv.seq1[a0 + l]];
-    }
-  }
-  return bsum;
-}
-
-// entry o of the pair's slice
-__device__ __forceinline__ ProfileEntry slice_entry(const TargetsArgs& ta, const Pair& p, int o) {
-  MOC_DCHECK(o >= 0 && o < p.slice);
-  MOC_DCHECK(p.b + o < chunk_count(ta.view, p.r));  // the slice lies inside the record's entries
-  return ta.view.prof[p.pb + p.b + o];
-}
-
-__device__ __forceinline__ int pair_threshold(const TargetsHitsArgs& ha, const Pair& p) {
-  if (!p.active || !ha.thresholds) return ha.min_score;
-  MOC_DCHECK(p.p >= 0 && p.p < ha.ta.view.n_total * ha.ta.T);
-  return ha.thresholds[p.p];
-}
 }  // namespace
 
 // pairs [pair0, pair0 + gridDim.x * (kBlock / G)) of the chunk's n_pairs = n_rec * T
@@ -138,7 +57,7 @@ __global__ __launch_bounds__(256) void targets_topk_kernel(TargetsArgs ta, int K
   const int sub = threadIdx.x & (G - 1);
   const Pair p = pair_of(ta, pv, bv, pair0 + static_cast<int64_t>(blockIdx.x) * kGroupsPerBlock + (threadIdx.x / G), n_pairs);
   // every lane of the wave reaches the shuffles (the loops are the only divergent parts)
-  const int bsum = group_sum_i32<G>(boundary_part<G>(p, pv, sub));
+  const int bsum = group_sum_i32<G>(boundary_part(p, pv, sub, G));
   const int C = p.slice + (p.boundary ? 1 : 0);
   // the boundary entry's key: one more key of the lane the stride would give its offset to
   const unsigned long long bkey =
@@ -194,7 +113,7 @@ __global__ __launch_bounds__(256) void targets_hits_count_kernel(TargetsHitsArgs
   int count = 0;  // slice < 2^31
   for (int o = sub; o < p.slice; o += G) count += slice_entry(ta, p, o).score >= thr ? 1 : 0;
   // every lane of the wave reaches the shuffles
-  const int bsum = group_sum_i32<G>(boundary_part<G>(p, pv, sub));
+  const int bsum = group_sum_i32<G>(boundary_part(p, pv, sub, G));
   count = group_sum_i32<G>(count);
   if (p.active && sub == 0) {
     MOC_DCHECK(p.p >= 0 && p.p + 1 <= ta.view.n_total * ta.T);
@@ -225,7 +144,7 @@ __global__ __launch_bounds__(256) void targets_hits_compact_kernel(TargetsHitsAr
   // the wave's longest slice, in a scalar register: the loop is wave-uniform and every lane reaches every ballot
   const int trips = __builtin_amdgcn_readfirstlane(wave_max_i32(slice));
   int bpart = 0;
-  if (work) bpart = boundary_part<G>(p, pv, sub);
+  if (work) bpart = boundary_part(p, pv, sub, G);
   const int bsum = group_sum_i32<G>(bpart);
   int base = 0;  // hits of the passes before this one (group-uniform)
   for (int o0 = 0; o0 < trips; o0 += G) {
@@ -262,17 +181,6 @@ void preload_targets_rows_kernels() {
 }
 
 namespace {
-// fn(blocks, pair0) for every launch over n_pairs pairs with G lanes each, split below the grid limit
-template <int G, class Fn>
-void for_each_launch(int64_t n_pairs, Fn&& fn) {
-  constexpr int64_t kGroupsPerBlock = kBlock / G;
-  for (int64_t pair0 = 0; pair0 < n_pairs;) {
-    const int64_t blocks = std::min<int64_t>((n_pairs - pair0 + kGroupsPerBlock - 1) / kGroupsPerBlock, kMaxBlocksPerLaunch);
-    fn(static_cast<unsigned>(blocks), pair0);
-    pair0 += blocks * kGroupsPerBlock;
-  }
-}
-
 template <int G>
 void launch_topk_g(const TargetsArgs& ta, int K, const ProblemView& pv, const BatchView& bv, hipStream_t stream) {
   const int64_t n_pairs = ta.view.n_rec * ta.T;
@@ -303,20 +211,12 @@ void launch_hits_g(const TargetsHitsArgs& ha, const ProblemView& pv, const Batch
 
 void launch_targets_topk(const TargetsArgs& ta, int K, const ProblemView& pv, const BatchView& bv, hipStream_t stream) {
   if (ta.view.n_rec <= 0 || ta.T <= 0) return;
-  switch (ta.group) {
-    case 4: launch_topk_g<4>(ta, K, pv, bv, stream); break;
-    case 16: launch_topk_g<16>(ta, K, pv, bv, stream); break;
-    default: launch_topk_g<64>(ta, K, pv, bv, stream); break;
-  }
+  with_group(ta.group, [&](auto g) { launch_topk_g<g()>(ta, K, pv, bv, stream); });
 }
 
 void launch_targets_hits(const TargetsHitsArgs& ha, const ProblemView& pv, const BatchView& bv, hipStream_t stream) {
   if (ha.ta.view.n_rec <= 0 || ha.ta.T <= 0) return;
-  switch (ha.ta.group) {
-    case 4: launch_hits_g<4>(ha, pv, bv, stream); break;
-    case 16: launch_hits_g<16>(ha, pv, bv, stream); break;
-    default: launch_hits_g<64>(ha, pv, bv, stream); break;
-  }
+  with_group(ha.ta.group, [&](auto g) { launch_hits_g<g()>(ha, pv, bv, stream); });
 }
 
 }  // namespace dev
