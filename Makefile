@@ -54,7 +54,7 @@ COMM_OBJS := $(OBJ)/comm/comm.o $(OBJ)/comm/mpi_device_comm.o
 RCCL_OBJS := $(OBJ)/comm/rccl_comm.o
 HEADERS   := $(shell find csrc/include -name '*.h' -o -name '*.hpp')
 
-.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san hits-san wire-san peaks-san summary-san targets-san targets-summary-san targets-rows-san targets-peaks-san targets-rank-san
+.PHONY: all build lib clean run runOn2 test unit asan tsan debug-kernels profile-san tile-plan-san report-san hits-san wire-san peaks-san summary-san targets-san targets-summary-san targets-rows-san targets-peaks-san targets-rank-san far-san
 
 all: build
 build: lib final $(GPU_PLUGIN)
@@ -300,6 +300,14 @@ targets-rank-san: $(BUILD)/targets_rank_san
 	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/targets_rank_san
 $(BUILD)/targets_rank_san: csrc/tests/targets_rank_san.cpp $(PSAN_OBJS) $(HEADERS)
 	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/targets_rank_san.cpp $(PSAN_OBJS) -ldl
+
+# stand-alone ASan/UBSan check of the host code that carries 64-bit letter offsets (unpack33, unpack5, the P33 byte
+# ranges, expand_offsets, wire_dense_offsets, decode_wire_cpu, staged_chunks) at bit, byte and letter positions past
+# 2^31 and 2^32, on an anonymous mapping of 6 GiB of which only the written pages are touched (own main, host code only)
+far-san: $(BUILD)/far_offsets_san
+	ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1 $(BUILD)/far_offsets_san
+$(BUILD)/far_offsets_san: csrc/tests/far_offsets_san.cpp $(PSAN_OBJS) $(HEADERS)
+	$(CXX) $(PSAN_FLAGS) -o $@ csrc/tests/far_offsets_san.cpp $(PSAN_OBJS) -ldl
 
 # parser throughput (count vs fill, SIMD A/B): build/fill_bench [records]
 $(BUILD)/fill_bench: tools/fill_bench.cpp $(CPU_OBJS) $(HEADERS)

@@ -31,7 +31,8 @@ import torch  # noqa: E402
 
 from mpi_openmp_cuda_amd import (HipSearchEngine, Problem, Semantics, TargetSet, _lib, search_cpu,  # noqa: E402
                                  search_hits_cpu, search_profile_cpu, search_report_cpu, search_summary_cpu,
-                                 search_targets_cpu, search_targets_summary_cpu, search_topk_cpu)
+                                 search_targets_cpu, search_targets_hits_cpu, search_targets_rank_cpu,
+                                 search_targets_summary_cpu, search_targets_topk_cpu, search_topk_cpu)
 from mpi_openmp_cuda_amd.ops.align import as_triples  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -117,12 +118,17 @@ def side_stream():
     return _side[0]
 
 
-def both_fills(case, want, run, **kw):
-    """run(codes_t, offsets_t, h_offsets) -> rows, for both neighbour fills: equal to ``want`` and to each other."""
+def both_fills(case, want, run, batch=device_batch, **kw):
+    """run(codes_t, offsets_t, h_offsets) -> rows, for both neighbour fills: equal to ``want`` and to each other.
+    ``batch``: what lays the case on the device, ``device_batch`` or a maker of the same signature (whose ``restore``,
+    if it has one, runs after each fill)."""
     got = {}
     for fill in FILLS:
         with torch.cuda.stream(side_stream()):
-            got[fill] = run(*device_batch(case, fill, **kw))
+            try:
+                got[fill] = run(*batch(case, fill, **kw))
+            finally:
+                getattr(batch, "restore", lambda: None)()
         msg = differing(got[fill], want)
         assert not msg, f"c0 {case.c0} fill {fill} {kw}: {msg}"
     assert np.array_equal(got["A"], got["continue"])
@@ -316,30 +322,35 @@ def test_mixed_slice(engine, sem):
 
 
 # ---- 6. context-parallel keys -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["tile16", "tile16_slide"])
-def test_context_parallel_keys(engine, name):
+def keys_case(engine, name, c0, g, **kw):
+    """search_keys_device over two parts, their uint64 maximum, finalize_keys_device: the rows of ``solve_device``."""
     want = rows_of(name, Semantics.REFERENCE)
     flip = torch.tensor(-2**63, dtype=torch.int64, device=DEV)
+    case = family_case(name, c0)
+    n = case.sub.n
+    engine.set_problem(case.sub.weights, case.sub.seq1)
+
+    def run(codes_t, offs_t, h_offs):
+        parts = []
+        for part in range(2):
+            keys = Guarded((n,), torch.int64, 1)  # 8-byte aligned, off the 16-byte boundary
+            engine.search_keys_device(codes_t, offs_t, h_offs, part, 2, keys.out)
+            st = engine.stats()
+            assert "tile16" in st["kernels"] and "tile16" in st["forms"], st
+            keys.rows()
+            parts.append(keys.out)
+        best = torch.stack([p ^ flip for p in parts]).max(dim=0).values ^ flip  # uint64 max
+        out = Guarded((n, 3), torch.int32, g)
+        engine.finalize_keys_device(codes_t, offs_t, h_offs, best, out.out)
+        return out.rows()
+
+    both_fills(case, want, run, **kw)
+
+
+@pytest.mark.parametrize("name", ["tile16", "tile16_slide"])
+def test_context_parallel_keys(engine, name):
     for i, s in enumerate(FEW + (FAR - 32,)):
-        case = family_case(name, 32 + s)
-        n = case.sub.n
-        engine.set_problem(case.sub.weights, case.sub.seq1)
-
-        def run(codes_t, offs_t, h_offs):
-            parts = []
-            for part in range(2):
-                keys = Guarded((n,), torch.int64, 1)  # 8-byte aligned, off the 16-byte boundary
-                engine.search_keys_device(codes_t, offs_t, h_offs, part, 2, keys.out)
-                st = engine.stats()
-                assert "tile16" in st["kernels"] and "tile16" in st["forms"], st
-                keys.rows()
-                parts.append(keys.out)
-            best = torch.stack([p ^ flip for p in parts]).max(dim=0).values ^ flip  # uint64 max
-            out = Guarded((n, 3), torch.int32, 1 + i % 3)
-            engine.finalize_keys_device(codes_t, offs_t, h_offs, best, out.out)
-            return out.rows()
-
-        both_fills(case, want, run, d=1 if s == 13 else 0)
+        keys_case(engine, name, 32 + s, 1 + i % 3, d=1 if s == 13 else 0)
 
 
 # ---- 7. feature kernels, device forms: the tile-edge batch of tests/test_gpu_topk.py ------------------------------
@@ -356,7 +367,9 @@ def targets_of(sub):
     return TargetSet(sub.seq1, [0, TARGET_LENS[0], sub.L1])
 
 
-def feature_forms(eng, sem, shifts, chunked=False):
+def feature_forms(eng, sem, shifts, chunked=False, batch=device_batch):
+    """Every device form of the profile family at the first offsets ``shifts``: 32 + s for a small s, the offset
+    itself from FAR on."""
     sub = feature_sub()
     n, total = sub.n, int(sub.offsets[-1])
     ts = targets_of(sub)
@@ -367,6 +380,10 @@ def feature_forms(eng, sem, shifts, chunked=False):
     summ, hist = oracle(key + ("summary",), lambda: search_summary_cpu(sub, BINS, LO, WIDTH, sem))
     trows = oracle(key + ("targets",), lambda: search_targets_cpu(sub, ts, sem))
     tsumm, thist = oracle(key + ("tsummary",), lambda: search_targets_summary_cpu(sub, ts, BINS, LO, WIDTH, sem))
+    ttop = {r: oracle(key + ("ttop", r), lambda: search_targets_topk_cpu(sub, ts, 3, sem, radius=r)) for r in (0, 1)}
+    thits = {r: oracle(key + ("thits", r), lambda: search_targets_hits_cpu(sub, ts, within=20, semantics=sem, radius=r))
+             for r in (0, 1)}
+    trank = oracle(key + ("trank",), lambda: search_targets_rank_cpu(sub, ts, 2, sem))
     best = rows_of(FEATURE, sem)
     counts1, marks1 = oracle(key + ("report1",), lambda: search_report_cpu(sub, best, marks=True))
     counts3, marks3 = oracle(key + ("report3",), lambda: search_report_cpu(sub, top[0], marks=True))
@@ -377,9 +394,9 @@ def feature_forms(eng, sem, shifts, chunked=False):
         assert all(k in st["kernels"] for k in kernels) and (not chunked or st["chunks"] > 1), st
 
     for i, s in enumerate(shifts):
-        case = family_case(FEATURE, 32 + s if s != FAR else FAR)
+        case = family_case(FEATURE, 32 + s if s < FAR else s)
         g = 1 + i % 3
-        kw = dict(d=7) if s == 13 else {}
+        kw = dict(batch=batch, **(dict(d=7) if s == 13 else {}))
 
         def profile(c, o, h):
             out = Guarded((len(prof), 2), torch.int32, g)
@@ -435,6 +452,39 @@ def feature_forms(eng, sem, shifts, chunked=False):
             return s_out.rows()
 
         both_fills(case, tsumm, targets_summary, **kw)
+
+        for radius in (0, 1):
+            peaks = ["targets_peaks"] if radius else []
+
+            def targets_topk(c, o, h):
+                out = Guarded((n, ts.T, 3, 3), torch.int32, g)
+                eng.solve_targets_topk_device(c, o, h, ts, 3, out.out, radius=radius)
+                ran("profile", "targets_topk", *peaks)
+                return out.rows()
+
+            both_fills(case, ttop[radius], targets_topk, **kw)
+
+            def targets_hits(c, o, h):
+                w_rows, w_toff = thits[radius]
+                best_t = eng.solve_targets_device(c, o, h, ts)  # within 20 of each pair's best, as the CPU call forms it
+                thr_t = (best_t[:, :, 0].to(torch.int64) - 20).clamp(-2**31, 2**31 - 1).to(torch.int32).contiguous()
+                rows = Guarded((len(w_rows), 3), torch.int32, g)
+                toff = Guarded((n * ts.T + 1,), torch.int64, 1)
+                eng.solve_targets_hits_device(c, o, h, ts, thresholds_t=thr_t, cap=len(w_rows), rows_t=rows.out,
+                                              toffsets_t=toff.out, radius=radius)
+                ran("profile", "targets_hits", *peaks)
+                assert np.array_equal(toff.rows(), w_toff)
+                return rows.rows()
+
+            both_fills(case, thits[radius][0], targets_hits, **kw)
+
+        def targets_rank(c, o, h):
+            out = Guarded((n, 2, 4), torch.int32, g)
+            eng.solve_targets_rank_device(c, o, h, ts, 2, out.out)
+            ran("profile", "targets", "targets_rank")
+            return out.rows()
+
+        both_fills(case, trank, targets_rank, **kw)
 
         if chunked:
             continue
